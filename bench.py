@@ -1,6 +1,12 @@
 """Headline benchmark: occupancy query-points/sec of the PPSurf 50NN decoder path at gen_resolution_global=257.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the inputs, decodes W untimed chunks, times exactly K chunks and prints one JSON
+line (`value`, `ms_per_step` = milliseconds per timed chunk).  --dump-outputs DIR then writes what the last timed chunk returned to a caller of
+ChunkPipeline.run as DIR/logits.npy (float32 [Q, 2]) and DIR/occupancy.npy (float32 [Q]); the inputs are seeded, so two builds given the same
+arguments can be compared output for output.  --full adds every other measurement described below (the per-kernel passes and roofline,
+the other decoder dtype, dense queries, shapes/hour, configs 2 and 5, the fit step, the CPU baseline; at N > 1 `strong` and `fit`).
 
 N > 1: one rank per GPU over RCCL.  Either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or plainly as `python bench.py --gpus N`: the script then re-executes itself under
@@ -11,10 +17,11 @@ synthetic 100k-point cloud (configs/poco.yaml:51-52, configs/ppsurf_50nn.yaml): 
 normalisation -> interpolation-attention + PointNet + MLP -> occupancy, through the PRODUCT's chunk loop
 (ppsurf_amd.decoder.ChunkPipeline, the class reconstruct.OccupancyField drives) and the product's C entry point
 pps_decode_fwd(_events)_f32.  The K chunks are DISTINCT: the first region-growing round of create_volume over as many synthetic
-shapes as it takes (47 full chunks per shape at R = 257).  Inputs (clouds, query lists, per-point tables, weights) are resident
-in HBM before the timed region.
+shapes as it takes (33-34 full chunks per shape at R = 257), up to MAX_SHAPES = 8 shapes (267 distinct chunks); a longer run goes
+through the same chunk list again, in the same order, so that setting up does not grow with --steps.  Inputs (clouds, query lists,
+per-point tables, weights) are resident in HBM before the timed region.
 
-N > 1 (the driver's SCALE run is this one command per N) puts THREE measurements on the one JSON line:
+With --full, N > 1 (the driver's SCALE run is this one command per N) puts THREE measurements on the one JSON line:
   * `value` -- shape-level replicas: every rank decodes its own chunks of its own shapes, no collective on the data path (what a test-set
     reconstruction with PPS_SHARD=shapes does; `scaling: weak`);
   * `strong` -- SURVEY 8(e)'s query-block sharding: ONE R = 257 shape reconstructed by all ranks together (PPS_SHARD=queries: every growth /
@@ -27,12 +34,12 @@ N > 1 (the driver's SCALE run is this one command per N) puts THREE measurements
 --single-rank-collectives (with --gpus 1): a ONE-rank process group runs the N > 1 code path -- every collective call site executes on the real
 backend (RCCL accepts a one-rank communicator) on a 1-GPU box.
 
-Extra keys on the same JSON line (skipped with --quick): `shapes_per_hour` (whole R=257 reconstructions by the product driver; N=1: first
-shape and steady state, N>1: every rank reconstructs its own shapes, the figure is all shapes of all ranks / the slowest rank's time),
-and at N=1 only `fit_ms_per_step` (BASELINE config 3, bf16-mixed, B=10) and `cpu_baseline`.
+Extra keys on the same JSON line with --full (--full --quick keeps only the per-kernel passes of the chunk loop and the roofline):
+`shapes_per_hour` (whole R=257 reconstructions by the product driver; N=1: first shape and steady state, N>1: every rank reconstructs its own
+shapes, the figure is all shapes of all ranks / the slowest rank's time), and at N=1 only `fit_ms_per_step` (BASELINE config 3, bf16-mixed,
+B=10) and `cpu_baseline`.
 
-The timed region is at least MIN_TIMED_S long: when `steps` distinct chunks take less, the same chunk list is decoded `repeats` times
-(`steps` is reported as given, `repeats` and `timed_s` next to it; ms_per_step and value are per chunk over all repeats).
+The timed region is the `steps` chunks, once (`repeats` 1, `timed_s` = steps x ms_per_step): the caller sets its length with --steps.
 """
 import argparse
 import json
@@ -54,7 +61,7 @@ Q_CHUNK = 50_000
 K_PROJ = 64
 P_LOCAL = 50
 RES = 257
-MIN_TIMED_S = 2.0                              # the timed region is stretched to this by repeating the chunk list (see `repeats`)
+MAX_SHAPES = 8                                 # synthetic shapes per rank in the chunk list (each is set up before the clock: cloud, latents, table, band)
 ALG_MFLOP_PER_QUERY = 53.21                    # conv+matmul FLOPs of the reference's from_latent at P=50
 # dominant kernel (interp_pool_kernel).  Reference work it replaces per query, poco_model.py:400-414:
 # 64 neighbours x (fc1 66304 + fc2 65536 + fc3 65536 + fc_query 16384 + fc_value 65536) MAC + 16384 MAC pooling
@@ -107,8 +114,9 @@ def cpu_baseline(sd, cloud, qry, lat, q_call=20_000, reps=3):
         return time.time() - t0
 
     host = os.cpu_count() or 1
+    cap = min(host, int(os.environ.get('OMP_NUM_THREADS') or host))   # a thread budget the environment sets holds
     tried = {}
-    for th in sorted({t for t in (8, 32, 64, 128, host) if t <= host}):
+    for th in sorted({t for t in (8, 32, 64, 128, cap) if t <= cap}):
         torch.set_num_threads(th)
         os.environ['OMP_NUM_THREADS'] = str(th)
         call(qry[:200])                                          # thread pool warm-up
@@ -179,13 +187,14 @@ def rank_values(x, rank, world, dist, red_dev):
 
 
 def build_work(plan, n_chunks, rank, dev, queries='band'):
-    """Resident inputs: as many synthetic shapes as it takes to give every step its own chunk of a real first-round band."""
+    """Resident inputs: as many synthetic shapes as it takes (at most MAX_SHAPES) to give every step its own chunk of a real first-round band;
+    beyond the chunks of MAX_SHAPES shapes the list starts over."""
     import bench_workloads as workloads
     from ppsurf_amd.decoder import ChunkPipeline
     from ppsurf_amd.synthetic import make_cloud, make_latents
     shapes, work = [], []                                        # work: (pipeline, chunk) per step
     s = 0
-    while len(work) < n_chunks:
+    while len(work) < n_chunks and s < MAX_SHAPES:
         cloud = make_cloud(N_POINTS, seed=42 + 1000 * rank + s)
         pts = torch.from_numpy(cloud).to(dev)
         lat = make_latents(256, N_POINTS, seed=77 + s)
@@ -199,25 +208,24 @@ def build_work(plan, n_chunks, rank, dev, queries='band'):
         shapes.append({'cloud': cloud, 'lat': lat, 'band': n_band, 'chunks': len(chunks)})
         work += [(pipe, c) for c in chunks]
         s += 1
-    return shapes, work[:n_chunks]
+    return shapes, [work[i % len(work)] for i in range(n_chunks)]
 
 
-def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_TIMED_S):
-    """`warmup` untimed chunks, then `repeats` passes over the next `steps` DISTINCT chunks between barrier + synchronize on both sides, handed to
+def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=0.0, extra=True):
+    """`warmup` untimed chunks, then `repeats` passes over the next `steps` chunks between barrier + synchronize on both sides, handed to
     the product's chunk loop the way reconstruct.OccupancyField hands it a growth round: ChunkPipeline.run(list of the shape's chunks), which deals
-    long lists to two HIP streams (ChunkPipeline lanes).  Per-kernel HIP events cannot be read under two lanes (a kernel's interval then contains
-    the moments it shares the chip), so the per-stage times and the roofline come from a SECOND, single-lane pass over the same chunks
-    (`single_lane`), timed the same way.
-    Returns the max-over-ranks wall time, this rank's own time, repeats, per-stage HIP-event means (ms) and the last occupancy."""
+    long lists to two HIP streams (ChunkPipeline lanes).  repeats = 1 unless min_timed_s > 0 stretches the timed region to at least that many
+    seconds (the extra legs of --full; the headline times `steps` chunks exactly).
+    extra: two more passes over the same chunks.  Per-kernel HIP events cannot be read under two lanes (a kernel's interval then contains the
+    moments it shares the chip), so the per-stage times and the roofline come from a SECOND, single-lane pass (`single_lane`), timed the same way;
+    the first pass is the timed loop again with one lane (`one_lane_loop`).
+    Returns the max-over-ranks wall time, this rank's own time, repeats, the last chunk's (logits, occupancy) and, with `extra`, per-stage
+    HIP-event means (ms) and the two passes' times."""
     import bench_workloads as workloads
     from ppsurf_amd import sharding
     from ppsurf_amd.fit import HostGcPacer
-    torch.cuda.synchronize()
-    tw = time.perf_counter()
     for pipe, c in work[:warmup]:
         pipe.run([c])
-    torch.cuda.synchronize()
-    est = (time.perf_counter() - tw) / max(warmup, 1)              # s per chunk, first-call overheads included: an over-estimate
     timed = work[warmup:warmup + steps]
     groups = []                                                   # consecutive chunks of one shape: one run() call each
     for pipe, c in timed:
@@ -226,17 +234,22 @@ def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_
         else:
             groups.append((pipe, [c]))
     repeats = 1
-    if warmup > 0 and min_timed_s > 0:
-        # one more untimed pass over the timed chunks' first group gives a steady-state estimate (and allocates the second lane's buffers)
+    if warmup > 0:
+        # untimed, issued as the timed loop issues them: the first group whole and every other shape's first chunks (the second lane's buffers and
+        # a whole group's result tensors exist before the clock starts); the first group's time is a steady-state estimate
         probe = groups[0]
         torch.cuda.synchronize()
         tw = time.perf_counter()
         probe[0].run(probe[1])
         torch.cuda.synchronize()
         est = (time.perf_counter() - tw) / len(probe[1])
+        seen = {id(probe[0])}
         for pipe, cs in groups[1:]:
-            pipe.run(cs[:min(len(cs), 4)])
-        repeats = max(1, int(math.ceil(min_timed_s / (est * steps))))
+            if id(pipe) not in seen:
+                seen.add(id(pipe))
+                pipe.run(cs[:min(len(cs), 4)])
+        if min_timed_s > 0:
+            repeats = max(1, int(math.ceil(min_timed_s / (est * steps))))
     repeats = int(round(sharding.max_over_ranks(float(repeats), red_dev)))
     pacer = HostGcPacer().__enter__()                             # as the predict loop of ppsurf_amd.runner decodes the chunks of a shape
     if dist is not None:
@@ -244,7 +257,7 @@ def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(repeats):
-        for pipe, cs in groups:                                   # `steps` distinct chunks of Q_CHUNK queries, `repeats` times
+        for pipe, cs in groups:                                   # `steps` chunks of Q_CHUNK queries, `repeats` times
             res = pipe.run(cs, want_occ=True)
             pacer.tick()
     torch.cuda.synchronize()
@@ -252,8 +265,13 @@ def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_
     if dist is not None:
         dist.barrier()
     dt = sharding.max_over_ranks(time.perf_counter() - t0, red_dev)
-    occ = res[-1][1]
-    assert bool(torch.isfinite(occ).all())
+    last = res[-1]
+    assert bool(torch.isfinite(last[1]).all())
+    out = {'dt': dt, 'mine': mine, 'repeats': repeats, 'last': last, 'chunks': steps * repeats,
+           'lanes': max(min(pipe.lanes if pipe.lanes is not None else (2 if len(cs) >= pipe.LANE_MIN_CHUNKS else 1), len(cs)) for pipe, cs in groups)}
+    if not extra:
+        pacer.close()
+        return out
     # ---- the SAME loop with the chunk lanes switched off: what the second HIP stream is worth (the difference between `value`
     #      and the per-kernel pass below is NOT the lanes' gain -- that pass issues one chunk per call with HIP events between the kernels)
     saved = [(pipe, pipe.lanes) for pipe, _ in groups]
@@ -269,7 +287,6 @@ def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_
     one_lane = (time.perf_counter() - t2) / (repeats * steps)
     for pipe, ln in saved:
         pipe.lanes = ln
-    lanes = max(min(pipe.lanes if pipe.lanes is not None else (2 if len(cs) >= pipe.LANE_MIN_CHUNKS else 1), len(cs)) for pipe, cs in groups)
     # ---- single-lane pass with HIP events around every kernel inside the product call: stage times, roofline -----------------------------------
     n_ev = min(len(timed), 100)
     ev = [workloads.HipEvents(6) for _ in range(n_ev)]
@@ -282,8 +299,8 @@ def chunk_loop(work, steps, warmup, rank, world, dist, red_dev, min_timed_s=MIN_
     single = (time.perf_counter() - t1) / n_ev
     pacer.close()
     stage_ms = {name: float(np.mean([e.elapsed_ms(j, j + 1) for e in ev])) for j, name in enumerate(STAGES)}
-    return {'dt': dt, 'mine': mine, 'repeats': repeats, 'stage_ms': stage_ms, 'occ': occ, 'chunks': steps * repeats, 'lanes': lanes,
-            'single_lane_ms_per_step': single * 1e3, 'single_lane_steps': n_ev, 'one_lane_loop_ms_per_step': one_lane * 1e3}
+    out.update({'stage_ms': stage_ms, 'single_lane_ms_per_step': single * 1e3, 'single_lane_steps': n_ev, 'one_lane_loop_ms_per_step': one_lane * 1e3})
+    return out
 
 
 def pmc_traffic(dtype):
@@ -333,26 +350,30 @@ def roofline_block(dtype, stage_ms):
 
 
 def dtype_stats(dtype, r, world):
-    """Per-dtype figures of one chunk_loop result `r`."""
+    """Per-dtype figures of one chunk_loop result `r` (the per-kernel ones only when chunk_loop ran its extra passes)."""
     f16 = dtype == 'f16x3'
     peak, mult = (PEAK_F16_MFMA_TFLOPS, 3.0) if f16 else (PEAK_F32_MFMA_TFLOPS, 1.0)
     value = world * Q_CHUNK * r['chunks'] / r['dt']
     ms_step = r['dt'] / r['chunks'] * 1e3
+    out = {'value': value, 'unit': 'queries/s', 'ms_per_step': ms_step, 'repeats': r['repeats'], 'timed_s': r['dt'], 'lanes': r.get('lanes', 1),
+           'whole_path_algorithmic_tflops': ALG_MFLOP_PER_QUERY * 1e6 * value / world / 1e12,
+           'whole_path_algorithmic_frac': ALG_MFLOP_PER_QUERY * 1e6 * value / world / 1e12 / peak,
+           'whole_path_executed_mfma_frac': mult * sum(STAGE_EXEC_MFMA_PER_QUERY.values()) * 2048.0 * value / world / 1e12 / peak}
+    if 'stage_ms' not in r:
+        return out
     sm = r['stage_ms']
-    return {'value': value, 'unit': 'queries/s', 'ms_per_step': ms_step, 'repeats': r['repeats'], 'timed_s': r['dt'], 'stage_ms': sm,
-            'stage_mfma_frac': {n: STAGE_ALG_FLOP_PER_QUERY[n] * Q_CHUNK / (sm[n] * 1e-3) / 1e12 / peak for n in STAGES},      # algorithmic (8d)
-            'stage_mfma_frac_executed': {n: mult * STAGE_EXEC_MFMA_PER_QUERY[n] * 2048.0 * Q_CHUNK / (sm[n] * 1e-3) / 1e12 / peak for n in STAGES},
-            'lanes': r.get('lanes', 1),
-            # the timed loop again with ONE chunk lane (same calls, no events): value / this = what the second stream gains
-            'one_lane_loop': {'ms_per_step': r['one_lane_loop_ms_per_step'], 'value': world * Q_CHUNK / (r['one_lane_loop_ms_per_step'] * 1e-3),
-                              'lanes_gain': r['one_lane_loop_ms_per_step'] / ms_step - 1.0},
-            # the same chunks one at a time on ONE stream with HIP events around every kernel: what stage_ms / roofline / spatial_ms describe
-            'single_lane': {'ms_per_step': r['single_lane_ms_per_step'], 'value': world * Q_CHUNK / (r['single_lane_ms_per_step'] * 1e-3),
-                            'steps': r['single_lane_steps']},
-            'spatial_ms': r['single_lane_ms_per_step'] - sum(sm.values()),
-            'whole_path_algorithmic_tflops': ALG_MFLOP_PER_QUERY * 1e6 * value / world / 1e12,
-            'whole_path_algorithmic_frac': ALG_MFLOP_PER_QUERY * 1e6 * value / world / 1e12 / peak,
-            'whole_path_executed_mfma_frac': mult * sum(STAGE_EXEC_MFMA_PER_QUERY.values()) * 2048.0 * value / world / 1e12 / peak}
+    out.update({
+        'stage_ms': sm,
+        'stage_mfma_frac': {n: STAGE_ALG_FLOP_PER_QUERY[n] * Q_CHUNK / (sm[n] * 1e-3) / 1e12 / peak for n in STAGES},      # algorithmic (8d)
+        'stage_mfma_frac_executed': {n: mult * STAGE_EXEC_MFMA_PER_QUERY[n] * 2048.0 * Q_CHUNK / (sm[n] * 1e-3) / 1e12 / peak for n in STAGES},
+        # the timed loop again with ONE chunk lane (same calls, no events): value / this = what the second stream gains
+        'one_lane_loop': {'ms_per_step': r['one_lane_loop_ms_per_step'], 'value': world * Q_CHUNK / (r['one_lane_loop_ms_per_step'] * 1e-3),
+                          'lanes_gain': r['one_lane_loop_ms_per_step'] / ms_step - 1.0},
+        # the same chunks one at a time on ONE stream with HIP events around every kernel: what stage_ms / roofline / spatial_ms describe
+        'single_lane': {'ms_per_step': r['single_lane_ms_per_step'], 'value': world * Q_CHUNK / (r['single_lane_ms_per_step'] * 1e-3),
+                        'steps': r['single_lane_steps']},
+        'spatial_ms': r['single_lane_ms_per_step'] - sum(sm.values())})
+    return out
 
 
 DTYPE_NOTE = {
@@ -369,7 +390,11 @@ def main():
     ap.add_argument('--steps', type=int, default=None, help='default 200 (weak: chunks) / 3 (strong: whole reconstructions)')
     ap.add_argument('--warmup', type=int, default=None, help='default 10 (weak) / 1 (strong)')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak')
-    ap.add_argument('--quick', action='store_true', help='query throughput only: no shapes/hour, fit step or CPU baseline legs')
+    ap.add_argument('--full', action='store_true', help='every measurement besides the headline: per-kernel passes and roofline, the other decoder dtype, '
+                    'dense queries, shapes/hour, configs 2 and 5, fit step, CPU baseline (N > 1: strong and fit)')
+    ap.add_argument('--quick', action='store_true', help='with --full: the per-kernel passes and roofline of the chunk loop only, none of the other legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed chunk returned (logits, occupancy) as DIR/<name>.npy, float32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--dtype', choices=['f32', 'f16x3'], default=HEADLINE_DTYPE, help='decoder dtype of the timed loop and of `value`')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N>1 ('nccl' = RCCL; 'gloo' only for single-GPU rehearsals)")
@@ -380,11 +405,14 @@ def main():
                          "(SURVEY 8d(i): 'every voxel of the Marching-Cubes grid')")
     ap.add_argument('--shapes', type=int, default=2, help='timed whole reconstructions per rank of the shapes/hour leg')
     ap.add_argument('--single-rank-collectives', action='store_true',
-                    help='--gpus 1 only: initialise a ONE-rank process group and run the N > 1 code path (strong + fit legs with every collective issued)')
-    ap.add_argument('--only', choices=['config2', 'config5', 'fit'], default=None, help='run ONE extra leg and print its object (profiling: tools/profile_config5.sh; the default line runs `fit` this way)')
+                    help='--gpus 1 only: initialise a ONE-rank process group and run the N > 1 code path (with --full: strong + fit legs with every '
+                         'collective issued)')
+    ap.add_argument('--only', choices=['config2', 'config5', 'fit'], default=None, help='run ONE extra leg and print its object (profiling: tools/profile_config5.sh; the --full line runs `fit` this way)')
     ap.add_argument('--fit-in-process', action='store_true', help='N = 1: the fit leg at the end of this process instead of in a process of its own')
-    ap.add_argument('--legs', default='replicas,strong,fit', help='N > 1: which measurements go on the line (comma list of replicas, strong, fit)')
+    ap.add_argument('--legs', default='replicas,strong,fit', help='N > 1 with --full: which measurements go on the line (comma list of replicas, strong, fit)')
     args = ap.parse_args()
+    if args.dump_outputs and (args.only or args.scaling == 'strong'):
+        ap.error('--dump-outputs writes the outputs of the weak-scaling chunk loop: not with --only or --scaling strong')
     if args.steps is None:
         args.steps = 200 if args.scaling == 'weak' else 3
     if args.warmup is None:
@@ -436,7 +464,9 @@ def main():
     sd = network_state_dict('ppsurf')
     plan = DecoderPlan(sd, dev, dtype=args.dtype)
     shapes, work = build_work(plan, args.warmup + args.steps, rank, dev, queries=args.queries)
-    r = chunk_loop(work, args.steps, args.warmup, rank, world, dist, red_dev)
+    r = chunk_loop(work, args.steps, args.warmup, rank, world, dist, red_dev, extra=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r['last'])
     per_rank = [Q_CHUNK * r['chunks'] / t for t in rank_values(r['mine'], rank, world, dist, red_dev)]
 
     out = None
@@ -450,26 +480,30 @@ def main():
             'backend': ('RCCL (torch.distributed nccl)' if args.backend == 'nccl' else args.backend) if multi else None,
             'per_rank_queries_per_s': {'min': min(per_rank), 'max': max(per_rank), 'all': per_rank},
             'dtype_note': DTYPE_NOTE[args.dtype],
-            'config': {'workload': 'ppsurf_50nn predict, R=257: {} distinct {} chunks of {} queries '
+            'config': {'workload': 'ppsurf_50nn predict, R=257: {} {} chunks ({} distinct) of {} queries '
                                    '(rec_batch_size) over {} synthetic 100k-point clouds per GPU, k=64, P=50'.format(
                                        args.steps, 'first-growth-round band' if args.queries == 'band' else 'dense z-slab (every voxel of the (R+2)^3 grid)',
-                                       Q_CHUNK, len(shapes)),
+                                       len({id(c) for _, c in work[args.warmup:]}), Q_CHUNK, len(shapes)),
                        'queries': args.queries,
                        'parallelism': 'shape-level replicas x{} (every rank its own shapes, no collective on the data path; the query-block sharding '
                                       'of ONE shape over all ranks is the `strong` key of this line)'.format(world) if multi else 'one GPU',
                        'weights': 'formula-filled (no checkpoint offline)',
                        'entry': 'ChunkPipeline.run -> pps_knn_blocked_f32, pps_patch_normalize_f32, pps_decode_fwd_events_f32'},
+            'lanes': st['lanes'],
+            'whole_path_algorithmic_tflops': st['whole_path_algorithmic_tflops'], 'whole_path_algorithmic_frac': st['whole_path_algorithmic_frac'],
+            'whole_path_executed_mfma_frac': st['whole_path_executed_mfma_frac'],
+        }
+    if rank == 0 and args.full:
+        out.update({
             'roofline': roofline_block(args.dtype, r['stage_ms']),
-            'lanes': st['lanes'], 'single_lane': st['single_lane'], 'one_lane_loop': st['one_lane_loop'],
+            'single_lane': st['single_lane'], 'one_lane_loop': st['one_lane_loop'],
             'lanes_note': 'value / ms_per_step: the product chunk loop (ChunkPipeline.run on the chunk list of a shape; lists of >= 4 chunks are dealt to 2 HIP '
                           'streams).  one_lane_loop: the same calls with one lane -- the gain of the second stream is value / one_lane_loop.value - 1.  '
                           'stage_ms, roofline, spatial_ms: a separate pass, ONE chunk per call with a HIP event between the kernels (single_lane): its '
                           'step is longer than one_lane_loop by the per-call overhead, not by lanes',
-            'stage_ms': st['stage_ms'], 'stage_mfma_frac': st['stage_mfma_frac'], 'stage_mfma_frac_executed': st['stage_mfma_frac_executed'], 'spatial_ms': st['spatial_ms'],
-            'whole_path_algorithmic_tflops': st['whole_path_algorithmic_tflops'], 'whole_path_algorithmic_frac': st['whole_path_algorithmic_frac'],
-            'whole_path_executed_mfma_frac': st['whole_path_executed_mfma_frac'],
-        }
-    if not args.quick:
+            'stage_ms': st['stage_ms'], 'stage_mfma_frac': st['stage_mfma_frac'], 'stage_mfma_frac_executed': st['stage_mfma_frac_executed'], 'spatial_ms': st['spatial_ms']})
+    legs_on = args.full and not args.quick
+    if legs_on:
         other = 'f16x3' if args.dtype == 'f32' else 'f32'
         if not multi:
             # ---- the other decoder dtype on the same chunks: an extra key, never `value` ----------------------------------------------
@@ -482,10 +516,10 @@ def main():
                 work2.append((pipes2[id(pipe)], c))
             n2, w2 = min(args.steps, 100), min(args.warmup, 5)
             r2 = chunk_loop(work2, n2, w2, rank, world, dist, red_dev, min_timed_s=1.0)
-            last_pipe, last_c = work[w2 + n2 - 1]                       # the chunk r2['occ'] belongs to, decoded by the headline dtype
+            last_pipe, last_c = work[w2 + n2 - 1]                       # the chunk r2['last'] belongs to, decoded by the headline dtype
             ref_occ = last_pipe.run([last_c], want_occ=True)[0][1]
             out[other] = dict(dtype_stats(other, r2, world), steps=n2, note=DTYPE_NOTE[other], roofline=roofline_block(other, r2['stage_ms']))
-            out[other]['max_abs_occ_diff_vs_{}_last_chunk'.format(args.dtype)] = float((r2['occ'] - ref_occ).abs().max())
+            out[other]['max_abs_occ_diff_vs_{}_last_chunk'.format(args.dtype)] = float((r2['last'][1] - ref_occ).abs().max())
             del plan2, pipes2, work2, r2
         if not multi and args.queries == 'band':
             # ---- the north star's other reading of the workload: dense z-slab blocks of the whole grid, same step, same dtype ---------------
@@ -541,7 +575,7 @@ def main():
             out[other]['reconstruction_steady_s'] = runs2[-1]['total_s']
         del model
         torch.cuda.empty_cache()
-    if multi and not args.quick:
+    if multi and legs_on:
         # ---- the two measurements that need every rank at once -------------------------------------------------------------------
         # (an exception every rank raises alike -- a bug, an unsupported configuration -- is reported in the line; the replica figure is not lost)
         if 'strong' in legs:
@@ -564,13 +598,13 @@ def main():
                     out['fit'] = {'error': '{}: {}'.format(type(exc).__name__, str(exc)[-1500:])}
                     out['fit_ms_per_step'] = None
             torch.cuda.empty_cache()
-    if not multi and not args.quick:
+    if not multi and legs_on:
         # ---- BASELINE.md section 3's other per-config report lines ---------------------------------------------------------
         out['config2'] = config2_leg(dev, args.dtype)
         torch.cuda.empty_cache()
         out['config5'] = config5_leg(dev, args.dtype)
         torch.cuda.empty_cache()
-    if not multi and not args.quick:
+    if not multi and legs_on:
         try:
             out.update(fit_leg(dev) if args.fit_in_process else fit_leg_fresh_process(args))
             if args.fit_in_process:
@@ -585,6 +619,14 @@ def main():
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, last):
+    """What the last timed chunk returned to the caller of ChunkPipeline.run -- logits float32 [Q, 2], occupancy float32 [Q] -- as .npy files
+    (600 kB at Q = 50 000)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in zip(('logits', 'occupancy'), last):
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def fit_roofline(ms_per_step):

@@ -23,6 +23,15 @@ def bumpy_field(q: torch.Tensor) -> torch.Tensor:
     return 14.0 * (0.33 + 0.05 * torch.sin(9.0 * q[..., 0]) * torch.cos(7.0 * q[..., 1]) + 0.03 * torch.sin(11.0 * q[..., 2]) - r)
 
 
+def recorded_refine_occ(g):
+    """The occupancy the refinement fixture's field gave at every point its refinement queried (softmax of bumpy_field's logits, float32),
+    as recorded with the fixture (refine.npz: occ_pts, occ_val): numpy float32 [q,3] -> float32 [q]; a point the reference never queried
+    raises KeyError.  Evaluated afresh, the float32 sin / cos come from the host's vector-math library, whose code path depends on the CPU:
+    a last-bit difference there moves a vertex."""
+    table = dict(zip(map(bytes, g['occ_pts']), g['occ_val']))
+    return lambda q: np.array([table[bytes(r)] for r in np.ascontiguousarray(q, dtype=np.float32)], dtype=np.float32)
+
+
 def forward_case(g):
     """The batch dictionary of the `ppsurf_forward` fixture (cloud by seed, support selections and queries from the file, id
     tables and patches rebuilt by the oracle's exact kNN): CPU tensors in the reference's layout."""

@@ -50,21 +50,22 @@ def test_a_mismatched_launcher_is_refused_not_ignored():
 
 @pytest.mark.gpu
 def test_plain_gpus_2_prints_one_line_with_replicas_strong_and_fit():
-    """`python bench.py --gpus 2` exactly as the driver would type it (plus the single-GPU rehearsal switches): self-spawn, two ranks on
+    """`python bench.py --gpus 2 --full` exactly as the driver would type it (plus the single-GPU rehearsal switches): self-spawn, two ranks on
     cuda:0 over gloo, ONE JSON line from rank 0 with n_gpus 2 carrying the three measurements of an N > 1 run: the replica
     figure (`value`, per-rank rates, shapes/hour), `strong` (ONE shape by both ranks, PPS_SHARD=queries) and `fit` (the staged data-parallel
-    step with its all-reduce accounting)."""
+    step with its all-reduce accounting).  400 steps: the timed region is the steps themselves, and 400 of them take more than a second."""
     env = dict(os.environ, PPS_BENCH_DDP_BATCH='4', PPS_MIN_SHARD='4096')
-    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--same-gpu', '--steps', '2', '--warmup', '1',
-                        '--shapes', '1'], capture_output=True, text=True, timeout=1500, cwd=REPO, env=env)
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--same-gpu', '--steps', '400', '--warmup', '1',
+                        '--shapes', '1', '--full'], capture_output=True, text=True, timeout=1500, cwd=REPO, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
     d = json.loads(lines[0])
-    assert d['n_gpus'] == 2 and d['world_size_seen'] == 2 and d['steps'] == 2 and d['scaling'] == 'weak'
+    assert d['n_gpus'] == 2 and d['world_size_seen'] == 2 and d['steps'] == 400 and d['scaling'] == 'weak'
     assert d['config']['parallelism'].startswith('shape-level replicas x2')          # not "query-block sharding": that is d['strong']
     assert len(d['per_rank_queries_per_s']['all']) == 2 and d['per_rank_queries_per_s']['min'] > 0
     assert d['value'] > 0 and d['repeats'] >= 1 and d['timed_s'] >= 1.0
+    assert d['repeats'] == 1 and abs(d['ms_per_step'] * d['steps'] - d['timed_s'] * 1e3) < 1e-6 * d['timed_s'] * 1e3     # --steps timed, no more
     assert d['shapes_per_hour'] and d['shapes_per_hour'] > 0 and len(d['reconstruction']['per_rank_shapes_per_hour']['all']) == 2
     assert 'cpu_baseline' not in d                                                   # rank 0 at N = 1 only
     st, ft = d['strong'], d['fit']
@@ -80,7 +81,7 @@ def test_plain_gpus_2_prints_one_line_with_replicas_strong_and_fit():
 
 @pytest.mark.gpu
 def test_self_spawned_single_rank_gives_the_same_kind_of_line():
-    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--spawn', '--quick', '--steps', '3', '--warmup', '1'],
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--spawn', '--full', '--quick', '--steps', '3', '--warmup', '1'],
                        capture_output=True, text=True, timeout=900, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
@@ -109,7 +110,7 @@ def test_strong_scaling_line_reports_the_dtype_it_ran_and_its_collectives(dtype)
 @pytest.mark.parametrize('leg', ['config2', 'config5'])
 def test_extra_config_legs_report_what_baseline_md_asks_for(leg):
     """config 2 (R = 129: q/s, s/shape) and config 5 (N = 250k, P = 200, Q = 25 000: q/s and the k = 200 search / patch gather
-    kernels' rates) are keys of the default line; `--only <leg>` prints the same object alone (what the counter passes profile)."""
+    kernels' rates) are keys of the --full line; `--only <leg>` prints the same object alone (what the counter passes profile)."""
     p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--only', leg], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][0])
@@ -125,7 +126,7 @@ def test_extra_config_legs_report_what_baseline_md_asks_for(leg):
 
 @pytest.mark.gpu
 def test_fit_leg_runs_in_a_process_of_its_own_and_says_where_the_time_goes():
-    """`python bench.py --only fit` = what the default line spawns for its fit leg (pps.py fit is a process of its own; at the end of the bench process
+    """`python bench.py --only fit` = what the --full line spawns for its fit leg (pps.py fit is a process of its own; at the end of the bench process
     the same step measured 19.7 .. 21.5 ms on one box depending on what ran before): step time, per-queue busy time, loader waits, GPU state."""
     p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--only', 'fit'], capture_output=True, text=True, timeout=900, cwd=REPO)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -135,3 +136,30 @@ def test_fit_leg_runs_in_a_process_of_its_own_and_says_where_the_time_goes():
     assert f['queue_busy_ms']['step']['mean'] > 0.8 * d['fit_ms_per_step'] and f['queue_busy_ms']['loader']['mean'] > 0
     assert f['loader_wait_ms']['mean'] < 2.0 and 'before' in f['gpu_state']
     assert f.get('roofline') is not None or 'roofline_note' in f
+
+
+@pytest.mark.gpu
+def test_plain_line_times_exactly_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) is the headline alone: `steps` timed chunks, once, and no extra leg on the line.  --dump-outputs writes what
+    the last timed chunk returned to the caller of ChunkPipeline.run; the same chunk decoded here gives the same arrays."""
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '2', '--dump-outputs',
+                        str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=REPO)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['steps'] == 5 and d['warmup'] == 2 and d['repeats'] == 1 and d['value'] > 1e6 and d['higher_is_better'] is True
+    assert d['unit'] == 'queries/s' and d['dtype'] == 'f16x3' and abs(d['ms_per_step'] * 5 - d['timed_s'] * 1e3) < 1e-6 * d['timed_s'] * 1e3
+    assert not {'roofline', 'stage_ms', 'single_lane', 'one_lane_loop', 'f32', 'dense', 'shapes_per_hour', 'config2', 'config5', 'fit',
+                'fit_ms_per_step', 'cpu_baseline'} & set(d)
+    logits, occ = np.load(tmp_path / 'logits.npy'), np.load(tmp_path / 'occupancy.npy')
+    assert logits.dtype == np.float32 and logits.shape == (50_000, 2) and occ.dtype == np.float32 and occ.shape == (50_000,)
+    import torch
+    from ppsurf_amd.decoder import DecoderPlan
+    from ppsurf_amd.synthetic import network_state_dict
+    bench = _bench()
+    dev = torch.device('cuda:0')
+    _, work = bench.build_work(DecoderPlan(network_state_dict('ppsurf'), dev, dtype='f16x3'), 7, 0, dev)            # warm-up 2 + 5 steps
+    pipe, chunk = work[6]
+    want_logits, want_occ = pipe.run([chunk], want_occ=True)[0]
+    assert np.array_equal(logits, want_logits.cpu().numpy()) and np.array_equal(occ, want_occ.cpu().numpy())

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from golden_util import load_golden
-from golden.cases_r2 import SAMPLING_CASES, bumpy_field
+from golden.cases_r2 import SAMPLING_CASES, recorded_refine_occ
 from ppsurf_amd import spatial, reconstruct
 from ppsurf_amd.synthetic import make_cloud
 
@@ -94,11 +94,10 @@ def test_latent_loop_equals_reference(tag, batch):
 
 def test_refine_vertices_equals_reference():
     g = load_golden('refine')
+    field = recorded_refine_occ(g)
 
-    def occ(q):                                            # what _predict_from_latent computes from the stub network's logits
-        d = bumpy_field(q)
-        p = torch.softmax(torch.stack([d, torch.zeros_like(d)], dim=0).unsqueeze(0), dim=1)
-        return (p[:, 0] - p[:, 1]).squeeze(0)
+    def occ(q):                                            # what _predict_from_latent computed from the stub network's logits
+        return torch.from_numpy(field(q.numpy()))
 
     verts = torch.from_numpy(g['mc_verts'].astype(np.float64))
     out = reconstruct.refine_vertices(occ, verts, torch.from_numpy(g['volume']), g['step'][()], g['bmin_pad'][()], int(g['refine_iter']))

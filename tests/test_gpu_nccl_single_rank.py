@@ -129,12 +129,12 @@ def test_staged_fit_runs_its_collectives_on_rccl(tmp_path, buckets):
 
 
 def test_bench_single_rank_line_carries_replicas_strong_and_fit_on_rccl():
-    """`bench.py --gpus 1 --spawn --single-rank-collectives` = the driver's `bench.py --gpus N` code path with N = 1 on RCCL: self-spawn under
-    torch.distributed.run, init_process_group('nccl', device_id=...), and ONE line with the replica figure, the `strong` block (query-block
-    sharding of one shape) and the `fit` block (staged data-parallel step) -- the three things a SCALE run records per N."""
+    """`bench.py --gpus 1 --spawn --single-rank-collectives --full` = the driver's `bench.py --gpus N --full` code path with N = 1 on RCCL:
+    self-spawn under torch.distributed.run, init_process_group('nccl', device_id=...), and ONE line with the replica figure, the `strong` block
+    (query-block sharding of one shape) and the `fit` block (staged data-parallel step) -- the three things a SCALE run records per N."""
     env = dict(os.environ, PPS_BENCH_DDP_BATCH='4')                          # B = 50 // 1 = 50 shapes would not be a test
     p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--spawn', '--single-rank-collectives', '--steps', '2',
-                        '--warmup', '1', '--shapes', '1'], capture_output=True, text=True, timeout=1500, cwd=REPO, env=env)
+                        '--warmup', '1', '--shapes', '1', '--full'], capture_output=True, text=True, timeout=1500, cwd=REPO, env=env)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1

@@ -176,12 +176,13 @@ def test_device_metrics_equal_the_reference_metrics():
             assert (np.isnan(a) and np.isnan(b)) or abs(a - b) < 1e-6, (k, a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/datasets/abc_minimal'), reason='reference dataset only exists in the build container')
 def test_readers_on_the_reference_dataset_files():
     """The reference's own abc_minimal files (trimesh-written binary PLY with a comment line, float32 .npy queries / distances,
-    set lists) through this package's readers and the reconstruction dataset (source/occupancy_data_module.py:34-71,174-253)."""
+    set lists) through this package's readers and the reconstruction dataset (source/occupancy_data_module.py:34-71,174-253).
+    tests/golden/abc_minimal_testset holds the test split of that dataset byte for byte (clouds and queries of the three test shapes,
+    the three set lists)."""
     from ppsurf_amd import data
-    in_file = '/root/reference/datasets/abc_minimal/testset.txt'
+    in_file = os.path.join(GOLDEN, 'abc_minimal_testset', 'testset.txt')
     names = data.read_shape_list(in_file)
     train, val, test = data.get_set_files(in_file)
     assert len(names) == 3 and len(data.read_shape_list(train)) == 7 and len(data.read_shape_list(val)) == 3 and test == in_file

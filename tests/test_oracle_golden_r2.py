@@ -12,7 +12,7 @@ from oracle import driver_oracle as D
 from oracle import ppsurf_oracle as O
 from ppsurf_amd.synthetic import make_cloud
 
-from golden.cases_r2 import SAMPLING_CASES, bumpy_field, forward_case
+from golden.cases_r2 import SAMPLING_CASES, forward_case, recorded_refine_occ
 
 
 @pytest.mark.parametrize('tag', [c[0] for c in SAMPLING_CASES])
@@ -89,12 +89,7 @@ def test_latent_loop_equals_reference(tag):
 
 def test_refinement_equals_reference():
     g = load_golden('refine')
-
-    def occ(q):
-        d = bumpy_field(torch.from_numpy(q))
-        p = torch.softmax(torch.stack([d, torch.zeros_like(d)], dim=0).unsqueeze(0), dim=1)
-        return (p[:, 0] - p[:, 1]).squeeze(0).numpy()
-
+    occ = recorded_refine_occ(g)
     out = D.refine_vertices(g['mc_verts'].astype(np.float64), g['volume'], occ, g['step'][()], g['bmin_pad'][()], int(g['refine_iter']), 5000)
     assert np.array_equal(out, g['refined'])
     assert np.array_equal(D.refine_vertices(g['mc_verts'].astype(np.float64), g['volume'], occ, g['step'][()], g['bmin_pad'][()], 0),

@@ -21,7 +21,7 @@ def main(prefix):
             break
     lines = ['# Per-kernel time, HBM traffic and MFMA utilisation ({}, one MI355X)'.format(tag), '',
              'Source: `{0}_rocprof_summary.txt` / `{0}_pmc.json` (`tools/profile_round.sh`: `rocprofv3 --kernel-trace --stats` and separate'.format(tag),
-             '`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, `--pmc SQ_*/GRBM_GUI_ACTIVE` passes of `python bench.py --steps 20 --warmup 3 --quick`).',
+             '`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, `--pmc SQ_*/GRBM_GUI_ACTIVE` passes of `python bench.py --steps 20 --warmup 3 --full --quick`).',
              'FETCH_SIZE is doubled (gfx950 reports half of a wide coalesced read stream, MI355X_MICROARCH.md §HBM); KiB -> MB.',
              'MFMA utilisation = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 XCDs x 1024 SIMDs).',
              '**Per-STEP sums**: a bench step launches some kernels more than once (the PointNet row kernels: packed full rounds + per-query remainder);',

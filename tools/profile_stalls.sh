@@ -1,5 +1,5 @@
 #!/bin/bash
-# Where do the waves of the decoder kernels spend their cycles?  SQ counter passes (no trace domains) over `bench.py --quick`:
+# Where do the waves of the decoder kernels spend their cycles?  SQ counter passes (no trace domains) over `bench.py --full --quick`:
 # wave-parked (s_waitcnt / barrier) vs issue-stalled vs issuing, per instruction class; LDS activity and bank conflicts.
 #   tools/profile_stalls.sh <tag> [f16x3|f32]   -> gpurun_out/stalls_<tag>/summary_{rocprof_summary.txt,pmc.json}
 TAG=${1:-r4}
@@ -7,7 +7,7 @@ DT=${2:-f16x3}
 OUT=$PWD/gpurun_out/stalls_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python $PWD/bench.py --steps 20 --warmup 3 --quick --dtype $DT"
+BENCH="python $PWD/bench.py --steps 20 --warmup 3 --full --quick --dtype $DT"
 cd /tmp
 rocprofv3 --list-avail > $OUT/list_avail.txt 2>&1
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1

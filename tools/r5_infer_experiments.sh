@@ -10,7 +10,7 @@ mkdir -p $OUT
 STEPS=${1:-94}
 run() {   # name, env...
     local name=$1; shift
-    env "$@" python bench.py --quick --steps $STEPS --warmup 6 > $OUT/$name.json 2> $OUT/$name.err || echo "FAILED $name" >> $OUT/failed.txt
+    env "$@" python bench.py --full --quick --steps $STEPS --warmup 6 > $OUT/$name.json 2> $OUT/$name.err || echo "FAILED $name" >> $OUT/failed.txt
     python - "$OUT/$name.json" "$name" <<'EOF'
 import json, sys
 try:

@@ -10,7 +10,7 @@ names = [('interp_pool_f16x3_kernel', 'interp_pool_f16x3'), ('pointnet_stn_rows_
          ('pointnet_feat_rows_kernel<true>', 'feat_rows<f16x3>'), ('knn_blocked_kernel<1>', 'knn_blocked')]
 lines = ['# Where the waves of the decoder kernels spend their cycles (SQ counters, one MI355X, f16x3, `tools/profile_stalls.sh`, sources digest {} at commit {})'.format(
     d['csrc_digest'], d['git_head']), '',
-    '`python bench.py --steps 20 --warmup 3 --quick --dtype f16x3` under four separate `rocprofv3 --pmc` passes (no trace domains).  Cycle counters are in',
+    '`python bench.py --steps 20 --warmup 3 --full --quick --dtype f16x3` under four separate `rocprofv3 --pmc` passes (no trace domains).  Cycle counters are in',
     'units of 4 clocks; shares are of SQ_WAVE_CYCLES (wave-resident time).  parked = SQ_WAIT_ANY (s_waitcnt / barrier), issue-stalled = SQ_WAIT_INST_ANY',
     '(an instruction is ready but cannot issue: matrix pipe taken, dependency), issuing = SQ_ACTIVE_INST_ANY.  pipe = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM/8 x 1024 SIMDs).', '',
     '| kernel | avg µs | parked | issue-stalled (of which LDS) | issuing | matrix pipe busy | MFMA | other VALU | LDS instr | VMEM rd | LDS array active | bank conflicts |',

@@ -592,6 +592,34 @@ int pps_gemm_tn_16(const void* g, int64_t ldg, const void* x, int64_t ldx, int64
 int pps_transpose_entry_bytes(void);
 int pps_transpose_cast_pieces(const void* table, int entries, int64_t tiles, int dtype, void* stream);
 
+/* ---- evaluation against ground-truth meshes (csrc/pps_eval.hip) --------------------------------------------------------------------------------
+ * replaces: the mesh comparison of source/base/metrics.py:120-323 (trimesh sampling, pysdf inside test, pykdtree 1-NN, numpy sums), reached from
+ * source/poco_model.py:275-300 -> source/base/evaluation.py:32-59.  The 1-NN searches are pps_knn_* with k = 1.
+ *   pps_eval_face_stats      verts f32 [nv,3], faces int32 [nf,3] -> area f32 [nf] (0.5 |e1 x e2|), normal f32 [nf,3] (unit e1 x e2, trimesh's
+ *                            face_normals without re-orientation, 0 for a degenerate face), corners f32 [nf,9] (v0 v1 v2 face-major).  A face with
+ *                            an index outside [0, nv) gets area 0.   replaces: trimesh Trimesh.area_faces / face_normals.
+ *   pps_eval_sample_surface  n area-weighted surface samples out_pts f32 [n,3] and their faces out_face int32 [n] from corners and the fp64 inclusive
+ *                            prefix of the areas (total > 0), counter-based generator keyed by (seed, stream_id, sample index) written out at the
+ *                            top of csrc/pps_eval.hip: the first k samples of a draw of n are the draw of k; zero-area faces are never drawn.
+ *                            replaces: trimesh.sample.sample_surface (source/base/point_cloud.py `sample_mesh`, metrics.py:250-254).
+ *   pps_eval_winding_slices  number S of face slices of pps_eval_winding for m queries against nf faces (a function of m and nf only).
+ *   pps_eval_winding         generalised winding number out_w f64 [m] of query f32 [m,3] against a mesh given by corners [nf,9]:
+ *                            w = sum_f Omega_f / 4 pi, Omega_f the Van Oosterom-Strackee solid angle; |w| > 0.5 = inside.  partial f32 [S,m] is
+ *                            scratch (per-slice sums, added in slice order in fp64: bitwise reproducible).
+ *                            replaces: source/base/proximity.py `get_signed_distance_pysdf_inaccurate` (pysdf ray parity), metrics.py:157-219.
+ *   pps_eval_reduce          out f64 [8] = { sum sqrt(d2_rg), sum sqrt(d2_gr), TP, FP, FN, TN, sum arccos(clip(n_rec . n_gt[nn], -1, 1)), count }
+ *                            with rec = |w_rec| > 0.5, gt = |w_gt| > 0.5 over mq query points; NaN cosines are skipped.  The normal group
+ *                            (nn_rg int64 [n_rec], face_rec int32 [n_rec], face_gt int32 [n_gt], normal_rec, normal_gt) may be all NULL.
+ *                            One workgroup, fixed summation order.   replaces: the numpy sums of metrics.py:133-137, 202-214, 263-267. */
+int pps_eval_face_stats(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, float* area, float* normal, float* corners, void* stream);
+int pps_eval_sample_surface(const float* corners, const double* area_prefix, int64_t nf, int64_t n, uint64_t seed, uint64_t stream_id,
+                            float* out_pts, int32_t* out_face, void* stream);
+int64_t pps_eval_winding_slices(int64_t m, int64_t nf);
+int pps_eval_winding(const float* corners, int64_t nf, const float* query, int64_t m, int64_t slices, float* partial, double* out_w, void* stream);
+int pps_eval_reduce(const float* d2_rg, int64_t n_rec, const float* d2_gr, int64_t n_gt, const int64_t* nn_rg, const int32_t* face_rec,
+                    const int32_t* face_gt, const float* normal_rec, const float* normal_gt, const double* w_rec, const double* w_gt, int64_t mq,
+                    double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

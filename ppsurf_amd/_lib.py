@@ -128,6 +128,11 @@ SIGNATURES = {
     'pps_cast_piece_bytes': (_I, []),
     'pps_cast_pieces': (_I, [_P, _I, _I, _P]),
     'pps_adamw_step': (_I, [_P, _I, _P, _I, _P, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _P, _P, _P]),
+    'pps_eval_face_stats': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P]),
+    'pps_eval_sample_surface': (_I, [_P, _P, _I64, _I64, _c.c_uint64, _c.c_uint64, _P, _P, _P]),
+    'pps_eval_winding_slices': (_I64, [_I64, _I64]),
+    'pps_eval_winding': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _P]),
+    'pps_eval_reduce': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -78,6 +78,12 @@ def get_results_dir(out_dir: str, name: str, in_file: str):
     return os.path.join(out_dir, name, os.path.basename(os.path.dirname(in_file)))
 
 
+def get_now_str():
+    """source/base/profiling.py `get_now_str`."""
+    import datetime
+    return str(datetime.datetime.now())
+
+
 class PocoModel(_Base):
 
     def __init__(self, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir, padding_factor, name,
@@ -210,17 +216,33 @@ class PocoModel(_Base):
         self.test_step_outputs.clear()
 
     def on_predict_epoch_end(self):
-        """poco_model.py:275-300: after reconstructing a DATASET the reference compares the meshes with ground truth
-        (source/base/evaluation.py: Chamfer distance, IoU, normal error through trimesh/pysdf in worker processes).  That
-        evaluation is outside the occupancy-query path; the guards are kept, the comparison is left to the reference's tools."""
+        """poco_model.py:275-300: after reconstructing a DATASET, compare every mesh with its ground truth in <dataset>/03_meshes
+        (ppsurf_amd/evaluation.py on the GPU: Chamfer distance, F1, IoU, normal error at 100k samples) and write one CSV table per
+        metric into the results directory.  Under a multi-rank predict the ranks meet in a barrier and rank 0 evaluates alone."""
         if not in_file_is_dataset(self.in_file):
             return
         gt_meshes_dir = os.path.join(os.path.dirname(self.in_file), '03_meshes')
+        rank, world = sharding.world()
+        if world > 1 and os.path.exists(gt_meshes_dir):
+            import torch.distributed as dist
+            dist.barrier()                                   # every rank has written its meshes
+        if rank != 0:
+            return
+        from . import evaluation
+        from .data import read_shape_list
+        print('{}: Evaluating {}'.format(get_now_str(), self.name))
+        results_dir = get_results_dir(out_dir=self.results_dir, name=self.name, in_file=self.in_file)
+        shape_names = read_shape_list(self.in_file)
         if not os.path.exists(gt_meshes_dir):
             print('Warning: {} not found. Skipping evaluation.'.format(gt_meshes_dir))
-            return
-        print('{}: meshes written to {}; quantitative comparison with {} is not part of ppsurf_amd (use the reference\'s '
-              'source/base/evaluation.py on these files)'.format(self.name, get_results_dir(self.results_dir, self.name, self.in_file), gt_meshes_dir))
+        else:
+            gt_meshes = [os.path.join(gt_meshes_dir, '{}.ply'.format(vs)) for vs in shape_names]
+            os.makedirs(results_dir, exist_ok=True)
+            evaluation.make_quantitative_comparison(
+                shape_names=shape_names, gt_mesh_files=gt_meshes, result_headers=[self.name],
+                result_file_templates=[os.path.join(results_dir, 'meshes/{}.xyz.ply')], comp_output_dir=results_dir,
+                num_processes=self.workers, num_samples=100000)
+        print('{}: Evaluating {} finished'.format(get_now_str(), self.name))
 
     def do_logging(self, loss_total, loss_components, log_type: str, output_names: list, metrics_dict: dict,
                    keys_to_log=frozenset({'abs_dist_rms', 'accuracy', 'precision', 'recall', 'f1_score'}), f1_in_prog_bar=True,

@@ -1,4 +1,4 @@
-"""Minimal PLY / XYZ / NPY IO for the predict path (the reference uses trimesh, absent here).
+"""Minimal PLY / XYZ / NPY IO for the predict path and the mesh evaluation (the reference uses trimesh, absent here).
 
 Point clouds of datasets/abc_minimal are binary little-endian PLY written by trimesh
 (`element vertex n`, `property float x/y/z`, optional normals, `element face 0`); meshes are written the same way
@@ -47,6 +47,141 @@ def read_ply_vertices(path):
             cols = {name: rec[name] for name, _ in props}
     names = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if all(k in cols for k in ('nx', 'ny', 'nz')) else [])
     return np.stack([np.asarray(cols[k], dtype=np.float64) for k in names], axis=1)
+
+
+def _fan(polys):
+    """Triangles of polygons fanned from their first corner (trimesh's triangulation of n-gons): [v0, vi, vi+1]."""
+    tris = []
+    for p in polys:
+        p = np.asarray(p, dtype=np.int64)
+        if p.shape[0] >= 3:
+            tris.append(np.stack([np.full(p.shape[0] - 2, p[0]), p[1:-1], p[2:]], axis=1))
+    return np.concatenate(tris, axis=0) if tris else np.zeros((0, 3), dtype=np.int64)
+
+
+def read_ply_mesh(path):
+    """Vertices float32 [nv,3] and triangles int32 [nf,3] of an ascii or binary PLY mesh (trimesh-written `03_meshes` files and
+    write_ply_mesh): float or double x/y/z (other vertex properties skipped), face list `vertex_indices` (or `vertex_index`) of
+    uchar/int/uint counts and int/uint indices, polygons fan-triangulated.  Other face properties and elements after `face` are skipped
+    (binary: fixed-size ones only).  Raises ValueError on anything else or on an index outside [0, nv)."""
+    with open(path, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise ValueError('not a PLY file: {}'.format(path))
+        fmt, elements = None, []                          # [name, count, [(prop, dtype) | (prop, (count_dtype, item_dtype))]]
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError('unterminated PLY header: {}'.format(path))
+            tok = line.decode('ascii', 'replace').split()
+            if not tok or tok[0] in ('comment', 'obj_info'):
+                continue
+            if tok[0] == 'format':
+                fmt = tok[1]
+            elif tok[0] == 'element':
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == 'property':
+                if not elements:
+                    raise ValueError('PLY property before any element: {}'.format(path))
+                if tok[1] == 'list':
+                    elements[-1][2].append((tok[4], (_PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]])))
+                else:
+                    elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+            elif tok[0] == 'end_header':
+                break
+        if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+            raise ValueError('unknown PLY format {!r}: {}'.format(fmt, path))
+        body = f.read()
+    verts, faces = None, None
+    end = '>' if fmt == 'binary_big_endian' else '<'
+    pos = 0
+    lines = body.decode('ascii', 'replace').split('\n') if fmt == 'ascii' else None
+    for name, count, props in elements:
+        if name == 'vertex':
+            if any(isinstance(t, tuple) for _, t in props):
+                raise ValueError('list property on vertices is not supported: {}'.format(path))
+            names = [n for n, _ in props]
+            if not all(k in names for k in 'xyz'):
+                raise ValueError('PLY vertices without x/y/z: {}'.format(path))
+            if fmt == 'ascii':
+                data = np.array([lines[pos + i].split()[:len(props)] for i in range(count)], dtype=np.float64).reshape(count, len(props))
+                pos += count
+                verts = np.stack([data[:, names.index(k)] for k in 'xyz'], axis=1)
+            else:
+                dt = np.dtype([(n, end + t) for n, t in props])
+                rec = np.frombuffer(body, dtype=dt, count=count, offset=pos)
+                pos += count * dt.itemsize
+                verts = np.stack([rec[k].astype(np.float64) for k in 'xyz'], axis=1)
+        elif name == 'face':
+            lists = [i for i, (_, t) in enumerate(props) if isinstance(t, tuple)]
+            idx_prop = [i for i in lists if props[i][0] in ('vertex_indices', 'vertex_index')]
+            if not idx_prop:
+                raise ValueError('PLY faces without vertex_indices: {}'.format(path))
+            ip = idx_prop[0]
+            if fmt == 'ascii':
+                polys = []
+                for i in range(count):
+                    vals = lines[pos + i].split()
+                    at = 0
+                    for j, (_, t) in enumerate(props):
+                        if isinstance(t, tuple):
+                            k = int(vals[at])
+                            if j == ip:
+                                polys.append([int(v) for v in vals[at + 1:at + 1 + k]])
+                            at += 1 + k
+                        else:
+                            at += 1
+                pos += count
+                faces = _fan(polys)
+            elif len(props) == 1:
+                cdt, idt = np.dtype(end + props[0][1][0]), np.dtype(end + props[0][1][1])
+                if count > 0:
+                    k0 = int(np.frombuffer(body, dtype=cdt, count=1, offset=pos)[0])
+                    dt = np.dtype([('n', cdt), ('v', idt, (k0,))])
+                    rec = np.frombuffer(body, dtype=dt, count=count, offset=pos) if pos + count * dt.itemsize <= len(body) else None
+                    if rec is not None and np.all(rec['n'] == k0):            # every face has the same corner count: one view
+                        pos += count * dt.itemsize
+                        faces = _fan([]) if k0 < 3 else _fan_uniform(rec['v'].astype(np.int64))
+                        continue
+                polys = []
+                for _ in range(count):
+                    k = int(np.frombuffer(body, dtype=cdt, count=1, offset=pos)[0])
+                    polys.append(np.frombuffer(body, dtype=idt, count=k, offset=pos + cdt.itemsize))
+                    pos += cdt.itemsize + k * idt.itemsize
+                faces = _fan(polys)
+            else:
+                polys = []
+                for _ in range(count):
+                    for j, (_, t) in enumerate(props):
+                        if isinstance(t, tuple):
+                            cdt, idt = np.dtype(end + t[0]), np.dtype(end + t[1])
+                            k = int(np.frombuffer(body, dtype=cdt, count=1, offset=pos)[0])
+                            if j == ip:
+                                polys.append(np.frombuffer(body, dtype=idt, count=k, offset=pos + cdt.itemsize))
+                            pos += cdt.itemsize + k * idt.itemsize
+                        else:
+                            pos += np.dtype(t).itemsize
+                faces = _fan(polys)
+        else:                                             # other elements: skipped (fixed-size records only in binary files)
+            if fmt == 'ascii':
+                pos += count
+            elif any(isinstance(t, tuple) for _, t in props):
+                if count > 0:
+                    raise ValueError('list property on PLY element {!r} is not supported: {}'.format(name, path))
+            else:
+                pos += count * sum(np.dtype(t).itemsize for _, t in props)
+    if verts is None:
+        raise ValueError('PLY file without vertices: {}'.format(path))
+    if faces is None:
+        faces = np.zeros((0, 3), dtype=np.int64)
+    if faces.size and (faces.min() < 0 or faces.max() >= verts.shape[0]):
+        raise ValueError('PLY face index out of range: {}'.format(path))
+    return verts.astype(np.float32), faces.astype(np.int32)
+
+
+def _fan_uniform(v):
+    """_fan for polygons that all have the same corner count k >= 3, v int [n, k] -> [n * (k - 2), 3] (polygon-major)."""
+    k = v.shape[1]
+    return np.stack([np.repeat(v[:, :1], k - 2, axis=1), v[:, 1:-1], v[:, 2:]], axis=2).reshape(-1, 3)
 
 
 def load_pts(pts_file: str) -> np.ndarray:

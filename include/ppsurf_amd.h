@@ -620,6 +620,31 @@ int pps_eval_reduce(const float* d2_rg, int64_t n_rec, const float* d2_gr, int64
                     const int32_t* face_gt, const float* normal_rec, const float* normal_gt, const double* w_rec, const double* w_gt, int64_t mq,
                     double* out, void* stream);
 
+/* ---- qualitative comparison: closest point on a mesh, rasteriser (csrc/pps_vis.hip) ---------------------------------------------------------
+ * replaces: source/base/proximity.py:20-36 (trimesh closest_point) and the pyrender renders of source/base/visualization.py:25-63, 122-134,
+ * reached from source/make_comparison.py.  The camera, coverage and shading rules are written out at the top of csrc/pps_vis.hip.
+ *   pps_vis_closest_slices   number of face slices S of pps_vis_closest_point for m queries against nf faces (a function of m and nf only).
+ *   pps_vis_closest_point    exact closest point of query f32 [m,3] on the mesh of corners f32 [nf,9] (pps_eval_face_stats): out_d f32 [m],
+ *                            out_face int32 [m], out_pt f32 [m,3].  Any slices in [1, min(nf, 65535)]; partial_d2 f32 [S,m] and partial_face
+ *                            int32 [S,m] are scratch.  Ties go to the lowest face: the result does not depend on S.
+ *   pps_vis_raster_ws_bytes  scratch bytes of pps_vis_raster_faces.
+ *   pps_vis_raster_faces     z-buffer keys (view depth bits << 32 | face id) of the mesh verts f32 [nv,3], faces int32 [nf,3] into keys uint64
+ *                            [height,width] by a 64-bit atomicMin (clear keys to all ones first).  cam: HOST array of 16 floats (world -> view
+ *                            rotation row-major, eye, focal length in pixels, 3 unused).
+ *   pps_vis_raster_points    the same for points pts f32 [n,3] as screen discs of radius px, key id = point index.
+ *   pps_vis_shade            out uint8 [height,width,3] from keys: faces given -> the mesh (verts, faces) with colours colors uint8 [nv,3] or the
+ *                            uniform rgb (0xRRGGBB) under a two-sided headlight; faces NULL -> points (colors uint8 [n,3] or rgb, unshaded);
+ *                            background white. */
+int64_t pps_vis_closest_slices(int64_t m, int64_t nf);
+int pps_vis_closest_point(const float* corners, int64_t nf, const float* query, int64_t m, int64_t slices, float* partial_d2, int32_t* partial_face,
+                          float* out_d, int32_t* out_face, float* out_pt, void* stream);
+size_t pps_vis_raster_ws_bytes(int64_t nv, int64_t nf);
+int pps_vis_raster_faces(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, const float* cam, int width, int height, void* ws,
+                         size_t ws_bytes, void* keys, void* stream);
+int pps_vis_raster_points(const float* pts, int64_t n, const float* cam, int width, int height, float radius, void* keys, void* stream);
+int pps_vis_shade(const void* keys, int width, int height, const float* verts, const int32_t* faces, const uint8_t* colors, uint32_t rgb,
+                  const float* cam, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,12 @@ SIGNATURES = {
     'pps_eval_winding_slices': (_I64, [_I64, _I64]),
     'pps_eval_winding': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _P]),
     'pps_eval_reduce': (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    'pps_vis_closest_slices': (_I64, [_I64, _I64]),
+    'pps_vis_closest_point': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    'pps_vis_raster_ws_bytes': (_SZ, [_I64, _I64]),
+    'pps_vis_raster_faces': (_I, [_P, _I64, _P, _I64, _P, _I, _I, _P, _SZ, _P, _P]),
+    'pps_vis_raster_points': (_I, [_P, _I64, _P, _I, _I, _c.c_float, _P, _P]),
+    'pps_vis_shade': (_I, [_P, _I, _I, _P, _P, _P, _c.c_uint32, _P, _P, _P]),
 }
 
 _lib = None

@@ -14,6 +14,25 @@ _PLY_TYPES = {'char': 'i1', 'uchar': 'u1', 'short': 'i2', 'ushort': 'u2', 'int':
 
 def read_ply_vertices(path):
     """Vertex x,y,z (+ nx,ny,nz if present) of an ascii or binary PLY -> float array [n, 3|6]."""
+    cols = _ply_vertex_columns(path)
+    names = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if all(k in cols for k in ('nx', 'ny', 'nz')) else [])
+    return np.stack([np.asarray(cols[k], dtype=np.float64) for k in names], axis=1)
+
+
+def read_ply_vertex_colors(path):
+    """Vertex colours uint8 [n,3] (red, green, blue) of an ascii or binary PLY, or None when the vertices carry no colour.  Float colour
+    properties in [0, 1] are scaled to [0, 255]."""
+    cols = _ply_vertex_columns(path)
+    if not all(k in cols for k in ('red', 'green', 'blue')):
+        return None
+    rgb = np.stack([np.asarray(cols[k]) for k in ('red', 'green', 'blue')], axis=1)
+    if rgb.dtype.kind == 'f':
+        rgb = np.rint(np.clip(rgb, 0.0, 1.0) * 255.0)
+    return rgb.astype(np.uint8)
+
+
+def _ply_vertex_columns(path):
+    """{property name: array [n]} of the vertex element of an ascii or binary PLY (the vertex element must come first)."""
     with open(path, 'rb') as f:
         if f.readline().strip() != b'ply':
             raise ValueError('not a PLY file: {}'.format(path))
@@ -45,8 +64,7 @@ def read_ply_vertices(path):
             rec = np.frombuffer(f.read(nvert * sum(np.dtype(t).itemsize for _, t in props)),
                                 dtype=np.dtype([(n, end + t) for n, t in props]), count=nvert)
             cols = {name: rec[name] for name, _ in props}
-    names = ['x', 'y', 'z'] + (['nx', 'ny', 'nz'] if all(k in cols for k in ('nx', 'ny', 'nz')) else [])
-    return np.stack([np.asarray(cols[k], dtype=np.float64) for k in names], axis=1)
+    return cols
 
 
 def _fan(polys):
@@ -222,3 +240,51 @@ def write_ply_points(path, pts: np.ndarray):
     with open(path, 'wb') as f:
         f.write(header.encode('ascii'))
         f.write(pts.tobytes())
+
+
+def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8: np.ndarray):
+    """Binary little-endian PLY mesh with per-vertex `uchar red/green/blue/alpha` (the layout trimesh exports for vertex colours).
+    colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    verts = np.asarray(verts, dtype='<f4').reshape(-1, 3)
+    faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
+    colors = np.asarray(colors_u8, dtype=np.uint8).reshape(verts.shape[0], -1)
+    if colors.shape[1] == 3:
+        colors = np.concatenate([colors, np.full((colors.shape[0], 1), 255, dtype=np.uint8)], axis=1)
+    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {}\nproperty float x\nproperty float y\n'
+              'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face {}\n'
+              'property list uchar int vertex_indices\nend_header\n').format(verts.shape[0], faces.shape[0])
+    vrec = np.empty(verts.shape[0], dtype=[('p', '<f4', (3,)), ('c', 'u1', (4,))])
+    vrec['p'] = verts
+    vrec['c'] = colors[:, :4]
+    frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    frec['n'] = 3
+    frec['v'] = faces
+    with open(path, 'wb') as f:
+        f.write(header.encode('ascii'))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
+def read_obj_mesh(path):
+    """Vertices float32 [nv,3] and triangles int32 [nf,3] of a Wavefront OBJ: `v x y z` and `f` lines only (`a`, `a/b`, `a//c`, `a/b/c`
+    corners, 1-based or negative (relative) indices, polygons fan-triangulated).  Raises ValueError on an index outside the vertices."""
+    verts, polys = [], []
+    with open(path, 'r') as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == 'v':
+                verts.append([float(t) for t in tok[1:4]])
+            elif tok[0] == 'f':
+                poly = []
+                for c in tok[1:]:
+                    i = int(c.split('/')[0])
+                    poly.append(i - 1 if i > 0 else len(verts) + i)
+                polys.append(poly)
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    faces = _fan(polys)
+    if faces.size and (faces.min() < 0 or faces.max() >= v.shape[0]):
+        raise ValueError('OBJ face index out of range: {}'.format(path))
+    return v, faces.astype(np.int32)

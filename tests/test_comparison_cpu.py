@@ -1,0 +1,250 @@
+"""CPU tier of the comparison: subdivision, colour map, PLY / OBJ / PNG IO, metric tables, HTML report, camera, ABI declarations."""
+import glob
+import math
+import os
+import re
+import zlib
+
+import numpy as np
+import pytest
+import torch
+
+from ppsurf_amd import _lib, comparison, meshio, visualization
+from ppsurf_amd.evaluation import write_metric_table
+from tests import eval_spec, vis_spec
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GT_MESHES = sorted(glob.glob(os.path.join(HERE, 'golden', 'abc_minimal_gt', '03_meshes', '*.ply')))
+L = 256
+
+
+def _meshes():
+    out = [meshio.read_ply_mesh(p) for p in GT_MESHES]
+    v, f = eval_spec.icosphere(2, 0.4)
+    out.append((v.astype(np.float32), f.astype(np.int32)))
+    return out
+
+
+@pytest.mark.parametrize('k', range(4))
+def test_subdivide_matches_spec(k):
+    v, f = _meshes()[k]
+    nv, nf = v.shape[0], f.shape[0]
+    vs, fs = visualization.subdivide(torch.from_numpy(v).double(), torch.from_numpy(f.astype(np.int64)))
+    vs, fs = vs.numpy(), fs.numpy()
+    edges = {tuple(sorted(e)) for t in f.tolist() for e in ((t[0], t[1]), (t[1], t[2]), (t[2], t[0]))}
+    assert vs.shape[0] == nv + len(edges) and fs.shape[0] == 4 * nf
+    assert np.array_equal(vs[:nv], v.astype(np.float64))
+    assert abs(vis_spec.mesh_area(vs, fs) - vis_spec.mesh_area(v, f)) <= 1e-6 * vis_spec.mesh_area(v, f)
+    mids = {tuple(np.round((v[a].astype(np.float64) + v[b]) * 0.5, 9)) for a, b in edges}
+    assert all(tuple(np.round(p, 9)) in mids for p in vs[nv:])
+    sv, sf, n_edges = vis_spec.subdivide_spec(v, f)
+    assert n_edges == len(edges)
+    assert vis_spec.triangle_set(vs, fs) == vis_spec.triangle_set(sv, sf)
+
+
+def test_subdivide_float32_device_agnostic():
+    v, f = eval_spec.icosphere(1, 0.3)
+    vs, fs = visualization.subdivide(torch.from_numpy(v.astype(np.float32)), torch.from_numpy(f.astype(np.int32)))
+    assert vs.dtype == torch.float32 and fs.dtype == torch.int32 and fs.shape[0] == 4 * f.shape[0]
+
+
+def test_color_map_index_rule():
+    cut = 0.05
+    d = np.array([0.0, cut / 2, cut, 2 * cut, 1e9], dtype=np.float32)
+    idx = visualization.distance_color_indices(d, cut)
+    assert idx.tolist() == [0, int(np.float32(0.5) * np.float32(L - 1)), L - 1, L - 1, L - 1]
+    cols = visualization.distances_to_vertex_colors(d, cut)
+    assert cols.dtype == np.uint8 and cols.shape == (5, 3)
+    assert np.array_equal(cols, visualization.PARULA[idx])
+    t = visualization.PARULA
+    assert t.shape == (L, 3)
+    assert t[0, 2] > t[0, 0] and t[0, 2] > t[0, 1]                          # blue
+    assert t[-1, 0] > 200 and t[-1, 1] > 200 and t[-1, 2] < 60               # yellow
+    assert t[L // 2, 1] > t[L // 2, 0]                                       # green-ish middle
+
+
+def test_colored_ply_round_trip(tmp_path):
+    v, f = eval_spec.icosphere(1, 0.5)
+    rng = np.random.default_rng(0)
+    col = rng.integers(0, 256, size=(v.shape[0], 3), dtype=np.uint8)
+    p = str(tmp_path / 'c.ply')
+    meshio.write_ply_mesh_colored(p, v, f, col)
+    v2, f2 = meshio.read_ply_mesh(p)
+    assert np.array_equal(v2, v.astype(np.float32)) and np.array_equal(f2, f.astype(np.int32))
+    assert np.array_equal(meshio.read_ply_vertex_colors(p), col)
+    meshio.write_ply_mesh(str(tmp_path / 'n.ply'), v, f)
+    assert meshio.read_ply_vertex_colors(str(tmp_path / 'n.ply')) is None
+    head = open(p, 'rb').read(400).split(b'end_header')[0].decode()
+    for c in ('red', 'green', 'blue', 'alpha'):
+        assert 'property uchar {}'.format(c) in head
+
+
+def test_obj_reader(tmp_path):
+    p = tmp_path / 'm.obj'
+    p.write_text('# quad and a triangle\nv 0 0 0\nv 1 0 0\nv 1 1 0\nv 0 1 0\nvn 0 0 1\nvt 0 0\n'
+                 'f 1/1/1 2/1/1 3/1/1 4/1/1\nf -4//1 -2//1 -1//1\nf 2 3 4\n')
+    v, f = meshio.read_obj_mesh(str(p))
+    assert v.shape == (4, 3) and v.dtype == np.float32
+    assert f.tolist() == [[0, 1, 2], [0, 2, 3], [0, 2, 3], [1, 2, 3]]
+    (tmp_path / 'bad.obj').write_text('v 0 0 0\nf 1 2 3\n')
+    with pytest.raises(ValueError):
+        meshio.read_obj_mesh(str(tmp_path / 'bad.obj'))
+
+
+def test_png_round_trip(tmp_path):
+    rng = np.random.default_rng(1)
+    img = rng.integers(0, 256, size=(17, 23, 3), dtype=np.uint8)
+    p = str(tmp_path / 'a.png')
+    visualization.write_png(p, img)
+    data = open(p, 'rb').read()
+    assert data[:8] == b'\x89PNG\r\n\x1a\n'
+    # decode by hand: IHDR then one IDAT
+    assert data[12:16] == b'IHDR'
+    n = int.from_bytes(data[33:37], 'big')
+    assert data[37:41] == b'IDAT'
+    rows = np.frombuffer(zlib.decompress(data[41:41 + n]), dtype=np.uint8).reshape(17, 1 + 23 * 3)
+    assert np.all(rows[:, 0] == 0) and np.array_equal(rows[:, 1:].reshape(17, 23, 3), img)
+    assert np.array_equal(visualization.read_png(p), img)
+    try:
+        from PIL import Image
+    except ImportError:
+        return
+    assert np.array_equal(np.asarray(Image.open(p).convert('RGB')), img)
+
+
+def _write_tables(root, method, shapes, values):
+    """values: {metric: [per shape]} -> <root>/<method>/ds/<metric>.csv with header = method."""
+    path = os.path.join(root, method, 'ds')
+    for m, vals in values.items():
+        write_metric_table(os.path.join(path, m + '.csv'), shapes, [method], [np.asarray(vals, dtype=np.float64)])
+    return path
+
+
+def test_table_assembly(tmp_path):
+    import pandas as pd
+    shapes = ['s0', 's1', 's2', 's3']
+    a = {'chamfer_distance': [0.01, 0.02, 0.03, 0.10], 'iou': [0.9, 0.8, 0.7, 0.6], 'f1': [0.95, 0.9, 0.85, 0.8], 'normal_error': [5, 6, 7, 30]}
+    b = {'chamfer_distance': [0.05, 0.04, 0.06, 0.05], 'iou': [0.5, 0.5, 0.6, 0.4], 'f1': [0.6, 0.6, 0.7, 0.5], 'normal_error': [9, 8, 7, 6]}
+    pa = _write_tables(str(tmp_path / 'res'), 'alpha', shapes, a)
+    pb = _write_tables(str(tmp_path / 'res'), 'beta', shapes, b)
+    pc = os.path.join(str(tmp_path / 'res'), 'gone', 'ds')
+    comp = str(tmp_path / 'comp' / 'ds')
+    out = comparison.assemble_quantitative_comparison(comp, [os.path.join(p, '{}.csv') for p in (pa, pb, pc)])
+    for m in comparison.METRICS:
+        arr = out[m]
+        assert arr.shape == (4, 3)
+        assert np.allclose(arr[:, 0], a[m]) and np.allclose(arr[:, 1], b[m]) and np.all(np.isnan(arr[:, 2]))
+        df = pd.read_csv(os.path.join(comp, m + '.csv'), index_col=0)
+        assert list(df.columns) == ['alpha', 'beta', 'gone']
+        assert list(df.index) == shapes + ['AVERAGE', 'MEDIAN', 'STDEV']
+        assert np.isclose(df.loc['MEDIAN', 'alpha'], np.median(a[m]))
+        assert np.isclose(df.loc['STDEV', 'beta'], np.std(b[m], ddof=1))
+        assert np.isnan(df.loc['AVERAGE', 'gone'])
+    # stats rows are dropped on read: a second assembly of the written tables gives the same arrays
+    again = comparison.assemble_quantitative_comparison(str(tmp_path / 'comp2'), [os.path.join(comp, '{}.csv')])
+    assert np.allclose(again['iou'][:, :2], out['iou'][:, :2]) and again['iou'].shape == (4, 3)
+
+    mean_file = str(tmp_path / 'comp' / 'ds' / 'comp_mean.csv')
+    reports = [tuple(os.path.join(p, m + '.csv') for m in ('chamfer_distance', 'iou', 'f1', 'normal_error')) for p in (pa, pb, pc)]
+    comparison.make_dataset_comparison(reports, mean_file)
+    df = pd.read_csv(mean_file, index_col=0)
+    assert list(df.index) == ['beta', 'alpha', 'gone']                      # descending mean Chamfer, NaN last
+    assert np.isclose(df.loc['alpha', 'Mean chamfer_distance'], np.mean(a['chamfer_distance']))
+    assert np.isclose(df.loc['alpha', 'Median normal_error'], pd.Series(a['normal_error'], dtype=float).median())
+    assert np.isclose(df.loc['beta', 'Stdev iou'], pd.Series(b['iou']).std(ddof=1))
+    assert np.isnan(df.loc['gone', 'Mean f1'])
+    for m in ('chamfer_distance', 'iou', 'f1', 'normal_error'):
+        for s in ('Mean', 'Median', 'Stdev'):
+            assert '{} {}'.format(s, m) in df.columns
+
+
+def test_html_report(tmp_path):
+    comp = tmp_path / 'results' / 'comp' / 'ds'
+    shapes = ['shape_a', 'shape_b']
+    methods = ['m1', 'm2', 'm3']
+    pc = [str(comp / 'pc_rend' / (s + '.png')) for s in shapes]
+    gt = [str(comp / 'mesh_gt_rend' / (s + '.png')) for s in shapes]
+    cd = [[str(comp / m / 'cd_vis_rend' / (s + '.png')) for s in shapes] for m in methods]
+    img = np.full((4, 4, 3), 200, dtype=np.uint8)
+    for p in pc + gt + cd[0] + cd[1]:
+        visualization.write_png(p, img)
+    metrics_cd = [[0.0123, 0.02], [0.03, 0.04], [float('nan')] * 2]
+    metrics_iou = [[0.5, 0.6], [0.7, 0.8], [float('nan')] * 2]
+    metrics_nc = [[7, 8], [9, 10], [float('nan')] * 2]
+    out = str(comp / 'comp_html.html')
+    comparison.make_html_report(out, 'ds', pc, gt, cd, 0.05, metrics_cd, metrics_iou, metrics_nc)
+    text = open(out).read()
+    body = text.split('<tbody>')[1]
+    assert body.count('<tr>') == len(shapes)
+    header = text.split('<thead>')[1].split('</thead>')[0]
+    assert header.count('<th') == len(methods) + 3
+    for m in methods:
+        assert '>{}</th>'.format(m) in header
+    assert 'CD: 1.23, IoU: 0.50, NCE: 7.00' in text
+    srcs = re.findall(r'src="([^"]+)"', text)
+    assert len(srcs) == len(shapes) * (2 + 2)
+    for s in srcs:
+        assert not os.path.isabs(s) and os.path.isfile(os.path.join(os.path.dirname(out), s))
+    rows = body.split('<tr>')[1:]
+    for r in rows:
+        assert r.count('missing') == 1                                     # m3 has no renders
+
+
+def test_metrics_caption():
+    assert comparison.metrics_caption(0.0123, 0.5, 7) == 'CD: 1.23, IoU: 0.50, NCE: 7.00'
+
+
+def test_camera_matches_hand_computation():
+    verts = np.array([[-1.0, 0.0, 2.0], [3.0, 2.0, 4.0]])
+    eye, M, focal = visualization.camera(verts, 1024)
+    c = np.array([1.0, 1.0, 3.0])
+    s = math.sqrt(0.5)
+    # R = Ry(pi/4) Rx(pi/4), columns: right, up, back
+    R = np.array([[s, 0.5, 0.5], [0.0, s, -s], [-s, 0.5, 0.5]])
+    assert np.allclose(visualization.euler_sxyz(math.pi / 4, math.pi / 4, 0.0), R, atol=1e-12)
+    assert np.allclose(eye, c + 2.2 * np.array([0.5, -s, 0.5]), atol=1e-12)
+    assert np.allclose(M, R.T, atol=1e-12)
+    assert np.isclose(focal, 512.0 / math.tan(math.radians(22.5)))
+    # the box centre projects to the image centre at depth 2.2
+    sx, sy, z = vis_spec.project(c[None], visualization.camera_array(eye, M, focal), 1024, 1024)
+    assert abs(sx[0] - 512) < 1e-3 and abs(sy[0] - 512) < 1e-3 and abs(z[0] - 2.2) < 1e-5
+    # up (R y) goes up on the screen, right (R x) to the right
+    sx, sy, _ = vis_spec.project((c + 0.1 * R[:, 1])[None], visualization.camera_array(eye, M, focal), 1024, 1024)
+    assert sy[0] < 512
+    sx, sy, _ = vis_spec.project((c + 0.1 * R[:, 0])[None], visualization.camera_array(eye, M, focal), 1024, 1024)
+    assert sx[0] > 512
+
+
+def test_call_necessary(tmp_path):
+    a, b = tmp_path / 'a', tmp_path / 'b'
+    assert not visualization.call_necessary(str(a), str(b))                 # input missing
+    a.write_text('x')
+    assert visualization.call_necessary(str(a), str(b))                     # output missing
+    b.write_text('y')
+    os.utime(a, (1000, 1000))
+    os.utime(b, (2000, 2000))
+    assert not visualization.call_necessary(str(a), str(b))
+    os.utime(a, (3000, 3000))
+    assert visualization.call_necessary([str(a)], [str(b)])
+
+
+def test_vis_abi_declared():
+    header = open(os.path.join(HERE, '..', 'include', 'ppsurf_amd.h')).read()
+    declared = set(re.findall(r'^\w[\w\s\*]*?\b(pps_vis_\w+)\(', header, re.M))
+    expected = {'pps_vis_closest_slices', 'pps_vis_closest_point', 'pps_vis_raster_ws_bytes', 'pps_vis_raster_faces', 'pps_vis_raster_points',
+                'pps_vis_shade'}
+    assert declared == expected
+    assert expected <= set(_lib.SIGNATURES)
+    lib = _lib.lib()
+    for name in expected:
+        assert hasattr(lib, name)
+    assert lib.pps_abi_version() == 2
+    assert lib.pps_vis_closest_slices(0, 10) == -1 and lib.pps_vis_closest_slices(1000, 10) == 1
+    s = lib.pps_vis_closest_slices(150000, 20480)
+    assert 1 <= s <= 20480 // 64 + 1
+
+
+def test_device_functions_refuse_cpu_tensors():
+    v, f = eval_spec.icosphere(0)
+    with pytest.raises(_lib.PpsError):
+        visualization.closest_point_on_mesh(torch.from_numpy(v).float(), torch.from_numpy(f).int(), torch.zeros(4, 3))

@@ -645,6 +645,30 @@ int pps_vis_raster_points(const float* pts, int64_t n, const float* cam, int wid
 int pps_vis_shade(const void* keys, int width, int height, const float* verts, const int32_t* faces, const uint8_t* colors, uint32_t rgb,
                   const float* cam, uint8_t* out, void* stream);
 
+/* ---- dataset generation: virtual range scans and query points (csrc/pps_scan.hip) --------------------------------------------------------
+ * replaces: the external generator of the reference's datasets (BlenSor scans, trimesh / pysdf labels; only its settings.ini ships), driven
+ * by ppsurf_amd/make_dataset.py.  The intersection test, scanner model and generator are written out at the top of csrc/pps_scan.hip.
+ *   pps_scan_hit_slices   number of face slices S of pps_scan_first_hit for m rays against nf faces (a function of m and nf only).
+ *   pps_scan_first_hit    first hit of rays (orig f32 [m,3], dir f32 [m,3]) on the triangle soup corners f32 [nf,9] (pps_eval_face_stats),
+ *                         watertight, both faces, fp64: out_t f64 [m] (smallest t > 0 in units of |dir|, -1 for a miss), out_face int32 [m]
+ *                         (-1 for a miss), ties to the lowest face.  Any slices in [1, min(nf, 65535)]; partial_t f64 [S,m] and
+ *                         partial_face int32 [S,m] are scratch.  The result does not depend on S.
+ *   pps_scan_rays         one ray per pixel of every scan: cams f32 [n_scans,16] (device; eye, right, up, forward, tan(fov/2), sigma, 2
+ *                         unused) -> orig, dir f32 [n_scans res^2, 3] (dir unit), scan-major, rows top to bottom.
+ *   pps_scan_points       scan points out_pts f32 [n_scans res^2, 3] = orig + (t + sigma_s g) dir of the rays and their hits (NaN for a
+ *                         miss), g a standard normal keyed by (seed, stream_id, scan, pixel).
+ *   pps_scan_queries      out f32 [n_far + n_near, 3]: n_far points uniform in [-0.5, 0.5)^3 keyed by (seed, stream_id, index), then the
+ *                         surface samples surf_pts f32 [n_near,3] of faces surf_face int32 [n_near] moved along the unit face normal
+ *                         normal f32 [nf,3] by u radius, u uniform in [-1, 1). */
+int64_t pps_scan_hit_slices(int64_t m, int64_t nf);
+int pps_scan_first_hit(const float* corners, int64_t nf, const float* orig, const float* dir, int64_t m, int64_t slices, double* partial_t,
+                       int32_t* partial_face, double* out_t, int32_t* out_face, void* stream);
+int pps_scan_rays(const float* cams, int n_scans, int res, float* orig, float* dir, void* stream);
+int pps_scan_points(const float* orig, const float* dir, const double* t, const int32_t* face, const float* cams, int n_scans, int res, uint64_t seed,
+                    uint64_t stream_id, float* out_pts, void* stream);
+int pps_scan_queries(const float* surf_pts, const int32_t* surf_face, const float* normal, int64_t n_far, int64_t n_near, uint64_t seed,
+                     uint64_t stream_id, float radius, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,11 @@ SIGNATURES = {
     'pps_vis_raster_faces': (_I, [_P, _I64, _P, _I64, _P, _I, _I, _P, _SZ, _P, _P]),
     'pps_vis_raster_points': (_I, [_P, _I64, _P, _I, _I, _c.c_float, _P, _P]),
     'pps_vis_shade': (_I, [_P, _I, _I, _P, _P, _P, _c.c_uint32, _P, _P, _P]),
+    'pps_scan_hit_slices': (_I64, [_I64, _I64]),
+    'pps_scan_first_hit': (_I, [_P, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
+    'pps_scan_rays': (_I, [_P, _I, _I, _P, _P, _P]),
+    'pps_scan_points': (_I, [_P, _P, _P, _P, _P, _I, _I, _c.c_uint64, _c.c_uint64, _P, _P]),
+    'pps_scan_queries': (_I, [_P, _P, _P, _I64, _I64, _c.c_uint64, _c.c_uint64, _c.c_float, _P, _P]),
 }
 
 _lib = None

@@ -669,6 +669,28 @@ int pps_scan_points(const float* orig, const float* dir, const double* t, const 
 int pps_scan_queries(const float* surf_pts, const int32_t* surf_face, const float* normal, int64_t n_far, int64_t n_near, uint64_t seed,
                      uint64_t stream_id, float radius, float* out, void* stream);
 
+/* ---- preparation of raw scans: voxel-grid subsampling and statistical outlier removal (csrc/pps_cloud.hip) --------------------------------
+ * new capability (the reference leaves sub-sampling to its users, source/occupancy_data_module.py:183-184), driven by ppsurf_amd/cloud.py.
+ * The rules are written out at the top of csrc/pps_cloud.hip and in DESIGN.md section 12; every result is a pure function of its inputs.
+ *   pps_cloud_table_capacity  the power of two >= max(2 n, 64): default size of the cell table for n points.
+ *   pps_cloud_voxel_count     number of occupied cells of pts f32 [n,3] (device) in the grid of lo, hi (HOST f32 [3], per-axis minimum and
+ *                             maximum of pts), h and inv_h = 1 / h -> count u64 [1] (device).  table u64 [capacity] is scratch, capacity a
+ *                             power of two > n.  More than 2^20 cells along an axis, h <= 0 or a bad capacity: PPS_ERR_ARG, nothing is
+ *                             launched or written.
+ *   pps_cloud_voxel_select    same grid; keep u8 [n] = 1 for the point of every cell nearest to the cell centre (ties to the lowest index),
+ *                             0 elsewhere; count as above.  table, best u64 [capacity] are scratch.  Neither result depends on capacity.
+ *   pps_cloud_mean_knn_dist   m f64 [n]: mean over columns 1..k of sqrt(double(d2[i, j])), d2 f32 [n, k + 1] ascending per row.
+ *   pps_cloud_outlier_stats   out f64 [3] = mean of m, population standard deviation of m, mean + ratio * deviation; fixed summation order.
+ *   pps_cloud_outlier_keep    keep u8 [n] = (m[i] <= stats[2]). */
+int64_t pps_cloud_table_capacity(int64_t n);
+int pps_cloud_voxel_count(const float* pts, int64_t n, const float* lo, const float* hi, float h, float inv_h, uint64_t* table, int64_t capacity,
+                          uint64_t* count, void* stream);
+int pps_cloud_voxel_select(const float* pts, int64_t n, const float* lo, const float* hi, float h, float inv_h, uint64_t* table, uint64_t* best,
+                           int64_t capacity, uint64_t* count, uint8_t* keep, void* stream);
+int pps_cloud_mean_knn_dist(const float* d2, int64_t n, int k, double* m, void* stream);
+int pps_cloud_outlier_stats(const double* m, int64_t n, double ratio, double* out, void* stream);
+int pps_cloud_outlier_keep(const double* m, int64_t n, const double* stats, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,12 @@ SIGNATURES = {
     'pps_scan_rays': (_I, [_P, _I, _I, _P, _P, _P]),
     'pps_scan_points': (_I, [_P, _P, _P, _P, _P, _I, _I, _c.c_uint64, _c.c_uint64, _P, _P]),
     'pps_scan_queries': (_I, [_P, _P, _P, _I64, _I64, _c.c_uint64, _c.c_uint64, _c.c_float, _P, _P]),
+    'pps_cloud_table_capacity': (_I64, [_I64]),
+    'pps_cloud_voxel_count': (_I, [_P, _I64, _P, _P, _c.c_float, _c.c_float, _P, _I64, _P, _P]),
+    'pps_cloud_voxel_select': (_I, [_P, _I64, _P, _P, _c.c_float, _c.c_float, _P, _P, _I64, _P, _P, _P]),
+    'pps_cloud_mean_knn_dist': (_I, [_P, _I64, _I, _P, _P]),
+    'pps_cloud_outlier_stats': (_I, [_P, _I64, _c.c_double, _P, _P]),
+    'pps_cloud_outlier_keep': (_I, [_P, _I64, _P, _P, _P]),
 }
 
 _lib = None

@@ -17,6 +17,11 @@ import torch
 from . import meshio, spatial
 
 
+def cloud_enabled(max_points=None, voxel_size=None, outlier_k=0):
+    """True when the data module's arguments ask for a preparation of the input cloud (the defaults ask for none)."""
+    return max_points is not None or voxel_size is not None or bool(outlier_k)
+
+
 def in_file_is_dataset(in_file: str):
     return os.path.splitext(in_file)[1].lower() == '.txt'
 
@@ -39,28 +44,41 @@ def get_pc_file(in_file, shape_name):
     return in_file
 
 
-def load_shape_data_pc(in_file, padding_factor, shape_name, normalize=False):
-    """occupancy_data_module.py:227-253 (without the debug PLY and the kd-tree)."""
+def load_shape_data_pc(in_file, padding_factor, shape_name, normalize=False, prepare=None, device='cuda'):
+    """occupancy_data_module.py:227-253 (without the debug PLY and the kd-tree).  prepare: keyword arguments of cloud.prepare_cloud for a raw
+    scan (single files only); the cloud is prepared FIRST and normalised from the kept points, whose box the item then carries."""
     pts_file = get_pc_file(in_file, shape_name)
     pts = meshio.load_pts(pts_file)
+    if prepare:
+        from . import cloud
+        idx, _ = cloud.prepare_cloud(pts, device=device, **prepare)
+        if idx.shape[0] == 0:
+            raise ValueError('no point of {} is left after the preparation'.format(pts_file))
+        pts = pts[idx]
     if pts.shape[1] > 3:
         nrm = pts[:, 3:6]
         normals = nrm / np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-20)
         pts = pts[:, :3]
     else:
         normals = np.zeros(pts.shape, dtype=np.float64)            # the reference's zeros_like of trimesh's float64 vertices
+    out = {}
     if normalize:
         bb_min, bb_max = pts.min(axis=0), pts.max(axis=0)
+        if prepare:                                                # predict_step de-normalises with these instead of reloading the file
+            out['_bb_center'] = np.asarray((bb_min + bb_max) * 0.5, dtype=np.float64)
+            out['_scale'] = np.float64(np.max(bb_max - bb_min) * (1.0 + padding_factor))
         pts = (pts - (bb_min + bb_max) * 0.5) / (np.max(bb_max - bb_min) * (1.0 + padding_factor))
     # pts are cast to float32 after normalisation, normals stay float64 (occupancy_data_module.py:236-241; tests/golden/batch_manifest.json)
-    return {'pts_ms': pts.astype(np.float32), 'normals_ms': normals.astype(np.float64), 'pc_file_in': pts_file}
+    out.update({'pts_ms': pts.astype(np.float32), 'normals_ms': normals.astype(np.float64), 'pc_file_in': pts_file})
+    return out
 
 
 class ReconstructionDataset(torch.utils.data.Dataset):
     """PPSurfReconstructionDataset (ppsurf_data_loader.py:126-141): the whole cloud, no sub-sampling."""
 
-    def __init__(self, in_file, padding_factor, with_raw=True):
+    def __init__(self, in_file, padding_factor, with_raw=True, prepare=None, device='cuda'):
         self.in_file, self.padding_factor, self.with_raw = in_file, padding_factor, with_raw
+        self.prepare, self.device = prepare, device
         self.shape_names = read_shape_list(in_file) if in_file_is_dataset(in_file) else [in_file]
 
     def __len__(self):
@@ -75,13 +93,15 @@ class ReconstructionDataset(torch.utils.data.Dataset):
         return np.empty((0, 3), dtype=np.float32), np.empty((0, 3), dtype=np.float32)
 
     def __getitem__(self, i):
-        data = load_shape_data_pc(self.in_file, self.padding_factor, self.shape_names[i], normalize=not in_file_is_dataset(self.in_file))
+        data = load_shape_data_pc(self.in_file, self.padding_factor, self.shape_names[i], normalize=not in_file_is_dataset(self.in_file),
+                                  prepare=self.prepare, device=self.device)
         q, dist = self._queries(self.shape_names[i])
         item = {'pts_ms': torch.from_numpy(data['pts_ms']), 'normals_ms': torch.from_numpy(data['normals_ms']),
                 'pc_file_in': data['pc_file_in'], 'pts_query_ms': torch.from_numpy(q), 'imp_surf_dist_ms': torch.from_numpy(dist),
                 'shape_id': torch.tensor(i)}
         if self.with_raw:
             item['pts_raw_ms'] = item['pts_ms']
+        item.update({k: v for k, v in data.items() if k.startswith('_')})       # box of a prepared cloud: passes _collate1 unbatched
         return item
 
 
@@ -382,7 +402,14 @@ def _collate1(item):
 
 class PocoDataModule:
     def __init__(self, in_file, workers, use_ddp, padding_factor, seed, manifold_points, patches_per_shape, do_data_augmentation,
-                 batch_size):
+                 batch_size, max_points=None, voxel_size=None, outlier_k=0, outlier_ratio=2.0):
+        # preparation of a raw scan (ppsurf_amd/cloud.py): single-file inputs of predict only
+        self.prepare = None
+        if cloud_enabled(max_points, voxel_size, outlier_k):
+            if in_file_is_dataset(in_file):
+                raise ValueError('max_points / voxel_size / outlier_k apply to single-file inputs of predict, not to the dataset list {}: '
+                                 'its queries and labels refer to the unprepared frame'.format(in_file))
+            self.prepare = {'max_points': max_points, 'voxel_size': voxel_size, 'outlier_k': int(outlier_k), 'outlier_ratio': float(outlier_ratio)}
         self.in_file, self.workers, self.use_ddp, self.padding_factor, self.seed = in_file, workers, use_ddp, padding_factor, seed
         self.manifold_points, self.patches_per_shape = manifold_points, patches_per_shape
         self.do_data_augmentation, self.batch_size = do_data_augmentation, batch_size
@@ -391,15 +418,22 @@ class PocoDataModule:
         self.device = 'cuda'
 
     def predict_dataloader(self):
-        ds = ReconstructionDataset(self.testset, self.padding_factor)
+        ds = ReconstructionDataset(self.testset, self.padding_factor, prepare=self.prepare, device=self.device)
         return (_collate1(ds[i]) for i in range(len(ds)))
 
+    def _no_prepare(self, what):
+        if self.prepare is not None:
+            raise ValueError('max_points / voxel_size / outlier_k apply to predict only, not to {}: queries and labels refer to the '
+                             'unprepared frame'.format(what))
+
     def test_dataloader(self):
+        self._no_prepare('test')
         ds = TestDataset(self.testset, self.padding_factor, self.num_pts_local, self.manifold_points, self.seed, self.device)
         return (_collate1(ds[i]) for i in range(len(ds)))
 
     def _fit_loader(self, set_file, augment, shuffle):
         import torch.distributed as dist
+        self._no_prepare('fit')
         ddp = bool(self.use_ddp) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         ds = TrainDataset(set_file, self.padding_factor, self.seed, self.use_ddp, self.manifold_points, self.patches_per_shape, augment,
                           self.num_pts_local)
@@ -416,8 +450,9 @@ class PocoDataModule:
 
 class PPSurfDataModule(PocoDataModule):
     def __init__(self, num_pts_local, in_file, workers, use_ddp, padding_factor, seed, manifold_points, patches_per_shape,
-                 do_data_augmentation, batch_size):
+                 do_data_augmentation, batch_size, max_points=None, voxel_size=None, outlier_k=0, outlier_ratio=2.0):
         super().__init__(in_file=in_file, workers=workers, use_ddp=use_ddp, padding_factor=padding_factor, seed=seed,
                          manifold_points=manifold_points, patches_per_shape=patches_per_shape,
-                         do_data_augmentation=do_data_augmentation, batch_size=batch_size)
+                         do_data_augmentation=do_data_augmentation, batch_size=batch_size, max_points=max_points, voxel_size=voxel_size,
+                         outlier_k=outlier_k, outlier_ratio=outlier_ratio)
         self.num_pts_local = num_pts_local

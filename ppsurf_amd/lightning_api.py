@@ -458,11 +458,22 @@ class PocoModel(_Base):
             return 0                                                   # every rank holds the same mesh; rank 0 writes it
         if mesh is not None:
             verts, faces = mesh
+            double = False
             if not in_file_is_dataset(self.in_file):               # de-normalise single files (poco_model.py:256-265)
-                raw = meshio.load_pts(pc_file_in)[:, :3]
-                bb_min, bb_max = raw.min(axis=0), raw.max(axis=0)
-                verts = verts * (np.max(bb_max - bb_min) * (1.0 + self.padding_factor)) + (bb_min + bb_max) * 0.5
-            meshio.write_ply_mesh(out_file_rec, verts, faces)
+                if '_bb_center' in batch:                           # a prepared cloud: the box of the KEPT points, carried by the item
+                    scale, center = batch['_scale'], batch['_bb_center']
+                else:
+                    raw = meshio.load_pts(pc_file_in)[:, :3]
+                    bb_min, bb_max = raw.min(axis=0), raw.max(axis=0)
+                    scale, center = np.max(bb_max - bb_min) * (1.0 + self.padding_factor), (bb_min + bb_max) * 0.5
+                verts = verts * scale + center
+                # geo-referenced coordinates: doubles when float32 would move a vertex by more than 1e-3 of the grid step (file units)
+                moved = np.abs(np.asarray(verts, dtype=np.float64) - np.asarray(verts, dtype=np.float32).astype(np.float64))
+                double = bool(moved.size) and float(moved.max()) > 1e-3 * float(scale) / self.gen_resolution_global
+            if double:
+                meshio.write_ply_mesh(out_file_rec, verts, faces, double=True)
+            else:
+                meshio.write_ply_mesh(out_file_rec, verts, faces)
         else:
             print('No reconstruction for {}'.format(pc_file_in))
         return 0

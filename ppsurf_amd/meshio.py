@@ -1,4 +1,4 @@
-"""Minimal PLY / XYZ / NPY IO for the predict path and the mesh evaluation (the reference uses trimesh, absent here).
+"""Minimal PLY / XYZ / NPY / LAS / STL / OFF / OBJ / PCD IO for the predict path and the mesh evaluation (the reference uses trimesh, absent here).
 
 Point clouds of datasets/abc_minimal are binary little-endian PLY written by trimesh
 (`element vertex n`, `property float x/y/z`, optional normals, `element face 0`); meshes are written the same way
@@ -77,8 +77,8 @@ def _fan(polys):
     return np.concatenate(tris, axis=0) if tris else np.zeros((0, 3), dtype=np.int64)
 
 
-def read_ply_mesh(path):
-    """Vertices float32 [nv,3] and triangles int32 [nf,3] of an ascii or binary PLY mesh (trimesh-written `03_meshes` files and
+def read_ply_mesh(path, dtype=np.float32):
+    """Vertices float32 [nv,3] (`dtype=np.float64` keeps the doubles of a `write_ply_mesh(..., double=True)` file) and triangles int32 [nf,3] of an ascii or binary PLY mesh (trimesh-written `03_meshes` files and
     write_ply_mesh): float or double x/y/z (other vertex properties skipped), face list `vertex_indices` (or `vertex_index`) of
     uchar/int/uint counts and int/uint indices, polygons fan-triangulated.  Other face properties and elements after `face` are skipped
     (binary: fixed-size ones only).  Raises ValueError on anything else or on an index outside [0, nv)."""
@@ -193,7 +193,7 @@ def read_ply_mesh(path):
         faces = np.zeros((0, 3), dtype=np.int64)
     if faces.size and (faces.min() < 0 or faces.max() >= verts.shape[0]):
         raise ValueError('PLY face index out of range: {}'.format(path))
-    return verts.astype(np.float32), faces.astype(np.int32)
+    return verts.astype(dtype), faces.astype(np.int32)
 
 
 def _fan_uniform(v):
@@ -202,8 +202,121 @@ def _fan_uniform(v):
     return np.stack([np.repeat(v[:, :1], k - 2, axis=1), v[:, 1:-1], v[:, 2:]], axis=2).reshape(-1, 3)
 
 
+def read_las_points(path):
+    """x, y, z float64 [n,3] of an uncompressed LAS 1.0-1.4 file, point formats 0-10 (ASPRS LAS specification, public header block):
+    offset to point data (byte 96), point format (104), record length (105), legacy number of points (107; for 1.4 the 64-bit field at 247
+    when the legacy one is 0), scale (131) and offset (155).  Every record starts with int32 X, Y, Z; xyz = int32 * scale + offset in float64,
+    as laspy's `las.xyz`.  Colours, intensity and classification are not read."""
+    import struct
+    with open(path, 'rb') as f:
+        head = f.read(375)
+        if len(head) < 227 or head[:4] != b'LASF':
+            raise ValueError('not a LAS file: {}'.format(path))
+        major, minor = head[24], head[25]
+        header_size, data_offset = struct.unpack_from('<HI', head, 94)
+        fmt, rec_len, n = struct.unpack_from('<BHI', head, 104)
+        if fmt & 0xC0:
+            raise ValueError('compressed LAS (LAZ) is not supported: {}: decompress it to .las or convert it to .npy first'.format(path))
+        if (major, minor) >= (1, 4) and n == 0 and len(head) >= 255:
+            n = struct.unpack_from('<Q', head, 247)[0]
+        if major != 1 or minor > 4 or fmt > 10 or rec_len < 12:
+            raise ValueError('unsupported LAS {}.{} point format {}: {}'.format(major, minor, fmt, path))
+        scale = np.array(struct.unpack_from('<3d', head, 131), dtype=np.float64)
+        offset = np.array(struct.unpack_from('<3d', head, 155), dtype=np.float64)
+        f.seek(data_offset)
+        raw = f.read(n * rec_len)
+    if len(raw) < n * rec_len:
+        raise ValueError('LAS file ends before its {} point records: {}'.format(n, path))
+    ints = np.ndarray((n, 3), dtype='<i4', buffer=raw, strides=(rec_len, 4)) if n else np.zeros((0, 3), dtype='<i4')
+    return ints.astype(np.float64) * scale[None] + offset[None]
+
+
+def read_stl_vertices(path):
+    """Facet corners float64 [3 nf, 3] of a binary or ascii STL as they are stored (three per facet, duplicates kept)."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    if len(data) >= 84:
+        nf = int(np.frombuffer(data, dtype='<u4', count=1, offset=80)[0])
+        if len(data) == 84 + 50 * nf:                      # the size test tells binary from ascii (binary headers may start with `solid` too)
+            rec = np.frombuffer(data, dtype=np.dtype([('n', '<f4', (3,)), ('v', '<f4', (3, 3)), ('a', '<u2')]), count=nf, offset=84)
+            return rec['v'].reshape(-1, 3).astype(np.float64)
+    if not data.lstrip()[:5].lower() == b'solid':
+        raise ValueError('neither a binary nor an ascii STL: {}'.format(path))
+    verts = [line.split()[1:4] for line in data.decode('ascii', 'replace').split('\n') if line.split()[:1] == ['vertex']]
+    v = np.array(verts, dtype=np.float64).reshape(-1, 3)
+    if v.shape[0] % 3:
+        raise ValueError('ascii STL with a vertex count that is no multiple of 3: {}'.format(path))
+    return v
+
+
+def read_off_vertices(path):
+    """Vertices float64 [nv,3] of an OFF / COFF / NOFF file: the `OFF` keyword (the counts `nv nf ne` on the same or the next line), then nv
+    lines that start with x y z (colours or normals after them are skipped); `#` comments and empty lines anywhere."""
+    with open(path, 'r') as f:
+        lines = [t for t in (line.split('#', 1)[0].split() for line in f) if t]
+    if not lines or not lines[0][0].upper().endswith('OFF'):
+        raise ValueError('not an OFF file: {}'.format(path))
+    counts = lines[0][1:] if len(lines[0]) > 1 else (lines[1] if len(lines) > 1 else [])
+    first = 1 if len(lines[0]) > 1 else 2
+    try:
+        nv = int(counts[0])
+        v = np.array([t[:3] for t in lines[first:first + nv]], dtype=np.float64).reshape(-1, 3)
+    except (IndexError, ValueError):
+        raise ValueError('malformed OFF file: {}'.format(path))
+    if v.shape[0] != nv:
+        raise ValueError('OFF file ends before its {} vertices: {}'.format(nv, path))
+    return v
+
+
+_PCD_TYPES = {('F', 4): 'f4', ('F', 8): 'f8', ('I', 1): 'i1', ('I', 2): 'i2', ('I', 4): 'i4', ('I', 8): 'i8',
+              ('U', 1): 'u1', ('U', 2): 'u2', ('U', 4): 'u4', ('U', 8): 'u8'}
+
+
+def read_pcd_points(path):
+    """x, y, z [n,3] of a PCD 0.7 file (Point Cloud Library), `DATA ascii` or `DATA binary`, any field list that holds x y z as 4- or 8-byte
+    floats (float64 out when they are 8-byte, float32 otherwise)."""
+    with open(path, 'rb') as f:
+        head = {}
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError('unterminated PCD header: {}'.format(path))
+            tok = line.decode('ascii', 'replace').split()
+            if not tok or tok[0].startswith('#'):
+                continue
+            head[tok[0].upper()] = tok[1:]
+            if tok[0].upper() == 'DATA':
+                break
+        body = f.read()
+    try:
+        fields, sizes, types = head['FIELDS'], [int(v) for v in head['SIZE']], head['TYPE']
+        counts = [int(v) for v in head.get('COUNT', ['1'] * len(fields))]
+        n = int(head['POINTS'][0]) if 'POINTS' in head else int(head['WIDTH'][0]) * int(head['HEIGHT'][0])
+        mode = head['DATA'][0].lower()
+    except (KeyError, IndexError, ValueError):
+        raise ValueError('incomplete PCD header: {}'.format(path))
+    for k in 'xyz':
+        if k not in fields or types[fields.index(k)].upper() != 'F' or sizes[fields.index(k)] not in (4, 8) or counts[fields.index(k)] != 1:
+            raise ValueError('PCD without float x y z fields: {}'.format(path))
+    out_type = np.float64 if any(sizes[fields.index(k)] == 8 for k in 'xyz') else np.float32
+    if mode == 'ascii':
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        rows = [line.split() for line in body.decode('ascii', 'replace').split('\n') if line.strip()][:n]
+        if len(rows) < n:
+            raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
+        return np.array([[r[starts[fields.index(k)]] for k in 'xyz'] for r in rows], dtype=out_type).reshape(n, 3)
+    if mode != 'binary':
+        raise ValueError('PCD DATA {} is not supported (ascii and binary are): {}'.format(mode, path))
+    dt = np.dtype([(name, '<' + _PCD_TYPES[(t.upper(), s)], (c,)) for name, s, t, c in zip(fields, sizes, types, counts)])
+    if len(body) < n * dt.itemsize:
+        raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
+    rec = np.frombuffer(body, dtype=dt, count=n)
+    return np.stack([rec[k][:, 0].astype(out_type) for k in 'xyz'], axis=1)
+
+
 def load_pts(pts_file: str) -> np.ndarray:
-    """source/occupancy_data_module.py:174-225 for the formats that need no third-party package."""
+    """source/occupancy_data_module.py:174-225 without a third-party package: the reference's formats (trimesh for STL / OBJ / OFF, laspy for
+    LAS) are read here from their published layouts.  LAS and 8-byte PCD coordinates stay float64."""
     ext = os.path.splitext(pts_file)[1].lower()
     if ext == '.npy':
         return np.load(pts_file)
@@ -213,15 +326,29 @@ def load_pts(pts_file: str) -> np.ndarray:
         return np.loadtxt(pts_file, ndmin=2)
     if ext == '.ply':
         return read_ply_vertices(pts_file)
+    if ext == '.las':
+        return read_las_points(pts_file)
+    if ext in ('.laz', '.copc', '.crs'):
+        raise ValueError('compressed LAS is not supported ({}): decompress it to .las or convert it to .npy first'.format(pts_file))
+    if ext == '.stl':
+        return read_stl_vertices(pts_file)
+    if ext == '.off':
+        return read_off_vertices(pts_file)
+    if ext == '.obj':
+        return read_obj_mesh(pts_file)[0]
+    if ext == '.pcd':
+        return read_pcd_points(pts_file)
     raise ValueError('Unknown point cloud type: {}'.format(pts_file))
 
 
-def write_ply_mesh(path, verts: np.ndarray, faces: np.ndarray):
+def write_ply_mesh(path, verts: np.ndarray, faces: np.ndarray, double=False):
+    """Binary little-endian PLY mesh; double=True stores `property double x/y/z` (geo-referenced coordinates lose centimetres in float32)."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    verts = np.asarray(verts, dtype='<f4')
+    verts = np.asarray(verts, dtype='<f8' if double else '<f4')
     faces = np.asarray(faces, dtype='<i4')
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {}\nproperty float x\nproperty float y\n'
-              'property float z\nelement face {}\nproperty list uchar int vertex_indices\nend_header\n').format(verts.shape[0], faces.shape[0])
+    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {2} x\nproperty {2} y\n'
+              'property {2} z\nelement face {1}\nproperty list uchar int vertex_indices\nend_header\n').format(
+                  verts.shape[0], faces.shape[0], 'double' if double else 'float')
     rec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
     rec['n'] = 3
     rec['v'] = faces

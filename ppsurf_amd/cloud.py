@@ -27,12 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib, meshio, ops
+from .geometry import _stream
 
 MAX_AXIS = 1 << 20
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _f3(v):

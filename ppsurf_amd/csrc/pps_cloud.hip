@@ -35,6 +35,7 @@ struct Grid {
     float h, inv_h;
 };
 
+// Not mix64 of pps_rng.h: a hash finaliser without the additive constant (0 maps to 0), and the voxel results do not depend on it.
 __device__ __forceinline__ u64 cloud_mix64(u64 x) {          // splitmix64 finaliser: spreads the keys of neighbouring cells over the table
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
     x ^= x >> 27; x *= 0x94D049BB133111EBull;

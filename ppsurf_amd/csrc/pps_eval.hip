@@ -3,39 +3,24 @@
 // metrics.  The reference runs trimesh / pysdf / pykdtree on the CPU in a process pool; the 1-NN searches of the Chamfer and normal-error
 // steps reuse the kNN kernels of pps_knn.hip (k = 1).
 //
-// Counter-based generator of the surface sampling (restated in numpy by tests/eval_spec.py; keep the two in step):
-//     mix(x)    = splitmix64 finaliser of x + 0x9E3779B97F4A7C15:
-//                   z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
-//                   return z ^ (z >> 31)                                                       (all uint64, wrapping)
-//     key       = mix(mix(seed) ^ stream_id)
-//     bits(i,d) = mix(key ^ ((uint64)i << 2 | d))            sample index i, draw d in {0, 1, 2}
-//     u53       = (bits(i,0) >> 11) * 2^-53                  fp64 in [0, 1)
-//     r1, r2    = (bits(i,1) >> 40) * 2^-24, (bits(i,2) >> 40) * 2^-24          fp32 in [0, 1)
+// Surface sampling (restated in numpy by tests/eval_spec.py; keep the two in step), generator and its conversions as in pps_rng.h:
+//   u53       = unit53(bits(i << 2)),  r1, r2 = unit24(bits(i << 2 | 1)), unit24(bits(i << 2 | 2))           sample index i
 //   face      = upper bound of t = u53 * total in the inclusive fp64 prefix of the face areas (first j with prefix[j] > t, i.e.
 //               searchsorted(prefix, t, side='right')); if t rounds up to total, the first j with prefix[j] == total (the last face of
 //               positive area).  A face of zero area is never drawn.
 //   if r1 + r2 > 1 (fp32): r1, r2 = 1 - r1, 1 - r2              (trimesh's parallelogram fold)
 //   point     = (r1 * e1 + r2 * e2) + v0, e1 = v1 - v0, e2 = v2 - v0, fp32 without contraction (trimesh's order of operations)
 // Sample i depends on (seed, stream_id, i) only: the first k samples of a draw of n are the draw of k.
+//
+// The winding number is one operation of the sliced face sweep of pps_sweep.h.
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_rng.h"
+#include "pps_sweep.h"
 #include "../../include/ppsurf_amd.h"
 
 namespace {
-
-constexpr int WIND_BLOCK = 256;
-constexpr int WIND_QPL = 4;                                   // queries per lane, held in registers
-constexpr int WIND_QBLOCK = WIND_BLOCK * WIND_QPL;            // queries per workgroup
-constexpr int64_t WIND_TARGET_BLOCKS = 16384;                 // ~10 rounds of 256 CUs x 6 resident workgroups: a short tail
-constexpr int64_t WIND_MIN_SLICE = 64;                        // faces per slice, at least
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // area = 0.5 |e1 x e2|, unit normal (e1 x e2) / |e1 x e2| (0 for a degenerate face), corners v0 v1 v2 face-major [nf, 9].  A face with an
 // index outside [0, nv) reads no vertex and gets area 0, normal 0 and corners 0.
@@ -74,9 +59,9 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ c
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint64_t ctr = (uint64_t)i << 2;
-    const double u = (double)(mix64(key ^ ctr) >> 11) * 0x1.0p-53;
-    float r1 = (float)(uint32_t)(mix64(key ^ (ctr | 1)) >> 40) * 0x1.0p-24f;
-    float r2 = (float)(uint32_t)(mix64(key ^ (ctr | 2)) >> 40) * 0x1.0p-24f;
+    const double u = unit53(rng_bits(key, ctr));
+    float r1 = unit24(rng_bits(key, ctr | 1));
+    float r2 = unit24(rng_bits(key, ctr | 2));
     const double total = prefix[nf - 1];
     const double t = u * total;
     int64_t lo = 0, hi = nf;                                  // upper bound: first j with prefix[j] > t
@@ -126,34 +111,22 @@ __device__ __forceinline__ float atan2_fast(float y, float x) {
     return copysignf(r, y);
 }
 
-// Partial winding sums: workgroup (qb, s) adds, for WIND_QBLOCK queries, the half solid angles atan2(det, D) of the faces of slice s in face
-// order (Van Oosterom-Strackee: Omega_f = 2 atan2(det[a b c], |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|), a b c = corners - query).
-// The face index is wave-uniform, so the nine corner floats of a face are scalar loads shared by the wave; each lane keeps WIND_QPL
-// queries and their fp32 sums in registers.  partial[s, q] = sum over slice s, no atomics.  The lengths use the bare v_sqrt_f32 (1 ulp):
-// sqrtf's correctly rounded expansion (denormal scaling + two correction steps) was about half of the loop.
-__global__ __launch_bounds__(WIND_BLOCK) void winding_partial_kernel(const float* __restrict__ corners, int64_t nf, const float* __restrict__ query,
-                                                                     int64_t m, int64_t per_slice, float* __restrict__ partial) {
-    const int64_t q0 = (int64_t)blockIdx.x * WIND_QBLOCK + threadIdx.x;
-    const int64_t f0 = (int64_t)blockIdx.y * per_slice;
-    const int64_t f1 = f0 + per_slice < nf ? f0 + per_slice : nf;
-    float px[WIND_QPL], py[WIND_QPL], pz[WIND_QPL], acc[WIND_QPL];
-#pragma unroll
-    for (int j = 0; j < WIND_QPL; ++j) {
-        int64_t q = q0 + (int64_t)j * WIND_BLOCK;
-        q = q < m ? q : m - 1;
-        px[j] = query[3 * q];
-        py[j] = query[3 * q + 1];
-        pz[j] = query[3 * q + 2];
-        acc[j] = 0.f;
-    }
-    for (int64_t f = f0; f < f1; ++f) {
-        const float* c = corners + 9 * f;
+// Partial winding sums (pps_sweep.h): every query adds the half solid angles atan2(det, D) of the faces of its slice in face order, in fp32
+// (Van Oosterom-Strackee: Omega_f = 2 atan2(det[a b c], |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|), a b c = corners - query).
+// The lengths use the bare v_sqrt_f32 (1 ulp): sqrtf's correctly rounded expansion (denormal scaling + two correction steps) was about
+// half of the loop.
+struct WindingOp {
+    const float* __restrict__ query;
+    float* __restrict__ partial;
+    struct Item { float px, py, pz, acc; };
+    __device__ __forceinline__ Item load(int64_t q) const { return {query[3 * q], query[3 * q + 1], query[3 * q + 2], 0.f}; }
+    __device__ __forceinline__ void face(const float* __restrict__ c, int32_t, Item (&it)[SWEEP_IPL]) const {
         const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5], c6 = c[6], c7 = c[7], c8 = c[8];
 #pragma unroll
-        for (int j = 0; j < WIND_QPL; ++j) {
-            const float ax = c0 - px[j], ay = c1 - py[j], az = c2 - pz[j];
-            const float bx = c3 - px[j], by = c4 - py[j], bz = c5 - pz[j];
-            const float cx = c6 - px[j], cy = c7 - py[j], cz = c8 - pz[j];
+        for (int j = 0; j < SWEEP_IPL; ++j) {
+            const float ax = c0 - it[j].px, ay = c1 - it[j].py, az = c2 - it[j].pz;
+            const float bx = c3 - it[j].px, by = c4 - it[j].py, bz = c5 - it[j].pz;
+            const float cx = c6 - it[j].px, cy = c7 - it[j].py, cz = c8 - it[j].pz;
             const float la = __builtin_amdgcn_sqrtf(fmaf(ax, ax, fmaf(ay, ay, az * az)));
             const float lb = __builtin_amdgcn_sqrtf(fmaf(bx, bx, fmaf(by, by, bz * bz)));
             const float lc = __builtin_amdgcn_sqrtf(fmaf(cx, cx, fmaf(cy, cy, cz * cz)));
@@ -162,16 +135,11 @@ __global__ __launch_bounds__(WIND_BLOCK) void winding_partial_kernel(const float
             const float bc = fmaf(bx, cx, fmaf(by, cy, bz * cz));
             const float ca = fmaf(cx, ax, fmaf(cy, ay, cz * az));
             const float den = fmaf(la * lb, lc, fmaf(ab, lc, fmaf(bc, la, ca * lb)));
-            acc[j] += atan2_fast(det, den);
+            it[j].acc += atan2_fast(det, den);
         }
     }
-    float* out = partial + (int64_t)blockIdx.y * m;
-#pragma unroll
-    for (int j = 0; j < WIND_QPL; ++j) {
-        const int64_t q = q0 + (int64_t)j * WIND_BLOCK;
-        if (q < m) out[q] = acc[j];
-    }
-}
+    __device__ __forceinline__ void store(const Item& it, int64_t k) const { partial[k] = it.acc; }
+};
 
 // w[q] = (sum over s in slice order of partial[s, q], fp64) / (2 pi)
 __global__ __launch_bounds__(256) void winding_sum_kernel(const float* __restrict__ partial, int64_t slices, int64_t m, double* __restrict__ w) {
@@ -244,31 +212,21 @@ int pps_eval_sample_surface(const float* corners, const double* area_prefix, int
     if (nf < 1 || n < 0 || nf > INT32_MAX) return PPS_ERR_ARG;
     if (n == 0) return PPS_OK;
     if (!corners || !area_prefix || !out_pts || !out_face) return PPS_ERR_ARG;
-    const uint64_t key = mix64(mix64(seed) ^ stream_id);
-    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, corners, area_prefix, nf, n, key, out_pts, out_face);
+    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, corners, area_prefix, nf, n,
+                       rng_key(seed, stream_id), out_pts, out_face);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 
-int64_t pps_eval_winding_slices(int64_t m, int64_t nf) {
-    if (m < 1 || nf < 1) return -1;
-    const int64_t qblocks = (m + WIND_QBLOCK - 1) / WIND_QBLOCK;
-    int64_t s = (WIND_TARGET_BLOCKS + qblocks - 1) / qblocks;
-    const int64_t smax = (nf + WIND_MIN_SLICE - 1) / WIND_MIN_SLICE;
-    s = s < smax ? s : smax;
-    const int64_t per = (nf + s - 1) / s;                     // no empty slice
-    return (nf + per - 1) / per;
-}
+int64_t pps_eval_winding_slices(int64_t m, int64_t nf) { return sweep_slices(m, nf); }
 
+// Unlike the other sweeps, this one insists on the planner's slice count: its fp32 partial sums depend on where the slices are cut.
 int pps_eval_winding(const float* corners, int64_t nf, const float* query, int64_t m, int64_t slices, float* partial, double* out_w, void* stream) {
     if (nf < 1 || m < 0) return PPS_ERR_ARG;
     if (m == 0) return PPS_OK;
-    if (slices != pps_eval_winding_slices(m, nf)) return PPS_ERR_ARG;
+    if (slices != sweep_slices(m, nf)) return PPS_ERR_ARG;
     if (!corners || !query || !partial || !out_w) return PPS_ERR_ARG;
-    const int64_t qblocks = (m + WIND_QBLOCK - 1) / WIND_QBLOCK;
-    if (qblocks > INT32_MAX || slices > 65535) return PPS_ERR_ARG;
-    const int64_t per = (nf + slices - 1) / slices;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(winding_partial_kernel, dim3((unsigned)qblocks, (unsigned)slices), dim3(WIND_BLOCK), 0, st, corners, nf, query, m, per, partial);
+    if (!sweep_launch(corners, nf, m, slices, WindingOp{query, partial}, st)) return PPS_ERR_ARG;
     hipLaunchKernelGGL(winding_sum_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float*)partial, slices, m, out_w);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }

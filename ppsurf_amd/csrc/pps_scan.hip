@@ -1,7 +1,7 @@
 // Dataset generation (ppsurf_amd/make_dataset.py): virtual range scans of a triangle mesh and the query points of its signed-distance labels.
 // The reference downloads abc_minimal ready-made; the generator that made it (BlenSor scans, trimesh / pysdf labels) is not part of it.
 // The scanner model below is this project's own: it does not claim to match BlenSor.  The labels reuse pps_vis_closest_point (distance)
-// and pps_eval_winding (sign); pps_eval_sample_surface and pps_eval_face_stats feed the near-surface queries.
+// and pps_eval_winding (sign); pps_eval_sample_surface and pps_eval_face_stats feed the near-surface queries (ppsurf_amd/geometry.py).
 //
 // First hit -- rays (origin o, direction d, fp32 [m,3] each) against a triangle soup given as corners f32 [nf,9] (pps_eval_face_stats).
 // Watertight test of Woop, Benthin & Wald (JCGT 2(1), 2013), both faces of a triangle (no back-face culling), every step in fp64 from the
@@ -15,7 +15,8 @@
 //     T = (U (Sz A_kz) + V (Sz B_kz)) + W (Sz C_kz);  t = T / det;  hit iff t > 0     (NaN anywhere is a miss)
 // The result of a ray is the smallest t and its face, ties to the lowest face id; t = -1 and face = -1 for a miss.  t is the distance
 // along d in units of |d|.  Pass 1 keeps, per ray and face slice, the smallest t (strict <, faces in order); pass 2 takes the minimum over
-// the slices in slice order (strict <).  The result depends on (corners, o, d) only, not on the slice count.  Brute force: no BVH.
+// the slices in slice order (strict <).  The result depends on (corners, o, d) only, not on the slice count.  Brute force: no BVH; pass 1
+// is an operation of the sliced face sweep of pps_sweep.h.
 //
 // Scanner (one launch per stage covers every scan of a mesh; the cameras are built on the host, make_dataset.scan_cameras).  Camera s of
 // cams f32 [n_scans,16]: eye 0..2, right 3..5, up 6..8, forward 9..11 (unit, orthogonal), tan(fov / 2) 12, sigma_s 13, 14..15 unused.
@@ -23,34 +24,24 @@
 //     x = ((2 col + 1) / res - 1) tan,  y = (1 - (2 row + 1) / res) tan;  q_k = (forward_k + x right_k) + y up_k
 //     d_k = q_k / sqrt((q_0 q_0 + q_1 q_1) + q_2 q_2),  o = eye
 // A ray that hits at t gives the point o + (t + sigma_s g) d (fp64, then fp32), g a standard normal by Box-Muller from the counter-based
-// generator of pps_eval.hip (mix64, key = mix(mix(seed) ^ stream_id)) at counter c = (s << 32 | pixel) << 2:
-//     u1 = ((mix(key ^ c) >> 11) + 1) 2^-53 in (0, 1],  u2 = (mix(key ^ (c | 1)) >> 11) 2^-53 in [0, 1)
+// generator of pps_rng.h (mix, key, bits, unit53, unit24 as defined there) at counter c = (s << 32 | pixel) << 2:
+//     u1 = unit53_pos(bits(c)) in (0, 1],  u2 = unit53(bits(c | 1)) in [0, 1)
 //     g  = sqrt(-2 log u1) cos(2 pi u2)
 // A miss writes NaN; the caller drops misses, which keeps the (scan, pixel) order of the rest.
 //
 // Query points (key as above, counter c = i << 2 for query i): i < n_far is uniform in [-0.5, 0.5)^3, coordinate k exactly
-// (mix(key ^ (c | k)) >> 40) 2^-24 - 0.5 in fp32.  Query n_far + j takes surface sample j (pps_eval_sample_surface, its own stream) and moves
-// it along the unit normal n of its face by u r, u = (mix(key ^ c) >> 40) 2^-23 - 1 in [-1, 1) (fp32, exact): p + (u r) n in fp64, then fp32.
+// unit24(bits(c | k)) - 0.5 in fp32.  Query n_far + j takes surface sample j (pps_eval_sample_surface, its own stream) and moves
+// it along the unit normal n of its face by u r, u = 2 unit24(bits(c)) - 1 in [-1, 1) (fp32, exact): p + (u r) n in fp64, then fp32.
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_rng.h"
+#include "pps_sweep.h"
 #include "../../include/ppsurf_amd.h"
 
 namespace {
 
-constexpr int HIT_BLOCK = 256;
-constexpr int HIT_RPL = 4;                                    // rays per lane, held in registers
-constexpr int HIT_RBLOCK = HIT_BLOCK * HIT_RPL;
-constexpr int64_t HIT_TARGET_BLOCKS = 16384;
-constexpr int64_t HIT_MIN_SLICE = 64;
 constexpr int CAM_FLOATS = 16;
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ float pick(float a, float b, float c, int k) { return k == 0 ? a : (k == 1 ? b : c); }
 
@@ -81,31 +72,23 @@ __device__ __forceinline__ RayW ray_setup(const float* __restrict__ orig, const 
     return w;
 }
 
-// Pass 1: workgroup (rb, s) tests the faces of slice s in face order for HIT_RBLOCK rays (HIT_RPL per lane).  The face index is
-// wave-uniform: the nine corner floats are scalar loads shared by the wave.
-__global__ __launch_bounds__(HIT_BLOCK) void hit_partial_kernel(const float* __restrict__ corners, int64_t nf, const float* __restrict__ orig,
-                                                                const float* __restrict__ dir, int64_t m, int64_t per_slice, double* __restrict__ part_t,
-                                                                int32_t* __restrict__ part_face) {
-    const int64_t r0 = (int64_t)blockIdx.x * HIT_RBLOCK + threadIdx.x;
-    const int64_t f0 = (int64_t)blockIdx.y * per_slice;
-    const int64_t f1 = f0 + per_slice < nf ? f0 + per_slice : nf;
-    RayW ray[HIT_RPL];
-    double best[HIT_RPL];
-    int32_t bf[HIT_RPL];
-#pragma unroll
-    for (int j = 0; j < HIT_RPL; ++j) {
-        int64_t r = r0 + (int64_t)j * HIT_BLOCK;
-        r = r < m ? r : m - 1;
-        ray[j] = ray_setup(orig, dir, r);
-        best[j] = INFINITY;
-        bf[j] = -1;
-    }
-    for (int64_t f = f0; f < f1; ++f) {
-        const float* c = corners + 9 * f;
+// Pass 1 (pps_sweep.h): the smallest t of every ray over the faces of its slice, ties to the lowest face; face -1 for no hit.
+struct HitOp {
+    const float* __restrict__ orig;
+    const float* __restrict__ dir;
+    double* __restrict__ part_t;
+    int32_t* __restrict__ part_face;
+    struct Item {
+        RayW w;
+        double best;
+        int32_t bf;
+    };
+    __device__ __forceinline__ Item load(int64_t r) const { return {ray_setup(orig, dir, r), INFINITY, -1}; }
+    __device__ __forceinline__ void face(const float* __restrict__ c, int32_t f, Item (&it)[SWEEP_IPL]) const {
         const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5], c6 = c[6], c7 = c[7], c8 = c[8];
 #pragma unroll
-        for (int j = 0; j < HIT_RPL; ++j) {
-            const RayW& w = ray[j];
+        for (int j = 0; j < SWEEP_IPL; ++j) {
+            const RayW& w = it[j].w;
             const double akx = (double)pick(c0, c1, c2, w.kx) - w.o0, aky = (double)pick(c0, c1, c2, w.ky) - w.o1;
             const double akz = (double)pick(c0, c1, c2, w.kz) - w.o2;
             const double bkx = (double)pick(c3, c4, c5, w.kx) - w.o0, bky = (double)pick(c3, c4, c5, w.ky) - w.o1;
@@ -122,23 +105,19 @@ __global__ __launch_bounds__(HIT_BLOCK) void hit_partial_kernel(const float* __r
                 if (det != 0.0) {
                     const double tt = (u * (w.sz * akz) + v * (w.sz * bkz)) + ww * (w.sz * ckz);
                     const double t = tt / det;
-                    if (t > 0.0 && t < best[j]) {
-                        best[j] = t;
-                        bf[j] = (int32_t)f;
+                    if (t > 0.0 && t < it[j].best) {
+                        it[j].best = t;
+                        it[j].bf = f;
                     }
                 }
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < HIT_RPL; ++j) {
-        const int64_t r = r0 + (int64_t)j * HIT_BLOCK;
-        if (r < m) {
-            part_t[(int64_t)blockIdx.y * m + r] = best[j];
-            part_face[(int64_t)blockIdx.y * m + r] = bf[j];
-        }
+    __device__ __forceinline__ void store(const Item& it, int64_t k) const {
+        part_t[k] = it.best;
+        part_face[k] = it.bf;
     }
-}
+};
 
 // Pass 2: minimum over the slices in slice order (strict <: ties to the lower slice, i.e. the lower face).
 __global__ __launch_bounds__(256) void hit_final_kernel(int64_t m, int64_t slices, const double* __restrict__ part_t, const int32_t* __restrict__ part_face,
@@ -193,8 +172,8 @@ __global__ __launch_bounds__(256) void points_kernel(const float* __restrict__ o
     const int64_t pix = (int64_t)res * res;
     const int64_t s = i / pix, p = i - s * pix;
     const uint64_t ctr = (((uint64_t)s << 32) | (uint64_t)p) << 2;
-    const double u1 = (double)((mix64(key ^ ctr) >> 11) + 1) * 0x1.0p-53;
-    const double u2 = (double)(mix64(key ^ (ctr | 1)) >> 11) * 0x1.0p-53;
+    const double u1 = unit53_pos(rng_bits(key, ctr));
+    const double u2 = unit53(rng_bits(key, ctr | 1));
     const double g = sqrt(-2.0 * log(u1)) * cos(2.0 * 3.141592653589793 * u2);
     const double r = t[i] + (double)cams[CAM_FLOATS * s + 13] * g;
 #pragma unroll
@@ -209,11 +188,11 @@ __global__ __launch_bounds__(256) void queries_kernel(const float* __restrict__ 
     const uint64_t ctr = (uint64_t)i << 2;
     if (i < n_far) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) out[3 * i + k] = (float)(uint32_t)(mix64(key ^ (ctr | (uint64_t)k)) >> 40) * 0x1.0p-24f - 0.5f;
+        for (int k = 0; k < 3; ++k) out[3 * i + k] = unit24(rng_bits(key, ctr | (uint64_t)k)) - 0.5f;
         return;
     }
     const int64_t j = i - n_far;
-    const float u = (float)(uint32_t)(mix64(key ^ ctr) >> 40) * 0x1.0p-23f - 1.f;
+    const float u = unit24(rng_bits(key, ctr)) * 2.f - 1.f;  // the doubling is exact
     const double off = (double)u * (double)radius;
     const float* nr = normal + 3 * (int64_t)surf_face[j];
 #pragma unroll
@@ -224,30 +203,16 @@ __global__ __launch_bounds__(256) void queries_kernel(const float* __restrict__ 
 
 extern "C" {
 
-int64_t pps_scan_hit_slices(int64_t m, int64_t nf) {
-    if (m < 1 || nf < 1) return -1;
-    const int64_t rblocks = (m + HIT_RBLOCK - 1) / HIT_RBLOCK;
-    int64_t s = (HIT_TARGET_BLOCKS + rblocks - 1) / rblocks;
-    const int64_t smax = (nf + HIT_MIN_SLICE - 1) / HIT_MIN_SLICE;
-    s = s < smax ? s : smax;
-    s = s < 65535 ? s : 65535;
-    const int64_t per = (nf + s - 1) / s;                     // no empty slice
-    return (nf + per - 1) / per;
-}
+int64_t pps_scan_hit_slices(int64_t m, int64_t nf) { return sweep_slices(m, nf); }
 
 int pps_scan_first_hit(const float* corners, int64_t nf, const float* orig, const float* dir, int64_t m, int64_t slices, double* partial_t,
                        int32_t* partial_face, double* out_t, int32_t* out_face, void* stream) {
     if (nf < 1 || m < 0 || nf > INT32_MAX) return PPS_ERR_ARG;
     if (m == 0) return PPS_OK;
-    if (slices < 1 || slices > 65535 || slices > nf) return PPS_ERR_ARG;
     if (!corners || !orig || !dir || !partial_t || !partial_face || !out_t || !out_face) return PPS_ERR_ARG;
-    const int64_t rblocks = (m + HIT_RBLOCK - 1) / HIT_RBLOCK;
-    if (rblocks > INT32_MAX) return PPS_ERR_ARG;
-    const int64_t per = (nf + slices - 1) / slices;
-    const int64_t used = (nf + per - 1) / per;                // slices that hold a face; the rest of partial is not written
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(hit_partial_kernel, dim3((unsigned)rblocks, (unsigned)used), dim3(HIT_BLOCK), 0, st, corners, nf, orig, dir, m, per, partial_t,
-                       partial_face);
+    const int64_t used = sweep_launch(corners, nf, m, slices, HitOp{orig, dir, partial_t, partial_face}, st);
+    if (!used) return PPS_ERR_ARG;
     hipLaunchKernelGGL(hit_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, m, used, (const double*)partial_t,
                        (const int32_t*)partial_face, out_t, out_face);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
@@ -268,8 +233,8 @@ int pps_scan_points(const float* orig, const float* dir, const double* t, const 
     const int64_t m = (int64_t)n_scans * res * res;
     if (m == 0) return PPS_OK;
     if (!orig || !dir || !t || !face || !cams || !out_pts) return PPS_ERR_ARG;
-    const uint64_t key = mix64(mix64(seed) ^ stream_id);
-    hipLaunchKernelGGL(points_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, orig, dir, t, face, cams, m, res, key, out_pts);
+    hipLaunchKernelGGL(points_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, orig, dir, t, face, cams, m, res,
+                       rng_key(seed, stream_id), out_pts);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 
@@ -279,9 +244,8 @@ int pps_scan_queries(const float* surf_pts, const int32_t* surf_face, const floa
     const int64_t n = n_far + n_near;
     if (n == 0) return PPS_OK;
     if (!out || (n_near > 0 && (!surf_pts || !surf_face || !normal))) return PPS_ERR_ARG;
-    const uint64_t key = mix64(mix64(seed) ^ stream_id);
-    hipLaunchKernelGGL(queries_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, surf_pts, surf_face, normal, n_far, n, key,
-                       radius, out);
+    hipLaunchKernelGGL(queries_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, surf_pts, surf_face, normal, n_far, n,
+                       rng_key(seed, stream_id), radius, out);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 

@@ -7,7 +7,8 @@
 // query and face slice, the smallest squared distance, ties to the lowest face: in fp32 (the interior region measured as the plane
 // distance (ap.n)^2 / n.n), or in fp64 for a thin face (height below 0.1 x its longest edge), whose fp32 region tests are unreliable.
 // Pass 2 takes the minimum over the slices in slice order (ties to the lower face again) and recomputes distance and closest point of
-// the winning face in fp64.  The result depends on (corners, query) only, not on the slice count.
+// the winning face in fp64.  The result depends on (corners, query) only, not on the slice count.  Pass 1 is an operation of the sliced
+// face sweep of pps_sweep.h; corners is the face table of pps_eval_face_stats.
 //
 // Rasteriser -- replaces the pyrender / pyglet renders of source/base/visualization.py:25-63, 122-134.  Camera (host array of 16 floats):
 // M = cam[0..8] (world -> view rotation, row-major), eye = cam[9..11], f = cam[12] (focal length in pixels); cam[13..15] unused.  Per
@@ -28,15 +29,11 @@
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_sweep.h"
 #include "../../include/ppsurf_amd.h"
 
 namespace {
 
-constexpr int CP_BLOCK = 256;
-constexpr int CP_QPL = 4;                                     // queries per lane, held in registers
-constexpr int CP_QBLOCK = CP_BLOCK * CP_QPL;
-constexpr int64_t CP_TARGET_BLOCKS = 16384;
-constexpr int64_t CP_MIN_SLICE = 64;
 constexpr float NEAR = 0.01f;
 constexpr float SLIVER = 0.01f;                               // |e1 x e2|^2 < SLIVER lmax^4 (height < 0.1 x longest edge): pass 1 in fp64
 
@@ -98,63 +95,50 @@ __device__ __forceinline__ void closest_on_triangle(V3<T> p, V3<T> a, V3<T> b, V
     }
 }
 
-// Pass 1: workgroup (qb, s) scans the faces of slice s in face order for CP_QBLOCK queries (CP_QPL per lane in registers).  The face
-// index is wave-uniform: the nine corner floats are scalar loads shared by the wave.  Strict < keeps the lowest face of equal distance.
-__global__ __launch_bounds__(CP_BLOCK) void closest_partial_kernel(const float* __restrict__ corners, int64_t nf, const float* __restrict__ query,
-                                                                   int64_t m, int64_t per_slice, float* __restrict__ part_d2,
-                                                                   int32_t* __restrict__ part_face) {
-    const int64_t q0 = (int64_t)blockIdx.x * CP_QBLOCK + threadIdx.x;
-    const int64_t f0 = (int64_t)blockIdx.y * per_slice;
-    const int64_t f1 = f0 + per_slice < nf ? f0 + per_slice : nf;
-    V3<float> p[CP_QPL];
-    float best[CP_QPL];
-    int32_t bf[CP_QPL];
-#pragma unroll
-    for (int j = 0; j < CP_QPL; ++j) {
-        int64_t q = q0 + (int64_t)j * CP_BLOCK;
-        q = q < m ? q : m - 1;
-        p[j] = {query[3 * q], query[3 * q + 1], query[3 * q + 2]};
-        best[j] = INFINITY;
-        bf[j] = -1;
-    }
-    for (int64_t f = f0; f < f1; ++f) {
-        const float* c = corners + 9 * f;
+// Pass 1 (pps_sweep.h): the smallest squared distance of every query over the faces of its slice.  Strict < keeps the lowest face of equal
+// distance; face -1 means no finite distance in the slice.  The face is classified once for the lane's whole tile.  The running minimum
+// is two selects, not a branch: the branch costs three more VGPRs.
+struct ClosestOp {
+    const float* __restrict__ query;
+    float* __restrict__ part_d2;
+    int32_t* __restrict__ part_face;
+    struct Item {
+        V3<float> p;
+        float best;
+        int32_t bf;
+    };
+    __device__ __forceinline__ Item load(int64_t q) const { return {{query[3 * q], query[3 * q + 1], query[3 * q + 2]}, INFINITY, -1}; }
+    __device__ __forceinline__ void face(const float* __restrict__ c, int32_t f, Item (&it)[SWEEP_IPL]) const {
         const V3<float> a = {c[0], c[1], c[2]}, b = {c[3], c[4], c[5]}, cc = {c[6], c[7], c[8]};
         const V3<float> ab = sub(b, a), ac = sub(cc, a), bc = sub(cc, b), n = cross(ab, ac);
         const float lmax = fmaxf(dot(ab, ab), fmaxf(dot(ac, ac), dot(bc, bc)));
         if (dot(n, n) < SLIVER * (lmax * lmax)) {             // thin face (face-uniform branch): fp32 misclassifies the regions
             const V3<double> a64 = {a.x, a.y, a.z}, b64 = {b.x, b.y, b.z}, c64 = {cc.x, cc.y, cc.z};
 #pragma unroll
-            for (int j = 0; j < CP_QPL; ++j) {
+            for (int j = 0; j < SWEEP_IPL; ++j) {
                 double s, t, d2;
-                closest_on_triangle<double>(V3<double>{p[j].x, p[j].y, p[j].z}, a64, b64, c64, s, t, d2);
+                closest_on_triangle<double>(V3<double>{it[j].p.x, it[j].p.y, it[j].p.z}, a64, b64, c64, s, t, d2);
                 const float d2f = (float)d2;
-                if (d2f < best[j]) {
-                    best[j] = d2f;
-                    bf[j] = (int32_t)f;
-                }
+                const bool lt = d2f < it[j].best;
+                it[j].best = lt ? d2f : it[j].best;
+                it[j].bf = lt ? f : it[j].bf;
             }
-            continue;
+            return;
         }
 #pragma unroll
-        for (int j = 0; j < CP_QPL; ++j) {
+        for (int j = 0; j < SWEEP_IPL; ++j) {
             float s, t, d2;
-            closest_on_triangle<float>(p[j], a, b, cc, s, t, d2);
-            if (d2 < best[j]) {
-                best[j] = d2;
-                bf[j] = (int32_t)f;
-            }
+            closest_on_triangle<float>(it[j].p, a, b, cc, s, t, d2);
+            const bool lt = d2 < it[j].best;
+            it[j].best = lt ? d2 : it[j].best;
+            it[j].bf = lt ? f : it[j].bf;
         }
     }
-#pragma unroll
-    for (int j = 0; j < CP_QPL; ++j) {
-        const int64_t q = q0 + (int64_t)j * CP_BLOCK;
-        if (q < m) {
-            part_d2[(int64_t)blockIdx.y * m + q] = best[j];
-            part_face[(int64_t)blockIdx.y * m + q] = bf[j];
-        }
+    __device__ __forceinline__ void store(const Item& it, int64_t k) const {
+        part_d2[k] = it.best;
+        part_face[k] = it.bf;
     }
-}
+};
 
 // Pass 2: minimum over the slices in slice order (strict <: ties to the lower slice, i.e. the lower face), then distance and closest
 // point of the winning face in fp64.  A query whose every distance is NaN gets face 0.
@@ -426,30 +410,16 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" {
 
-int64_t pps_vis_closest_slices(int64_t m, int64_t nf) {
-    if (m < 1 || nf < 1) return -1;
-    const int64_t qblocks = (m + CP_QBLOCK - 1) / CP_QBLOCK;
-    int64_t s = (CP_TARGET_BLOCKS + qblocks - 1) / qblocks;
-    const int64_t smax = (nf + CP_MIN_SLICE - 1) / CP_MIN_SLICE;
-    s = s < smax ? s : smax;
-    s = s < 65535 ? s : 65535;
-    const int64_t per = (nf + s - 1) / s;                     // no empty slice
-    return (nf + per - 1) / per;
-}
+int64_t pps_vis_closest_slices(int64_t m, int64_t nf) { return sweep_slices(m, nf); }
 
 int pps_vis_closest_point(const float* corners, int64_t nf, const float* query, int64_t m, int64_t slices, float* partial_d2, int32_t* partial_face,
                           float* out_d, int32_t* out_face, float* out_pt, void* stream) {
     if (nf < 1 || m < 0 || nf > INT32_MAX) return PPS_ERR_ARG;
     if (m == 0) return PPS_OK;
-    if (slices < 1 || slices > 65535 || slices > nf) return PPS_ERR_ARG;
     if (!corners || !query || !partial_d2 || !partial_face || !out_d || !out_face || !out_pt) return PPS_ERR_ARG;
-    const int64_t qblocks = (m + CP_QBLOCK - 1) / CP_QBLOCK;
-    if (qblocks > INT32_MAX) return PPS_ERR_ARG;
-    const int64_t per = (nf + slices - 1) / slices;
-    const int64_t used = (nf + per - 1) / per;                // slices that hold a face; the rest of partial is not written
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(closest_partial_kernel, dim3((unsigned)qblocks, (unsigned)used), dim3(CP_BLOCK), 0, st, corners, nf, query, m, per, partial_d2,
-                       partial_face);
+    const int64_t used = sweep_launch(corners, nf, m, slices, ClosestOp{query, partial_d2, partial_face}, st);
+    if (!used) return PPS_ERR_ARG;
     hipLaunchKernelGGL(closest_final_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, corners, query, m, used, (const float*)partial_d2,
                        (const int32_t*)partial_face, out_d, out_face, out_pt);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;

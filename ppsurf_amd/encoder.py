@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .geometry import _stream
 
 BN_EPS = 1e-5
 ACT_CODE = {'relu': 1.0, 'silu': 2.0}
@@ -22,10 +23,6 @@ def _np64(t):
 def _bn_scale_shift(sd, bn):
     scale = _np64(sd[bn + '.weight']) / np.sqrt(_np64(sd[bn + '.running_var']) + BN_EPS)
     return scale, _np64(sd[bn + '.bias']) - _np64(sd[bn + '.running_mean']) * scale
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 class FKAConvParams:

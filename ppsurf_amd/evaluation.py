@@ -4,7 +4,8 @@
         --num_samples 100000
 
 Replaces source/base/evaluation.py:32-59 (`make_quantitative_comparison`) and source/base/metrics.py:120-323, which need trimesh,
-pysdf, pykdtree and openpyxl.  Per mesh pair, one upload and one set of samples serve all four metrics (csrc/pps_eval.hip):
+pysdf, pykdtree and openpyxl.  Per mesh pair, one upload and one set of samples serve all four metrics (the mesh queries are
+geometry.py's, the reduction is csrc/pps_eval.hip):
   * face statistics (areas, unit normals, face-major corners) of both meshes;
   * `num_samples` area-weighted surface samples of each mesh (counter-based generator, stream 0 = reconstruction, 1 = ground truth);
   * the two 1-NN searches between the sample sets (ops.KnnBlocks, k = 1): Chamfer = (sum d(gt->rec) + sum d(rec->gt)) / (N_rec + N_gt)
@@ -30,20 +31,11 @@ import numpy as np
 import torch
 
 from . import _lib, meshio, ops
+from .geometry import _device, _need_device, _ptr, _stream, area_prefix, face_stats, sample_surface, winding_number
 from .lightning_api import calc_f1, calc_precision, calc_recall
 
 METRIC_FILES = {'chamfer': 'chamfer_distance', 'f1': 'f1', 'iou': 'iou', 'normals': 'normal_error'}
 _KEYS = {'chamfer': 'chamfer', 'f1': 'f1', 'iou': 'iou', 'normals': 'normal_error'}
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _need_device(*tensors):
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.PpsError('ppsurf_amd.evaluation needs device tensors; there is no CPU fallback')
 
 
 def iou_query_points(num_samples: int, num_dims: int = 3) -> np.ndarray:
@@ -52,62 +44,16 @@ def iou_query_points(num_samples: int, num_dims: int = 3) -> np.ndarray:
     return rng.random(size=(num_samples, num_dims)) - 0.5
 
 
-def face_stats(verts: torch.Tensor, faces: torch.Tensor):
-    """verts f32 [nv,3], faces int32 [nf,3] on the device -> (area f32 [nf], unit normal f32 [nf,3], corners f32 [nf,9])."""
-    _need_device(verts, faces)
-    assert verts.dtype == torch.float32 and faces.dtype == torch.int32 and verts.is_contiguous() and faces.is_contiguous()
-    nf = faces.shape[0]
-    area = torch.empty(nf, dtype=torch.float32, device=verts.device)
-    normal = torch.empty((nf, 3), dtype=torch.float32, device=verts.device)
-    corners = torch.empty((nf, 9), dtype=torch.float32, device=verts.device)
-    _lib.check(_lib.lib().pps_eval_face_stats(verts.data_ptr(), verts.shape[0], faces.data_ptr(), nf, area.data_ptr(), normal.data_ptr(),
-                                              corners.data_ptr(), _stream(verts)), 'pps_eval_face_stats')
-    return area, normal, corners
-
-
-def area_prefix(area: torch.Tensor) -> torch.Tensor:
-    """fp64 inclusive prefix of the face areas (the sampler's face table)."""
-    return torch.cumsum(area.to(torch.float64), 0)
-
-
-def sample_surface(corners: torch.Tensor, prefix: torch.Tensor, n: int, seed: int = 0, stream_id: int = 0):
-    """n area-weighted surface samples -> (points f32 [n,3], face ids int32 [n]).  prefix = area_prefix(area), its last entry > 0."""
-    _need_device(corners, prefix)
-    assert corners.dtype == torch.float32 and prefix.dtype == torch.float64 and corners.is_contiguous() and prefix.is_contiguous()
-    pts = torch.empty((n, 3), dtype=torch.float32, device=corners.device)
-    face = torch.empty(n, dtype=torch.int32, device=corners.device)
-    _lib.check(_lib.lib().pps_eval_sample_surface(corners.data_ptr(), prefix.data_ptr(), corners.shape[0], int(n), int(seed) & (2 ** 64 - 1),
-                                                  int(stream_id) & (2 ** 64 - 1), pts.data_ptr(), face.data_ptr(), _stream(corners)),
-               'pps_eval_sample_surface')
-    return pts, face
-
-
-def winding_number(corners: torch.Tensor, query: torch.Tensor) -> torch.Tensor:
-    """Generalised winding number f64 [m] of query f32 [m,3] with respect to the mesh of corners [nf,9] (0 for a mesh without faces)."""
-    _need_device(corners, query)
-    query = query.contiguous().float()
-    m, nf = query.shape[0], corners.shape[0]
-    w = torch.zeros(m, dtype=torch.float64, device=query.device)
-    if m == 0 or nf == 0:
-        return w
-    L = _lib.lib()
-    slices = L.pps_eval_winding_slices(m, nf)
-    partial = torch.empty((slices, m), dtype=torch.float32, device=query.device)
-    _lib.check(L.pps_eval_winding(corners.data_ptr(), nf, query.data_ptr(), m, slices, partial.data_ptr(), w.data_ptr(), _stream(query)),
-               'pps_eval_winding')
-    return w
-
-
 def reduce_sums(d2_rg, d2_gr, nn_rg, face_rec, face_gt, normal_rec, normal_gt, w_rec, w_gt) -> torch.Tensor:
     """f64 [8] on the device: sum sqrt(d2_rg), sum sqrt(d2_gr), TP, FP, FN, TN, sum arccos(...), number of non-NaN cosines.
     d2_rg / d2_gr (and the normal group) may be None."""
     dev = w_rec.device
     out = torch.empty(8, dtype=torch.float64, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None
     n_rec = d2_rg.shape[0] if d2_rg is not None else 0
     n_gt = d2_gr.shape[0] if d2_gr is not None else 0
-    _lib.check(_lib.lib().pps_eval_reduce(ptr(d2_rg), n_rec, ptr(d2_gr), n_gt, ptr(nn_rg), ptr(face_rec), ptr(face_gt), ptr(normal_rec), ptr(normal_gt),
-                                          w_rec.data_ptr(), w_gt.data_ptr(), w_rec.shape[0], out.data_ptr(), _stream(w_rec)), 'pps_eval_reduce')
+    _lib.check(_lib.lib().pps_eval_reduce(_ptr(d2_rg), n_rec, _ptr(d2_gr), n_gt, _ptr(nn_rg), _ptr(face_rec), _ptr(face_gt), _ptr(normal_rec),
+                                          _ptr(normal_gt), w_rec.data_ptr(), w_gt.data_ptr(), w_rec.shape[0], out.data_ptr(), _stream(w_rec)),
+               'pps_eval_reduce')
     return out
 
 
@@ -166,12 +112,6 @@ def load_mesh(path: str):
     if os.path.splitext(path)[1].lower() != '.ply':
         raise ValueError('only PLY meshes are supported: {}'.format(path))
     return meshio.read_ply_mesh(path)
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('ppsurf_amd.evaluation needs a GPU; there is no CPU fallback')
-    return torch.device('cuda', torch.cuda.current_device())
 
 
 def file_metrics(file_in: str, file_ref: str, num_samples: int) -> dict:

@@ -16,8 +16,8 @@ its own (csrc/pps_scan.hip):
     [scanner_noise_sigma_min, scanner_noise_sigma_max] x the longest bounding-box edge); misses are dropped;
   * the first floor(n / 2) queries are uniform in [-0.5, 0.5)^3, the others area-weighted surface samples moved along their face normal
     by u r, u uniform in [-1, 1), r = query_near_radius (3 / 128, the band of the reference's near-surface queries);
-  * labels: exact distance to the mesh (visualization.closest_point_on_corners) with the sign of the generalised winding number
-    (evaluation.winding_number, |w| > 0.5 inside -> positive), the convention of the reference's 05_query_dist.
+  * labels: exact distance to the mesh (geometry.closest_point_on_corners) with the sign of the generalised winding number
+    (geometry.winding_number, |w| > 0.5 inside -> positive), the convention of the reference's 05_query_dist.
 Meshes (PLY or OBJ) are normalised like a single-file input cloud (bounding-box centre to 0, longest edge x 1.05 to 1) unless
 --no_normalize, which copies them unchanged (meshes already in a dataset's frame).  A shape whose outputs are newer than its mesh is skipped.
 """
@@ -32,23 +32,15 @@ import zlib
 import numpy as np
 import torch
 
-from . import _lib, evaluation, meshio, visualization
+from . import _lib, meshio
+from .geometry import (_device, _need_device, _ptr, _stream, area_prefix, closest_point_on_corners, face_stats, first_hit, sample_surface,
+                       winding_number)
 
 DEFAULTS = {'num_scans_per_mesh_min': 5, 'num_scans_per_mesh_max': 30, 'scanner_noise_sigma_min': 0.0, 'scanner_noise_sigma_max': 0.05,
             'scan_resolution': 64, 'num_query_pts': 2000, 'query_near_radius': 3.0 / 128.0, 'seed': 42, 'test_fraction': 0.3, 'normalize': 1}
 PADDING = 0.05
 CAM_FLOATS = 16
 MESH_EXTS = ('.ply', '.obj')
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _need_device(*tensors):
-    for t in tensors:
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise _lib.PpsError('ppsurf_amd.make_dataset needs device tensors; there is no CPU path')
 
 
 # ---- settings, seeds, split ---------------------------------------------------------------------------------------------------------------------
@@ -140,27 +132,6 @@ def scan_cameras(bb_min, bb_max, settings: dict, rng: np.random.Generator) -> np
     return cams.astype(np.float32)
 
 
-def first_hit(corners: torch.Tensor, orig: torch.Tensor, dirs: torch.Tensor, slices: typing.Optional[int] = None):
-    """First hit of the rays (orig, dirs f32 [m,3]) on the triangle soup corners f32 [nf,9], device tensors -> (t f64 [m], face int32 [m]),
-    -1 for a miss.  `slices` forces the number of face slices (any value gives the same result; default pps_scan_hit_slices)."""
-    _need_device(corners, orig, dirs)
-    orig, dirs = orig.to(torch.float32).contiguous(), dirs.to(torch.float32).contiguous()
-    corners = corners.to(torch.float32).contiguous()
-    m, nf = orig.shape[0], corners.shape[0]
-    dev = orig.device
-    t = torch.full((m,), -1.0, dtype=torch.float64, device=dev)
-    face = torch.full((m,), -1, dtype=torch.int32, device=dev)
-    if m == 0 or nf == 0:
-        return t, face
-    L = _lib.lib()
-    s = L.pps_scan_hit_slices(m, nf) if slices is None else int(slices)
-    part_t = torch.empty((s, m), dtype=torch.float64, device=dev)
-    part_face = torch.empty((s, m), dtype=torch.int32, device=dev)
-    _lib.check(L.pps_scan_first_hit(corners.data_ptr(), nf, orig.data_ptr(), dirs.data_ptr(), m, s, part_t.data_ptr(), part_face.data_ptr(),
-                                    t.data_ptr(), face.data_ptr(), _stream(orig)), 'pps_scan_first_hit')
-    return t, face
-
-
 def scan_rays(cams: torch.Tensor, res: int):
     """One ray per pixel of every camera (device f32 [n_scans,16]) -> (orig, dirs f32 [n_scans res^2, 3])."""
     _need_device(cams)
@@ -191,7 +162,7 @@ def _mesh_tables(verts: torch.Tensor, faces: torch.Tensor):
     _need_device(verts, faces)
     v = verts.to(torch.float32).contiguous()
     f = faces.to(torch.int32).contiguous()
-    return evaluation.face_stats(v, f)
+    return face_stats(v, f)
 
 
 def scan_mesh(verts: torch.Tensor, faces: torch.Tensor, name: str, settings: typing.Optional[dict] = None, seed: int = DEFAULTS['seed']) -> torch.Tensor:
@@ -215,12 +186,11 @@ def query_points(verts: torch.Tensor, faces: torch.Tensor, name: str, n: int = D
     out = torch.empty((n_far + n_near, 3), dtype=torch.float32, device=verts.device)
     pts = face = None
     if n_near > 0:
-        prefix = evaluation.area_prefix(area)
+        prefix = area_prefix(area)
         if corners.shape[0] == 0 or not float(prefix[-1]) > 0.0:
             raise ValueError('the mesh has no samplable area')
-        pts, face = evaluation.sample_surface(corners, prefix, n_near, seed, (shape_stream(name) << 2) | 2)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    _lib.check(_lib.lib().pps_scan_queries(ptr(pts), ptr(face), normal.data_ptr(), n_far, n_near, int(seed) & (2 ** 64 - 1),
+        pts, face = sample_surface(corners, prefix, n_near, seed, (shape_stream(name) << 2) | 2)
+    _lib.check(_lib.lib().pps_scan_queries(_ptr(pts), _ptr(face), normal.data_ptr(), n_far, n_near, int(seed) & (2 ** 64 - 1),
                                            (shape_stream(name) << 2) | 1, float(radius), out.data_ptr(), _stream(out)), 'pps_scan_queries')
     return out
 
@@ -230,8 +200,8 @@ def signed_distance(verts: torch.Tensor, faces: torch.Tensor, query: torch.Tenso
     _need_device(verts, faces, query)
     _, _, corners = _mesh_tables(verts, faces)
     query = query.to(torch.float32).contiguous()
-    _, d, _ = visualization.closest_point_on_corners(corners, query)
-    w = evaluation.winding_number(corners, query)
+    _, d, _ = closest_point_on_corners(corners, query)
+    w = winding_number(corners, query)
     return torch.where(w.abs() > 0.5, d, -d)
 
 
@@ -263,12 +233,12 @@ def output_files(out_dir: str, name: str):
 def make_shape(mesh_file: str, out_dir: str, name: str, settings: dict, device) -> int:
     """All files of one shape; returns its point count."""
     f_mesh, f_pts, f_q, f_d = output_files(out_dir, name)
-    verts, faces, _ = visualization.load_mesh_any(mesh_file)
+    verts, faces, _ = meshio.load_mesh_any(mesh_file)
     if settings['normalize']:
         verts = normalize_mesh(verts)
     v = torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float32)).to(device)
     f = torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int32)).to(device)
-    area = evaluation.face_stats(v, f)[0] if faces.shape[0] else torch.zeros(0, device=device)
+    area = face_stats(v, f)[0] if faces.shape[0] else torch.zeros(0, device=device)
     if not float(area.double().sum()) > 0.0:
         raise ValueError('{}: the mesh has no samplable area'.format(mesh_file))
     seed = settings['seed']
@@ -294,12 +264,10 @@ def make_dataset(meshes_dir: str, out_dir: str, settings: typing.Optional[dict] 
     meshes = mesh_files(meshes_dir)
     if not meshes:
         raise ValueError('no PLY or OBJ meshes in {}'.format(meshes_dir))
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('ppsurf_amd.make_dataset needs a GPU; there is no CPU path')
-    device = torch.device('cuda', torch.cuda.current_device())
+    device = _device()
     built = []
     for name, path in meshes.items():
-        if not visualization.call_necessary(path, output_files(out_dir, name)):
+        if not meshio.call_necessary(path, output_files(out_dir, name)):
             continue
         n = make_shape(path, out_dir, name, s, device)
         built.append(name)

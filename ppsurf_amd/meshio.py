@@ -415,3 +415,31 @@ def read_obj_mesh(path):
     if faces.size and (faces.min() < 0 or faces.max() >= v.shape[0]):
         raise ValueError('OBJ face index out of range: {}'.format(path))
     return v, faces.astype(np.int32)
+
+
+def load_mesh_any(path: str):
+    """(verts f32 [nv,3], faces int32 [nf,3], colours uint8 [nv,3] or None) of a PLY, OBJ or .npy (points) file."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == '.npy':
+        pts = np.load(path)
+        return np.asarray(pts, dtype=np.float32)[:, :3], np.zeros((0, 3), dtype=np.int32), None
+    if ext == '.obj':
+        v, f = read_obj_mesh(path)
+        return v, f, None
+    if ext == '.ply':
+        v, f = read_ply_mesh(path)
+        return v, f, read_ply_vertex_colors(path)
+    raise ValueError('unsupported mesh file: {}'.format(path))
+
+
+def call_necessary(file_in, file_out) -> bool:
+    """source/base/fs.py `call_necessary`: False when an input is missing; True when an output is missing or not newer than every input."""
+    file_in = [file_in] if isinstance(file_in, str) else list(file_in)
+    file_out = [file_out] if isinstance(file_out, str) else list(file_out)
+    if not file_out:
+        return True
+    if any(not os.path.isfile(f) for f in file_in):
+        return False
+    if any(not os.path.isfile(f) for f in file_out):
+        return True
+    return max(os.path.getmtime(f) for f in file_in) >= min(os.path.getmtime(f) for f in file_out)

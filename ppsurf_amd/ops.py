@@ -2,10 +2,7 @@
 import torch
 
 from . import _lib
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+from .geometry import _stream
 
 
 def knn_point_major(pts: torch.Tensor, query: torch.Tensor, k: int, return_d2: bool = False, out: torch.Tensor = None):

@@ -1,10 +1,9 @@
 """Distance-coloured meshes and renders on the GPU: the qualitative half of the comparison (source/base/visualization.py, proximity.py).
 
 Replaces trimesh (subdivision, closest point, PLY export) and pyrender / pyglet (renders), which are not available and need an OpenGL
-context.  The kernels are in csrc/pps_vis.hip:
-  * `closest_point_on_mesh`: exact point-to-triangle closest point by brute force over face slices (ties to the lowest face id; the
-    result depends on the mesh and the queries only);
-  * `render_scene`: a deterministic z-buffer rasteriser (64-bit atomicMin of depth bits and id per pixel) and a shading pass.
+context.  The distances are geometry.closest_point_on_mesh (exact point-to-triangle closest point, ties to the lowest face id);
+`render_scene` is a deterministic z-buffer rasteriser (64-bit atomicMin of depth bits and id per pixel) and a shading pass, both in
+csrc/pps_vis.hip.
 
 Camera of `render_scene` (the reference's `scene.set_camera(angles=(pi/4, pi/4, 0), distance=2.2, fov=(45, 45))`; trimesh is not
 installed, so this definition is the specification):
@@ -30,7 +29,8 @@ import numpy as np
 import torch
 
 from . import _lib, meshio
-from .evaluation import _need_device, _stream, face_stats
+from .geometry import _device, _need_device, _ptr, _stream, closest_point_on_mesh
+from .meshio import call_necessary, load_mesh_any
 
 NEAR = 0.01
 RENDER_SIZE = 1024
@@ -77,47 +77,6 @@ def distances_to_vertex_colors(dist_per_vertex, cut_off=0.3) -> np.ndarray:
 
 
 # ---- closest point ------------------------------------------------------------------------------------------------------------------------------
-def closest_point_on_mesh(verts: torch.Tensor, faces: torch.Tensor, query: torch.Tensor, slices: typing.Optional[int] = None):
-    """Exact closest point on the mesh (verts f32 [nv,3], faces int [nf,3]) of query [m,3], all device tensors ->
-    (closest points f32 [m,3], distances f32 [m], face ids int32 [m]).  `slices` forces the number of face slices (any value gives the
-    same result; default pps_vis_closest_slices)."""
-    _need_device(verts, faces, query)
-    verts = verts.to(torch.float32).contiguous()
-    faces = faces.to(torch.int32).contiguous()
-    query = query.to(torch.float32).contiguous()
-    m, nf = query.shape[0], faces.shape[0]
-    if nf == 0:
-        raise ValueError('closest_point_on_mesh: the mesh has no faces')
-    _, _, corners = face_stats(verts, faces)
-    return closest_point_on_corners(corners, query, slices)
-
-
-def closest_point_on_corners(corners: torch.Tensor, query: torch.Tensor, slices: typing.Optional[int] = None):
-    """closest_point_on_mesh for face-major corners f32 [nf,9] (evaluation.face_stats)."""
-    _need_device(corners, query)
-    query = query.to(torch.float32).contiguous()
-    m, nf = query.shape[0], corners.shape[0]
-    dev = query.device
-    pt = torch.empty((m, 3), dtype=torch.float32, device=dev)
-    d = torch.empty(m, dtype=torch.float32, device=dev)
-    face = torch.empty(m, dtype=torch.int32, device=dev)
-    if m == 0:
-        return pt, d, face
-    L = _lib.lib()
-    s = L.pps_vis_closest_slices(m, nf) if slices is None else int(slices)
-    part_d2 = torch.empty((s, m), dtype=torch.float32, device=dev)
-    part_face = torch.empty((s, m), dtype=torch.int32, device=dev)
-    _lib.check(L.pps_vis_closest_point(corners.data_ptr(), nf, query.data_ptr(), m, s, part_d2.data_ptr(), part_face.data_ptr(), d.data_ptr(),
-                                       face.data_ptr(), pt.data_ptr(), _stream(query)), 'pps_vis_closest_point')
-    return pt, d, face
-
-
-def _device():
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('ppsurf_amd.visualization needs a GPU; there is no CPU fallback')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 def get_closest_point_on_mesh(mesh, query_pts, batch_size=1000):
     """proximity.py:20 with numpy in and out: mesh = (verts [nv,3], faces [nf,3]) -> (closest points f32 [m,3], distances f32 [m],
     face ids int32 [m]).  batch_size is accepted and ignored (one launch)."""
@@ -148,35 +107,7 @@ def subdivide(verts: torch.Tensor, faces: torch.Tensor):
     return torch.cat([verts, mid.to(verts.dtype)], dim=0), new_f.to(faces.dtype)
 
 
-# ---- meshes on disk -----------------------------------------------------------------------------------------------------------------------------
-def load_mesh_any(path: str):
-    """(verts f32 [nv,3], faces int32 [nf,3], colours uint8 [nv,3] or None) of a PLY, OBJ or .npy (points) file."""
-    ext = os.path.splitext(path)[1].lower()
-    if ext == '.npy':
-        pts = np.load(path)
-        return np.asarray(pts, dtype=np.float32)[:, :3], np.zeros((0, 3), dtype=np.int32), None
-    if ext == '.obj':
-        v, f = meshio.read_obj_mesh(path)
-        return v, f, None
-    if ext == '.ply':
-        v, f = meshio.read_ply_mesh(path)
-        return v, f, meshio.read_ply_vertex_colors(path)
-    raise ValueError('unsupported mesh file: {}'.format(path))
-
-
-def call_necessary(file_in, file_out) -> bool:
-    """source/base/fs.py `call_necessary`: False when an input is missing; True when an output is missing or not newer than every input."""
-    file_in = [file_in] if isinstance(file_in, str) else list(file_in)
-    file_out = [file_out] if isinstance(file_out, str) else list(file_out)
-    if not file_out:
-        return True
-    if any(not os.path.isfile(f) for f in file_in):
-        return False
-    if any(not os.path.isfile(f) for f in file_out):
-        return True
-    return max(os.path.getmtime(f) for f in file_in) >= min(os.path.getmtime(f) for f in file_out)
-
-
+# ---- distance-coloured meshes -----------------------------------------------------------------------------------------------------------------
 def visualize_chamfer_distance(input_mesh_file: str, reference_mesh_file: str, output_mesh_file: str, min_vertex_count: typing.Optional[int],
                                dist_cut_off=0.3, distance_batch_size=1000):
     """visualization.py:81-99: subdivide the input mesh until it has min_vertex_count vertices, colour every vertex by its exact distance
@@ -278,8 +209,7 @@ def shade(keys: torch.Tensor, verts: torch.Tensor, faces: typing.Optional[torch.
         colors = colors.to(torch.uint8).contiguous()
     packed = (int(rgb[0]) << 16) | (int(rgb[1]) << 8) | int(rgb[2])
     cam = np.ascontiguousarray(cam, dtype=np.float32)
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    _lib.check(_lib.lib().pps_vis_shade(keys.data_ptr(), w, h, verts.data_ptr(), ptr(faces), ptr(colors), packed, cam.ctypes.data, out.data_ptr(),
+    _lib.check(_lib.lib().pps_vis_shade(keys.data_ptr(), w, h, verts.data_ptr(), _ptr(faces), _ptr(colors), packed, cam.ctypes.data, out.data_ptr(),
                                         _stream(keys)), 'pps_vis_shade')
     return out
 

@@ -14,8 +14,8 @@ def mix64(x):
 
 
 def sample_spec(corners, prefix, n, seed, stream_id):
-    """The generator of the header comment of pps_eval.hip: (points f32 [n,3], face ids int64 [n]) from corners f32 [nf,9] and the
-    fp64 inclusive area prefix."""
+    """The sampler of the header comment of pps_eval.hip (generator: pps_rng.h): (points f32 [n,3], face ids int64 [n]) from corners
+    f32 [nf,9] and the fp64 inclusive area prefix."""
     corners = np.asarray(corners, dtype=np.float32)
     prefix = np.asarray(prefix, dtype=np.float64)
     key = mix64(mix64(np.uint64(seed)) ^ np.uint64(stream_id))

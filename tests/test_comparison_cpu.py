@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from ppsurf_amd import _lib, comparison, meshio, visualization
+from ppsurf_amd import _lib, comparison, geometry, meshio, visualization
 from ppsurf_amd.evaluation import write_metric_table
 from tests import eval_spec, vis_spec
 
@@ -217,15 +217,15 @@ def test_camera_matches_hand_computation():
 
 def test_call_necessary(tmp_path):
     a, b = tmp_path / 'a', tmp_path / 'b'
-    assert not visualization.call_necessary(str(a), str(b))                 # input missing
+    assert not meshio.call_necessary(str(a), str(b))                 # input missing
     a.write_text('x')
-    assert visualization.call_necessary(str(a), str(b))                     # output missing
+    assert meshio.call_necessary(str(a), str(b))                     # output missing
     b.write_text('y')
     os.utime(a, (1000, 1000))
     os.utime(b, (2000, 2000))
-    assert not visualization.call_necessary(str(a), str(b))
+    assert not meshio.call_necessary(str(a), str(b))
     os.utime(a, (3000, 3000))
-    assert visualization.call_necessary([str(a)], [str(b)])
+    assert meshio.call_necessary([str(a)], [str(b)])
 
 
 def test_vis_abi_declared():
@@ -247,4 +247,4 @@ def test_vis_abi_declared():
 def test_device_functions_refuse_cpu_tensors():
     v, f = eval_spec.icosphere(0)
     with pytest.raises(_lib.PpsError):
-        visualization.closest_point_on_mesh(torch.from_numpy(v).float(), torch.from_numpy(f).int(), torch.zeros(4, 3))
+        geometry.closest_point_on_mesh(torch.from_numpy(v).float(), torch.from_numpy(f).int(), torch.zeros(4, 3))

@@ -31,10 +31,10 @@ def _fixture(name_index=1):
 
 
 def test_face_stats_against_numpy():
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import geometry
     verts, faces = _fixture(0)
     faces = np.concatenate([faces, np.array([[0, 0, 1], [5, 5, 5]], np.int32)])             # two degenerate faces at the end
-    area, normal, corners = evaluation.face_stats(*_dev(verts, faces))
+    area, normal, corners = geometry.face_stats(*_dev(verts, faces))
     a_np, n_np, c_np = E.face_stats_spec(verts, faces)
     assert np.array_equal(corners.cpu().numpy(), c_np.astype(np.float32))
     np.testing.assert_allclose(area.cpu().numpy(), a_np, rtol=1e-5, atol=1e-6 * a_np.max())   # fp32 cancellation on slivers
@@ -48,43 +48,43 @@ def test_face_stats_against_numpy():
 
 
 def test_sampling_matches_the_generator_and_is_a_prefix():
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import geometry
     verts, faces = _fixture(0)
-    area, _, corners = evaluation.face_stats(*_dev(verts, faces))
-    prefix = evaluation.area_prefix(area)
-    pts, face = evaluation.sample_surface(corners, prefix, 50000, seed=7, stream_id=3)
+    area, _, corners = geometry.face_stats(*_dev(verts, faces))
+    prefix = geometry.area_prefix(area)
+    pts, face = geometry.sample_surface(corners, prefix, 50000, seed=7, stream_id=3)
     p_np, f_np = E.sample_spec(corners.cpu().numpy(), prefix.cpu().numpy(), 50000, 7, 3)
     assert np.array_equal(face.cpu().numpy().astype(np.int64), f_np)
     np.testing.assert_allclose(pts.cpu().numpy(), p_np, rtol=0, atol=1e-6)
-    pk, fk = evaluation.sample_surface(corners, prefix, 1234, seed=7, stream_id=3)
+    pk, fk = geometry.sample_surface(corners, prefix, 1234, seed=7, stream_id=3)
     assert torch.equal(pk, pts[:1234]) and torch.equal(fk, face[:1234])
-    p2, _ = evaluation.sample_surface(corners, prefix, 1234, seed=7, stream_id=4)
+    p2, _ = geometry.sample_surface(corners, prefix, 1234, seed=7, stream_id=4)
     assert not torch.equal(p2, pk)                                                             # streams are independent draws
 
 
 def test_sampling_never_draws_zero_area_faces():
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import geometry
     v, f = E.icosphere(2, 0.3)
     nf = f.shape[0]
     degenerate = np.array([[0, 0, 1], [2, 3, 2], [4, 4, 4]])
     faces = np.concatenate([degenerate, f[:nf // 2], degenerate, f[nf // 2:], degenerate])      # first, inside and last
-    area, _, corners = evaluation.face_stats(*_dev(v, faces))
+    area, _, corners = geometry.face_stats(*_dev(v, faces))
     zero = (area == 0).cpu().numpy()
     assert zero.sum() == 9
-    _, face = evaluation.sample_surface(corners, evaluation.area_prefix(area), 200000, seed=1)
+    _, face = geometry.sample_surface(corners, geometry.area_prefix(area), 200000, seed=1)
     assert not zero[face.cpu().numpy()].any()
 
 
 def test_sampling_face_counts_follow_the_areas():
     """Chi-square of the face counts of 200k samples over 20 faces of very different areas (df = 19, p = 0.001: 43.82)."""
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import geometry
     rng = np.random.default_rng(5)
     scale = np.repeat(np.geomspace(0.05, 1.0, 20), 3)[:, None]
     verts = (rng.standard_normal((60, 3)) * scale).astype(np.float32)
     faces = np.arange(60, dtype=np.int32).reshape(20, 3)
-    area, _, corners = evaluation.face_stats(*_dev(verts, faces))
+    area, _, corners = geometry.face_stats(*_dev(verts, faces))
     n = 200000
-    _, face = evaluation.sample_surface(corners, evaluation.area_prefix(area), n, seed=11)
+    _, face = geometry.sample_surface(corners, geometry.area_prefix(area), n, seed=11)
     counts = np.bincount(face.cpu().numpy(), minlength=20)
     a = area.double().cpu().numpy()
     expected = n * a / a.sum()
@@ -93,9 +93,9 @@ def test_sampling_face_counts_follow_the_areas():
 
 
 def _winding_case(verts, faces, pts):
-    from ppsurf_amd import evaluation
-    _, _, corners = evaluation.face_stats(*_dev(verts, faces))
-    w = evaluation.winding_number(corners, torch.from_numpy(pts.astype(np.float32)).to(DEV)).cpu().numpy()
+    from ppsurf_amd import geometry
+    _, _, corners = geometry.face_stats(*_dev(verts, faces))
+    w = geometry.winding_number(corners, torch.from_numpy(pts.astype(np.float32)).to(DEV)).cpu().numpy()
     w_np = E.winding_spec(verts.astype(np.float32), faces, pts.astype(np.float32))
     band = (np.abs(w_np) > 0.499) & (np.abs(w_np) < 0.501)
     assert np.array_equal((np.abs(w) > 0.5)[~band], (np.abs(w_np) > 0.5)[~band])
@@ -115,11 +115,11 @@ def test_winding_number_against_numpy():
     w, w_np = _winding_case(verts, faces, rng.random((5000, 3)) - 0.5)
     assert 0.01 < (np.abs(w) > 0.5).mean() < 0.5                          # the part fills ~3 % of the query cube
     # a face-flipped mesh: w -> -w
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import geometry
     q = torch.from_numpy((rng.random((5000, 3)) - 0.5).astype(np.float32)).to(DEV)
-    _, _, c = evaluation.face_stats(*_dev(verts, faces))
-    _, _, c_flip = evaluation.face_stats(*_dev(verts, faces[:, ::-1].copy()))
-    w1, w2 = evaluation.winding_number(c, q), evaluation.winding_number(c_flip, q)
+    _, _, c = geometry.face_stats(*_dev(verts, faces))
+    _, _, c_flip = geometry.face_stats(*_dev(verts, faces[:, ::-1].copy()))
+    w1, w2 = geometry.winding_number(c, q), geometry.winding_number(c_flip, q)
     w1, w2 = w1.cpu().numpy(), w2.cpu().numpy()
     # not bitwise: the rounding order of det and D changes with b <-> c, and a query next to a face plane sees that face's fp32 error
     assert np.median(np.abs(w2 + w1)) < 1e-6 and (np.abs(w2 + w1) < 1e-5).mean() > 0.99
@@ -128,13 +128,13 @@ def test_winding_number_against_numpy():
 
 
 def test_chamfer_nn_step_against_brute_force():
-    from ppsurf_amd import evaluation
+    from ppsurf_amd import evaluation, geometry
     verts, faces = _fixture(0)
     vg, fg = _fixture(2)
-    a1, _, c1 = evaluation.face_stats(*_dev(verts, faces))
-    a2, _, c2 = evaluation.face_stats(*_dev(vg, fg))
-    s1, _ = evaluation.sample_surface(c1, evaluation.area_prefix(a1), 10000, seed=0, stream_id=0)
-    s2, _ = evaluation.sample_surface(c2, evaluation.area_prefix(a2), 10000, seed=0, stream_id=1)
+    a1, _, c1 = geometry.face_stats(*_dev(verts, faces))
+    a2, _, c2 = geometry.face_stats(*_dev(vg, fg))
+    s1, _ = geometry.sample_surface(c1, geometry.area_prefix(a1), 10000, seed=0, stream_id=0)
+    s2, _ = geometry.sample_surface(c2, geometry.area_prefix(a2), 10000, seed=0, stream_id=1)
     idx, d2 = evaluation.nearest(s2, s1)
     p1, p2 = s1.cpu().numpy().astype(np.float64), s2.cpu().numpy().astype(np.float64)
     ref = np.empty(p1.shape[0])

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from ppsurf_amd import evaluation, make_dataset as md, meshio, visualization
+from ppsurf_amd import geometry, make_dataset as md, meshio
 from tests import eval_spec, scan_spec
 
 pytestmark = pytest.mark.gpu
@@ -59,9 +59,9 @@ def test_first_hit_matches_spec_bitwise(mesh):
     d_np = np.concatenate([d_np, (tgt - eye[None]).astype(np.float32)])
     t_ref, f_ref = scan_spec.first_hit_spec(scan_spec.corners_of(v, f), o_np, d_np)
     assert (f_ref >= 0).mean() > 0.2
-    _, _, corners = evaluation.face_stats(_dev(v), _dev(f))
+    _, _, corners = geometry.face_stats(_dev(v), _dev(f))
     for s in (1, 37, None):
-        t, face = md.first_hit(corners, _dev(o_np), _dev(d_np), slices=s)
+        t, face = geometry.first_hit(corners, _dev(o_np), _dev(d_np), slices=s)
         t, face = t.cpu().numpy(), face.cpu().numpy()
         assert np.array_equal(face, f_ref), 'S = {}: {} faces differ'.format(s, int((face != f_ref).sum()))
         assert np.array_equal(t.view(np.uint64), t_ref.view(np.uint64)), 'S = {}: t differs'.format(s)
@@ -72,16 +72,16 @@ def test_noise_free_scans_lie_on_the_mesh_and_their_rays():
     settings = {'num_scans_per_mesh_min': 4, 'num_scans_per_mesh_max': 4, 'scanner_noise_sigma_max': 0.0, 'scan_resolution': 48}
     cams = _cams(v, settings, 'abc')
     L = float((v.max(0) - v.min(0)).max())
-    _, _, corners = evaluation.face_stats(_dev(v), _dev(f))
+    _, _, corners = geometry.face_stats(_dev(v), _dev(f))
     cams_d = _dev(cams)
     orig, dirs = md.scan_rays(cams_d, 48)
-    t, face = md.first_hit(corners, orig, dirs)
+    t, face = geometry.first_hit(corners, orig, dirs)
     pts_all = md.scan_points(corners, cams_d, 48, 0, 0, keep_misses=True)
     pts = md.scan_points(corners, cams_d, 48, 0, 0)
     hit = face >= 0
     assert pts.shape[0] == int(hit.sum()) > 1000
     assert torch.equal(pts, pts_all[hit]) and bool(torch.isnan(pts_all[~hit]).all())
-    _, d, _ = visualization.closest_point_on_corners(corners, pts)
+    _, d, _ = geometry.closest_point_on_corners(corners, pts)
     assert float(d.max()) <= 1e-6 * L
     o, dd, p = orig[hit].double(), dirs[hit].double(), pts.double()
     off_ray = torch.linalg.norm(torch.cross(p - o, dd, dim=1), dim=1)
@@ -101,10 +101,10 @@ def test_noisy_plane_residuals_and_spec():
     cams = _cams(v, settings, 'plane', seed=3)
     sigma = 0.01 * 2.0
     assert np.allclose(cams[:, 13], sigma)
-    _, _, corners = evaluation.face_stats(_dev(v), _dev(f))
+    _, _, corners = geometry.face_stats(_dev(v), _dev(f))
     cams_d = _dev(cams)
     orig, dirs = md.scan_rays(cams_d, 64)
-    t, face = md.first_hit(corners, orig, dirs)
+    t, face = geometry.first_hit(corners, orig, dirs)
     pts = md.scan_points(corners, cams_d, 64, 3, 77)
     hit = (face >= 0).cpu().numpy()
     assert hit.sum() > 5000
@@ -120,15 +120,15 @@ def test_query_points_match_spec():
     name = os.path.splitext(os.path.basename(GT_MESHES[2]))[0]
     q = md.query_points(_dev(v), _dev(f), name, 2001, 9).cpu().numpy()
     assert q.shape == (2001, 3) and q.dtype == np.float32
-    area, normal, corners = evaluation.face_stats(_dev(v), _dev(f))
+    area, normal, corners = geometry.face_stats(_dev(v), _dev(f))
     stream = md.shape_stream(name) << 2
-    surf, sface = eval_spec.sample_spec(corners.cpu().numpy(), evaluation.area_prefix(area).cpu().numpy(), 1001, 9, stream | 2)
+    surf, sface = eval_spec.sample_spec(corners.cpu().numpy(), geometry.area_prefix(area).cpu().numpy(), 1001, 9, stream | 2)
     _, nrm, _ = eval_spec.face_stats_spec(v, f)
     ref = scan_spec.queries_spec(surf, sface, nrm, 1000, 9, stream | 1, md.DEFAULTS['query_near_radius'])
     assert np.array_equal(q[:1000], ref[:1000])
     assert (q[:1000] >= -0.5).all() and (q[:1000] < 0.5).all()
     assert np.abs(q[1000:] - ref[1000:]).max() <= 1e-6
-    _, dist, _ = visualization.closest_point_on_corners(corners, _dev(q[1000:]))
+    _, dist, _ = geometry.closest_point_on_corners(corners, _dev(q[1000:]))
     assert float(dist.max()) <= md.DEFAULTS['query_near_radius'] * (1 + 1e-5)
 
 

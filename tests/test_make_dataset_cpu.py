@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from ppsurf_amd import _lib, make_dataset as md, meshio
+from ppsurf_amd import _lib, geometry, make_dataset as md, meshio
 from tests import eval_spec, scan_spec, vis_spec
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -189,7 +189,7 @@ def test_device_functions_refuse_cpu_tensors():
     with pytest.raises(_lib.PpsError):
         md.signed_distance(vt, ft, torch.zeros(4, 3))
     with pytest.raises(_lib.PpsError):
-        md.first_hit(torch.zeros(1, 9), torch.zeros(1, 3), torch.ones(1, 3))
+        geometry.first_hit(torch.zeros(1, 9), torch.zeros(1, 3), torch.ones(1, 3))
 
 
 def test_scan_abi_declared():

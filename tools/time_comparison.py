@@ -17,7 +17,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from ppsurf_amd import evaluation as ev, meshio, ops, visualization as vis  # noqa: E402
+from ppsurf_amd import geometry as geo, meshio, ops, visualization as vis  # noqa: E402
 from eval_spec import icosphere  # noqa: E402
 
 
@@ -38,7 +38,7 @@ def main():
     vg, fg = icosphere(5, r)
     v_gt = torch.from_numpy(vg.astype(np.float32)).to(dev)
     f_gt = torch.from_numpy(fg.astype(np.int32)).to(dev)
-    _, _, c_gt = ev.face_stats(v_gt, f_gt)
+    _, _, c_gt = geo.face_stats(v_gt, f_gt)
     cam = vis.camera_array(*vis.camera(v_rec.cpu().numpy(), size))
 
     stages = ['closest point', 'subdivide', 'raster', 'shade']
@@ -46,7 +46,7 @@ def main():
     for rep in range(args.reps + 1):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         e[0].record()
-        _, d, _ = vis.closest_point_on_corners(c_gt, v_rec)
+        _, d, _ = geo.closest_point_on_corners(c_gt, v_rec)
         e[1].record()
         vis.subdivide(v_rec, f_rec)
         e[2].record()
@@ -73,7 +73,7 @@ def main():
         rec, gt, pc = os.path.join(tmp, 'rec.ply'), os.path.join(tmp, 'gt.ply'), os.path.join(tmp, 'pc.ply')
         meshio.write_ply_mesh(rec, v_rec.cpu().numpy(), f_rec.cpu().numpy())
         meshio.write_ply_mesh(gt, vg, fg)
-        pts, _ = ev.sample_surface(c_gt, ev.area_prefix(ev.face_stats(v_gt, f_gt)[0]), 50000)
+        pts, _ = geo.sample_surface(c_gt, geo.area_prefix(geo.face_stats(v_gt, f_gt)[0]), 50000)
         meshio.write_ply_points(pc, pts.cpu().numpy())
         walls = []
         for rep in range(3):

@@ -13,7 +13,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from ppsurf_amd import evaluation as ev, ops  # noqa: E402
+from ppsurf_amd import evaluation as ev, geometry as geo, ops  # noqa: E402
 from eval_spec import icosphere  # noqa: E402
 
 
@@ -41,17 +41,17 @@ def main():
     for rep in range(args.reps + 1):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
         e[0].record()
-        ar, nr, cr = ev.face_stats(v_rec, f_rec)
-        ag, ng, cg = ev.face_stats(v_gt, f_gt)
+        ar, nr, cr = geo.face_stats(v_rec, f_rec)
+        ag, ng, cg = geo.face_stats(v_gt, f_gt)
         e[1].record()
-        pr, pg = ev.area_prefix(ar), ev.area_prefix(ag)
-        s_rec, fi_rec = ev.sample_surface(cr, pr, n, 0, 0)
-        s_gt, fi_gt = ev.sample_surface(cg, pg, n, 0, 1)
+        pr, pg = geo.area_prefix(ar), geo.area_prefix(ag)
+        s_rec, fi_rec = geo.sample_surface(cr, pr, n, 0, 0)
+        s_gt, fi_gt = geo.sample_surface(cg, pg, n, 0, 1)
         e[2].record()
         nn_rg, d2_rg = ev.nearest(s_gt, s_rec)
         _, d2_gr = ev.nearest(s_rec, s_gt)
         e[3].record()
-        w_rec, w_gt = ev.winding_number(cr, query), ev.winding_number(cg, query)
+        w_rec, w_gt = geo.winding_number(cr, query), geo.winding_number(cg, query)
         e[4].record()
         ev.reduce_sums(d2_rg, d2_gr, nn_rg, fi_rec, fi_gt, nr, ng, w_rec, w_gt)
         e[5].record()

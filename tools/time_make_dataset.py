@@ -15,12 +15,12 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from ppsurf_amd import evaluation as ev, make_dataset as md, meshio, ops  # noqa: E402
+from ppsurf_amd import geometry as geo, make_dataset as md, meshio, ops  # noqa: E402
 from eval_spec import icosphere  # noqa: E402
 
 
 def time_first_hit(name, verts, faces, reps):
-    _, _, corners = ev.face_stats(verts, faces)
+    _, _, corners = geo.face_stats(verts, faces)
     s = md.resolve_settings(None, num_scans_per_mesh_min=30, num_scans_per_mesh_max=30)
     v = verts.cpu().numpy()
     cams = md.scan_cameras(v.min(0), v.max(0), s, md.shape_rng(0, name))
@@ -29,7 +29,7 @@ def time_first_hit(name, verts, faces, reps):
     for rep in range(reps + 1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        t, face = md.first_hit(corners, orig, dirs)
+        t, face = geo.first_hit(corners, orig, dirs)
         e1.record()
         torch.cuda.synchronize()
         if rep > 0:                                   # the first round warms up (code objects, allocator)

@@ -691,6 +691,29 @@ int pps_cloud_mean_knn_dist(const float* d2, int64_t n, int k, double* m, void* 
 int pps_cloud_outlier_stats(const double* m, int64_t n, double ratio, double* out, void* stream);
 int pps_cloud_outlier_keep(const double* m, int64_t n, const double* stats, uint8_t* keep, void* stream);
 
+/* ---- mesh simplification: quadric vertex clustering (csrc/pps_simplify.hip) --------------------------------------------------------------------
+ * new capability (the reference writes the Marching Cubes mesh at the grid's own density), driven by ppsurf_amd/simplify.py.  The rules and
+ * the order of the fp64 operations are written out at the top of csrc/pps_simplify.hip and in DESIGN.md section 13; every result is a pure
+ * function of its inputs.  verts f64 [nv,3], faces int64 [nf,3] with indices in [0, nv) (device); lo, hi HOST f64 [3], the per-axis extremes
+ * of verts; h the cell edge and inv_h = 1 / h.  More than 2^20 cells along an axis, h <= 0 or a bad capacity: PPS_ERR_ARG, nothing is launched
+ * or written.
+ *   pps_simplify_leaders  leader int64 [nv]: the lowest vertex index of the cell of every vertex; count u64 [1]: number of occupied cells.
+ *                         table, best u64 [capacity] are scratch, capacity a power of two > nv (pps_cloud_table_capacity(nv)); no result
+ *                         depends on it.
+ *   pps_simplify_count    count u64 [1]: faces whose three leaders differ pairwise (the faces that survive before duplicate removal).
+ *   pps_simplify_place    one thread per cluster.  cid int64 [nv]: the cluster of every vertex (rank of its leader); corner_order /
+ *                         corner_off: CSR (pps_csr_build) of the 3 nf corner entries e = 3 f + k by cid[faces[f, k]]; vert_order / vert_off:
+ *                         CSR of the vertices by cid.  Out: A f64 [ncell,6] (A00 A01 A02 A11 A12 A22), b, xhat, pos f64 [ncell,3] and
+ *                         fallback u8 [ncell] = 1 where the cluster took its mean instead of the quadric optimum.  mean_only != 0: pos is
+ *                         centre + xhat everywhere and fallback 0. */
+int pps_simplify_leaders(const double* verts, int64_t nv, const double* lo, const double* hi, double h, double inv_h, uint64_t* table,
+                         uint64_t* best, int64_t capacity, int64_t* leader, uint64_t* count, void* stream);
+int pps_simplify_count(const int64_t* faces, int64_t nf, const int64_t* leader, int64_t nv, uint64_t* count, void* stream);
+int pps_simplify_place(const double* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* cid, int64_t ncell,
+                       const int64_t* corner_order, const int64_t* corner_off, const int64_t* vert_order, const int64_t* vert_off, const double* lo,
+                       const double* hi, double h, double inv_h, int mean_only, double* A, double* b, double* xhat, double* pos, uint8_t* fallback,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

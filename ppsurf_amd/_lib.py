@@ -150,6 +150,9 @@ SIGNATURES = {
     'pps_cloud_mean_knn_dist': (_I, [_P, _I64, _I, _P, _P]),
     'pps_cloud_outlier_stats': (_I, [_P, _I64, _c.c_double, _P, _P]),
     'pps_cloud_outlier_keep': (_I, [_P, _I64, _P, _P, _P]),
+    'pps_simplify_leaders': (_I, [_P, _I64, _P, _P, _c.c_double, _c.c_double, _P, _P, _I64, _P, _P, _P]),
+    'pps_simplify_count': (_I, [_P, _I64, _P, _I64, _P, _P]),
+    'pps_simplify_place': (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _c.c_double, _c.c_double, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

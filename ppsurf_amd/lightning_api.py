@@ -88,8 +88,11 @@ class PocoModel(_Base):
 
     def __init__(self, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir, padding_factor, name,
                  network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global, rec_batch_size,
-                 gen_refine_iter, workers):
+                 gen_refine_iter, workers, gen_max_faces=None):
         super().__init__()
+        if gen_max_faces is not None and int(gen_max_faces) < 4:
+            raise ValueError('gen_max_faces must be at least 4 (the faces of a tetrahedron), got {}'.format(gen_max_faces))
+        self.gen_max_faces = None if gen_max_faces is None else int(gen_max_faces)      # face budget of the written mesh (ppsurf_amd/simplify.py)
         self.output_names, self.in_channels, self.out_channels, self.k = output_names, in_channels, out_channels, k
         self.lambda_l1, self.network_latent_size = lambda_l1, network_latent_size
         self.gen_subsample_manifold_iter, self.gen_subsample_manifold = gen_subsample_manifold_iter, gen_subsample_manifold
@@ -452,7 +455,8 @@ class PocoModel(_Base):
         mesh = reconstruct.export_mesh_and_refine_vertices_region_growing_v3(
             network=self.network, latent=shape, pts_raw_ms=batch['pts_raw_ms'] if 'pts_raw_ms' in batch else None,
             resolution=self.gen_resolution_global, padding=1, mc_value=0, num_pts=self.rec_batch_size, num_pts_local=self.num_pts_local,
-            input_points=pts_cf.t().cpu().numpy(), refine_iter=self.gen_refine_iter, out_value=1, prog_bar=bar, pc_file_in=pc_file_in)
+            input_points=pts_cf.t().cpu().numpy(), refine_iter=self.gen_refine_iter, out_value=1, prog_bar=bar, pc_file_in=pc_file_in,
+            **({} if self.gen_max_faces is None else {'max_faces': self.gen_max_faces}))
         self.last_prediction = mesh
         if getattr(self, 'shard_queries', False) and sharding.world()[0] != 0:
             return 0                                                   # every rank holds the same mesh; rank 0 writes it
@@ -483,13 +487,14 @@ class PPSurfModel(PocoModel):
 
     def __init__(self, pointnet_latent_size, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir,
                  padding_factor, name, network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global,
-                 num_pts_local, rec_batch_size, gen_refine_iter, workers):
+                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None):
         self._pps = (num_pts_local, pointnet_latent_size)
         super().__init__(output_names=output_names, in_channels=in_channels, out_channels=out_channels, k=k, lambda_l1=lambda_l1,
                          debug=debug, in_file=in_file, results_dir=results_dir, padding_factor=padding_factor, name=name,
                          workers=workers, rec_batch_size=rec_batch_size, gen_refine_iter=gen_refine_iter,
                          gen_subsample_manifold=gen_subsample_manifold, gen_resolution_global=gen_resolution_global,
-                         gen_subsample_manifold_iter=gen_subsample_manifold_iter, network_latent_size=network_latent_size)
+                         gen_subsample_manifold_iter=gen_subsample_manifold_iter, network_latent_size=network_latent_size,
+                         gen_max_faces=gen_max_faces)
         self.num_pts_local, self.pointnet_latent_size = num_pts_local, pointnet_latent_size
 
     def _make_network(self):

@@ -159,11 +159,32 @@ def refine_vertices(eval_occ, verts: torch.Tensor, volume: torch.Tensor, step, b
     return verts
 
 
+def simplify_clean(verts: torch.Tensor, faces: torch.Tensor, max_faces: int):
+    """The face budget of a written mesh: simplify_mesh in model space, then the product's small-component rule (min_component_faces = 6) and
+    the compaction of the referenced vertices, so the file obeys the same guarantees as an unsimplified one.  Device tensors in and out."""
+    from . import simplify
+    verts, faces, _ = simplify.simplify_mesh(verts, faces, max_faces=max_faces)
+    return small_components_removed(verts, faces)
+
+
+def small_components_removed(verts: torch.Tensor, faces: torch.Tensor, min_component_faces=6):
+    """Faces of connected components of at most `min_component_faces` faces dropped (pps_mesh_small_components), unreferenced vertices
+    dropped, order kept: the last stage of mcubes.clean_mesh_torch without its merging by position."""
+    if faces.shape[0]:
+        faces = faces[~ops.mesh_small_components(faces.contiguous(), verts.shape[0], int(min_component_faces))]
+    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+    used[faces.reshape(-1)] = True
+    return verts[used], (torch.cumsum(used, 0) - 1)[faces]
+
+
 def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts_raw_ms, resolution: int, padding=0, mc_value=0,
                                                       num_pts=50000, num_pts_local=None, refine_iter=10, input_points=None,
-                                                      out_value=np.nan, dilation_size=2, prog_bar=None, pc_file_in: str = 'unknown'):
+                                                      out_value=np.nan, dilation_size=2, prog_bar=None, pc_file_in: str = 'unknown',
+                                                      max_faces=None):
     """poco_utils.py:26-175.  Returns (vertices float32 [V,3], faces int64 [F,3]) in model space, or None when the occupancy
-    never crosses `mc_value`.  (The reference wraps the same arrays into a trimesh.Trimesh; ppsurf_amd.meshio writes PLY.)"""
+    never crosses `mc_value`.  (The reference wraps the same arrays into a trimesh.Trimesh; ppsurf_amd.meshio writes PLY.)
+    `max_faces` (not in the reference): a face budget; the cleaned mesh is simplified to it on the device (ppsurf_amd/simplify.py) and passes
+    the small-component rule once more."""
     if latent['pts'].shape[0] != 1:
         raise ValueError('Reconstruction must be done with batch size = 0!')     # message kept from poco_utils.py:50
     progress = None
@@ -187,4 +208,7 @@ def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts
     verts, faces = mcubes.clean_mesh_torch(verts, faces, min_component_faces=6, welded=True, grid_coords=True)
     verts = refine_vertices(lambda q: sharding.sharded_map(field, q), verts, volume, step, bmin_pad, refine_iter, progress)
     verts, faces = mcubes.clean_mesh_torch(verts, faces, min_component_faces=6, welded=True, grid_coords=False)
+    if max_faces is not None:
+        # on the float32 vertices this function returns: the result is the one `python -m ppsurf_amd.simplify` gives on the unsimplified output
+        verts, faces = simplify_clean(verts.to(torch.float32), faces, int(max_faces))
     return verts.to(torch.float32).cpu().numpy(), faces.cpu().numpy()

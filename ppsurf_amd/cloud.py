@@ -27,7 +27,6 @@ import numpy as np
 import torch
 
 from . import _lib, meshio, ops
-from .geometry import _stream
 
 MAX_AXIS = 1 << 20
 
@@ -42,8 +41,7 @@ class VoxelGrid:
     test switch: results do not depend on it."""
 
     def __init__(self, pts: torch.Tensor, capacity=None):
-        if not torch.is_tensor(pts) or not pts.is_cuda:
-            raise _lib.PpsError('the voxel grid needs a device tensor; there is no CPU fallback')
+        _lib.need_device('VoxelGrid', pts)
         assert pts.dim() == 2 and pts.shape[1] == 3 and pts.shape[0] >= 1
         self.pts = pts.contiguous().float()
         self.n = int(self.pts.shape[0])
@@ -65,27 +63,24 @@ class VoxelGrid:
         h = np.float32(np.float64(self.ext) / np.float64(G))
         return h, np.float32(1.0) / h
 
-    def count_rc(self, h, inv_h):
+    def count_rc(self, h, inv_h, unchecked=True):
         """(status, number of occupied cells) of pps_cloud_voxel_count; the count is meaningless unless status == 0."""
         self._scratch()
-        rc = _lib.lib().pps_cloud_voxel_count(self.pts.data_ptr(), self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h),
-                                              self._table.data_ptr(), self.capacity, self._count.data_ptr(), _stream(self.pts))
+        rc = _lib.call('pps_cloud_voxel_count', self.pts, self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h), self._table, self.capacity,
+                       self._count, unchecked=unchecked)
         return rc, (int(self._count.item()) if rc == 0 else -1)
 
     def count(self, h, inv_h=None):
         inv_h = np.float32(1.0) / np.float32(h) if inv_h is None else inv_h
-        rc, c = self.count_rc(h, inv_h)
-        _lib.check(rc, 'pps_cloud_voxel_count')
-        return c
+        return self.count_rc(h, inv_h, unchecked=False)[1]
 
     def select(self, h, inv_h=None):
         """Ascending int64 indices (device) of the point kept by every occupied cell."""
         inv_h = np.float32(1.0) / np.float32(h) if inv_h is None else inv_h
         self._scratch(best=True)
         keep = torch.empty(self.n, dtype=torch.uint8, device=self.pts.device)
-        _lib.check(_lib.lib().pps_cloud_voxel_select(self.pts.data_ptr(), self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h),
-                                                     self._table.data_ptr(), self._best.data_ptr(), self.capacity, self._count.data_ptr(),
-                                                     keep.data_ptr(), _stream(self.pts)), 'pps_cloud_voxel_select')
+        _lib.call('pps_cloud_voxel_select', self.pts, self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h), self._table, self._best, self.capacity,
+                  self._count, keep)
         return torch.nonzero(keep).reshape(-1)
 
     def search(self, max_points):
@@ -102,12 +97,11 @@ class VoxelGrid:
 
 def mean_knn_distance(d2: torch.Tensor) -> torch.Tensor:
     """m f64 [n] of the squared (k+1)-NN distances d2 f32 [n, k+1] (ops.KnnBlocks.query(..., return_d2=True)); column 0 is dropped."""
-    if not d2.is_cuda:
-        raise _lib.PpsError('mean_knn_distance needs a device tensor; there is no CPU fallback')
+    _lib.need_device('mean_knn_distance', d2)
     d2 = d2.contiguous()
     assert d2.dtype == torch.float32 and d2.dim() == 2 and d2.shape[1] >= 2
     m = torch.empty(d2.shape[0], dtype=torch.float64, device=d2.device)
-    _lib.check(_lib.lib().pps_cloud_mean_knn_dist(d2.data_ptr(), d2.shape[0], d2.shape[1] - 1, m.data_ptr(), _stream(d2)), 'pps_cloud_mean_knn_dist')
+    _lib.call('pps_cloud_mean_knn_dist', d2, d2.shape[0], d2.shape[1] - 1, m)
     return m
 
 
@@ -115,14 +109,14 @@ def outlier_stats(m: torch.Tensor, ratio: float) -> torch.Tensor:
     """f64 [3] on the device: mean, population standard deviation, mean + ratio * deviation of m, summed in a fixed order."""
     assert m.is_cuda and m.dtype == torch.float64 and m.is_contiguous() and m.shape[0] >= 1
     out = torch.empty(3, dtype=torch.float64, device=m.device)
-    _lib.check(_lib.lib().pps_cloud_outlier_stats(m.data_ptr(), m.shape[0], float(ratio), out.data_ptr(), _stream(m)), 'pps_cloud_outlier_stats')
+    _lib.call('pps_cloud_outlier_stats', m, m.shape[0], float(ratio), out)
     return out
 
 
 def outlier_keep(m: torch.Tensor, stats: torch.Tensor) -> torch.Tensor:
     """Ascending int64 indices (device) of the points with m <= stats[2]."""
     keep = torch.empty(m.shape[0], dtype=torch.uint8, device=m.device)
-    _lib.check(_lib.lib().pps_cloud_outlier_keep(m.data_ptr(), m.shape[0], stats.data_ptr(), keep.data_ptr(), _stream(m)), 'pps_cloud_outlier_keep')
+    _lib.call('pps_cloud_outlier_keep', m, m.shape[0], stats, keep)
     return torch.nonzero(keep).reshape(-1)
 
 
@@ -150,8 +144,7 @@ def prepare_cloud(pts, max_points=None, voxel_size=None, outlier_k=0, outlier_ra
     if voxel_size is not None and not float(voxel_size) > 0:
         raise ValueError('voxel_size must be positive')
     if torch.is_tensor(pts):
-        if not pts.is_cuda:
-            raise _lib.PpsError('prepare_cloud needs a device tensor or a numpy array to upload; there is no CPU fallback')
+        _lib.need_device('prepare_cloud', pts)
         device = pts.device
         xyz = pts[:, :3]
         finite = torch.isfinite(xyz).all(dim=1)

@@ -45,7 +45,7 @@ def _wb(sd, name):
 def pack_dense(w):
     w = np.ascontiguousarray(w, dtype=np.float32)
     out = np.empty(_lib.lib().pps_packed_dense_floats(w.shape[0], w.shape[1]), dtype=np.float32)
-    _lib.check(_lib.lib().pps_pack_dense_f32(w.ctypes.data, w.shape[0], w.shape[1], out.ctypes.data), 'pps_pack_dense_f32')
+    _lib.call('pps_pack_dense_f32', w.ctypes.data, w.shape[0], w.shape[1], out.ctypes.data)
     return out
 
 
@@ -53,14 +53,14 @@ def pack_dense_f16x3(w):
     """[out,in] float -> uint16 image of the split-precision A operands (hi | lo f16 fragments, pps_pack_dense_f16x3)."""
     w = np.ascontiguousarray(w, dtype=np.float32)
     out = np.empty(_lib.lib().pps_packed_dense_f16x3_halfs(w.shape[0], w.shape[1]), dtype=np.uint16)
-    _lib.check(_lib.lib().pps_pack_dense_f16x3(w.ctypes.data, w.shape[0], w.shape[1], out.ctypes.data), 'pps_pack_dense_f16x3')
+    _lib.call('pps_pack_dense_f16x3', w.ctypes.data, w.shape[0], w.shape[1], out.ctypes.data)
     return out
 
 
 def pack_xyz(w):
     w = np.ascontiguousarray(w, dtype=np.float32)
     out = np.empty(_lib.lib().pps_packed_xyz_floats(w.shape[0]), dtype=np.float32)
-    _lib.check(_lib.lib().pps_pack_xyz_f32(w.ctypes.data, w.shape[0], out.ctypes.data), 'pps_pack_xyz_f32')
+    _lib.call('pps_pack_xyz_f32', w.ctypes.data, w.shape[0], out.ctypes.data)
     return out
 
 
@@ -218,9 +218,7 @@ class DecoderPlan:
         if cs == 1 and rs % 4 != 0:
             raise ValueError('point-major latents need a row stride that is a multiple of 4 floats')
         out = torch.empty((n, C), dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().pps_rows_dense256_f32(latents.data_ptr(), rs, cs, n, self.w['g_w'].data_ptr(),
-                                                    self.w['g_b'].data_ptr(), out.data_ptr(), st), 'pps_rows_dense256_f32')
+        _lib.call('pps_rows_dense256_f32', latents, rs, cs, n, self.w['g_w'], self.w['g_b'], out)
         return out
 
     def decode(self, table, pts, query, idx, patches, want_occ=True, stage_events=None, lane=0):
@@ -232,21 +230,19 @@ class DecoderPlan:
         q, k, p = query.shape[0], idx.shape[1], patches.shape[1]
         for t in (table, pts, query, idx, patches):
             assert t.is_contiguous() and t.device == self.device
-        st = torch.cuda.current_stream(self.device).cuda_stream
         logits = torch.empty((q, 2), dtype=torch.float32, device=self.device)
         occ = torch.empty((q,), dtype=torch.float32, device=self.device) if want_occ else None
         ws = self.scratch('decode_ws' if lane == 0 else 'decode_ws{}'.format(lane), (L.pps_decode_ws_bytes(q) // 4,))
         if getattr(self, '_wptrs', None) is None:
             self._wptrs = (ctypes.c_void_p * 10)(*[self.w[n].data_ptr() for n in ('ip_w', 'ip_b', 'pa_w', 'pa_b', 'pb_w', 'pb_b', 'pc_w',
                                                                                   'pc_b', 'tl_w', 'tl_b')])
-        args = (table.data_ptr(), pts.data_ptr(), query.data_ptr(), idx.data_ptr(), q, k, patches.data_ptr(), p, self._wptrs,
-                logits.data_ptr(), occ.data_ptr() if want_occ else None, ws.data_ptr())
+        args = (table, pts, query, idx, q, k, patches, p, self._wptrs, logits, occ, ws)
         if self.w16 is not None:
-            _lib.check(L.pps_decode_fwd_mixed_f32(*args[:9], self.w16, *args[9:], stage_events, st), 'pps_decode_fwd_mixed_f32')
+            _lib.call('pps_decode_fwd_mixed_f32', *args[:9], self.w16, *args[9:], stage_events)
         elif stage_events is None:
-            _lib.check(L.pps_decode_fwd_f32(*args, st), 'pps_decode_fwd_f32')
+            _lib.call('pps_decode_fwd_f32', *args)
         else:
-            _lib.check(L.pps_decode_fwd_events_f32(*args, stage_events, st), 'pps_decode_fwd_events_f32')
+            _lib.call('pps_decode_fwd_events_f32', *args, stage_events)
         return logits, occ
 
     def range_fallbacks(self):
@@ -422,24 +418,17 @@ class PocoDecoderPlan:
         """G [N,c] from latents of SHAPE [c,N] (any strides)."""
         lat = latents_cn.t().contiguous().float()
         out = torch.empty_like(lat)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(_lib.lib().pps_rows_gemm_f32(lat.data_ptr(), None, self.c, None, None, 0, self.g_w.data_ptr(), self.g_b.data_ptr(), None, 0,
-                                                lat.shape[0], self.c, out.data_ptr(), st), 'pps_rows_gemm_f32')
+        _lib.call('pps_rows_gemm_f32', lat, None, self.c, None, None, 0, self.g_w, self.g_b, None, 0, lat.shape[0], self.c, out)
         return out
 
     def decode(self, table, pts, query, idx):
         """table [N,c]; pts [N,3]; query [Q,3]; idx int64 [Q,k] -> logits [Q,nout]."""
         q, k = query.shape[0], idx.shape[1]
         out = torch.empty((q, self.nout), dtype=torch.float32, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
         if self.w16 is not None:
-            _lib.check(_lib.lib().pps_interp_small_f16x3(table.data_ptr(), pts.data_ptr(), query.data_ptr(), idx.data_ptr(), q, k, self.c,
-                                                         self.w.data_ptr(), self.w16.data_ptr(), self.b.data_ptr(), self.tail.data_ptr(), self.nout,
-                                                         out.data_ptr(), self._guard.data_ptr(), st), 'pps_interp_small_f16x3')
+            _lib.call('pps_interp_small_f16x3', table, pts, query, idx, q, k, self.c, self.w, self.w16, self.b, self.tail, self.nout, out, self._guard)
             return out
-        _lib.check(_lib.lib().pps_interp_small_f32(table.data_ptr(), pts.data_ptr(), query.data_ptr(), idx.data_ptr(), q, k, self.c,
-                                                   self.w.data_ptr(), self.b.data_ptr(), self.tail.data_ptr(), self.nout, out.data_ptr(), st),
-                   'pps_interp_small_f32')
+        _lib.call('pps_interp_small_f32', table, pts, query, idx, q, k, self.c, self.w, self.b, self.tail, self.nout, out)
         return out
 
     def range_fallbacks(self):

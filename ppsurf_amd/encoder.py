@@ -8,7 +8,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _stream
 
 BN_EPS = 1e-5
 ACT_CODE = {'relu': 1.0, 'silu': 2.0}
@@ -62,9 +61,7 @@ class FKAConvParams:
         L = _lib.lib()
         out = torch.empty((m, self.cout), dtype=torch.float32, device=x.device)
         ws = torch.empty((L.pps_fkaconv_ws_bytes(m, self.cin),), dtype=torch.uint8, device=x.device)
-        _lib.check(L.pps_fkaconv_fwd_f32(x.data_ptr(), pts.data_ptr(), sup.data_ptr(), idx.data_ptr(), n, m, k, self.cin, self.cout,
-                                         self.geo.data_ptr(), self.wpack.data_ptr(), self.bias.data_ptr() if self.bias is not None else None,
-                                         self.act_out, out.data_ptr(), ws.data_ptr(), _stream(x)), 'pps_fkaconv_fwd_f32')
+        _lib.call('pps_fkaconv_fwd_f32', x, pts, sup, idx, n, m, k, self.cin, self.cout, self.geo, self.wpack, self.bias, self.act_out, out, ws)
         return out
 
 
@@ -78,15 +75,11 @@ class FKAConvParams:
         g = torch.empty((mt, k, 16), dtype=torch.float32, device=x.device)
         stat = torch.empty((2, b, 32), dtype=torch.float32, device=x.device)
         ws = torch.empty((L.pps_fka_train_ws_bytes(b, mt // b, k),), dtype=torch.uint8, device=x.device)
-        _lib.check(L.pps_fka_geometry_fwd_f32(pts.data_ptr(), sup.data_ptr(), idx.data_ptr(), b, mt // b, k, geo_w.data_ptr(), 0.0,
-                                              g.data_ptr(), stat.data_ptr(), ws.data_ptr(), _stream(x)), 'pps_fka_geometry_fwd_f32')
+        _lib.call('pps_fka_geometry_fwd_f32', pts, sup, idx, b, mt // b, k, geo_w, 0.0, g, stat, ws)
         feat = torch.empty((mt, self.cin * 16), dtype=torch.float32, device=x.device)
-        _lib.check(L.pps_neighbour_contract_fwd_f32(x.data_ptr(), idx.data_ptr(), g.data_ptr(), mt, k, self.cin, feat.data_ptr(),
-                                                    _stream(x)), 'pps_neighbour_contract_fwd_f32')
+        _lib.call('pps_neighbour_contract_fwd_f32', x, idx, g, mt, k, self.cin, feat)
         out = torch.empty((mt, self.cout), dtype=torch.float32, device=x.device)
-        _lib.check(L.pps_rows_gemm_f32(feat.data_ptr(), None, self.cin * 16, None, None, 0, self.wpack.data_ptr(),
-                                       self.bias.data_ptr() if self.bias is not None else None, None, self.act_out, mt, self.cout,
-                                       out.data_ptr(), _stream(x)), 'pps_rows_gemm_f32')
+        _lib.call('pps_rows_gemm_f32', feat, None, self.cin * 16, None, None, 0, self.wpack, self.bias, None, self.act_out, mt, self.cout, out)
         return out
 
 
@@ -114,15 +107,10 @@ class LinearParams:
         if m is None:
             m = idx1.shape[0] if idx1 is not None else in1.shape[0]
         out = torch.empty((m, self.cout), dtype=torch.float32, device=in1.device)
-        p = lambda t: t.data_ptr() if t is not None else None
         if c1 % 16 == 0 and c2 % 16 == 0:
-            _lib.check(_lib.lib().pps_rows_gemm_f32(in1.data_ptr(), p(idx1), c1, p(in2), p(idx2), c2, self.wpack.data_ptr(),
-                                                    self.bias.data_ptr(), p(residual), 1 if relu else 0, m, self.cout, out.data_ptr(),
-                                                    _stream(in1)), 'pps_rows_gemm_f32')
+            _lib.call('pps_rows_gemm_f32', in1, idx1, c1, in2, idx2, c2, self.wpack, self.bias, residual, 1 if relu else 0, m, self.cout, out)
         else:
-            _lib.check(_lib.lib().pps_rows_linear_f32(in1.data_ptr(), p(idx1), c1, p(in2), p(idx2), c2, self.wt.data_ptr(),
-                                                      self.bias.data_ptr(), p(residual), 1 if relu else 0, m, self.cout, out.data_ptr(),
-                                                      _stream(in1)), 'pps_rows_linear_f32')
+            _lib.call('pps_rows_linear_f32', in1, idx1, c1, in2, idx2, c2, self.wt, self.bias, residual, 1 if relu else 0, m, self.cout, out)
         return out
 
 
@@ -130,7 +118,7 @@ def gather_max(x, idx):
     """out[m,c] = max_j x[idx[m,j], c]  (nn.py:677-680)."""
     m, k = idx.shape
     out = torch.empty((m, x.shape[1]), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().pps_gather_max_f32(x.data_ptr(), idx.data_ptr(), m, k, x.shape[1], out.data_ptr(), _stream(x)), 'pps_gather_max_f32')
+    _lib.call('pps_gather_max_f32', x, idx, m, k, x.shape[1], out)
     return out
 
 

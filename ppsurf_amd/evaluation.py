@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib, meshio, ops
-from .geometry import _device, _need_device, _ptr, _stream, area_prefix, face_stats, sample_surface, winding_number
+from .geometry import _device, area_prefix, face_stats, sample_surface, winding_number
 from .lightning_api import calc_f1, calc_precision, calc_recall
 
 METRIC_FILES = {'chamfer': 'chamfer_distance', 'f1': 'f1', 'iou': 'iou', 'normals': 'normal_error'}
@@ -51,9 +51,7 @@ def reduce_sums(d2_rg, d2_gr, nn_rg, face_rec, face_gt, normal_rec, normal_gt, w
     out = torch.empty(8, dtype=torch.float64, device=dev)
     n_rec = d2_rg.shape[0] if d2_rg is not None else 0
     n_gt = d2_gr.shape[0] if d2_gr is not None else 0
-    _lib.check(_lib.lib().pps_eval_reduce(_ptr(d2_rg), n_rec, _ptr(d2_gr), n_gt, _ptr(nn_rg), _ptr(face_rec), _ptr(face_gt), _ptr(normal_rec),
-                                          _ptr(normal_gt), w_rec.data_ptr(), w_gt.data_ptr(), w_rec.shape[0], out.data_ptr(), _stream(w_rec)),
-               'pps_eval_reduce')
+    _lib.call('pps_eval_reduce', d2_rg, n_rec, d2_gr, n_gt, nn_rg, face_rec, face_gt, normal_rec, normal_gt, w_rec, w_gt, w_rec.shape[0], out)
     return out
 
 
@@ -73,7 +71,7 @@ def mesh_metrics(verts_rec: torch.Tensor, faces_rec: torch.Tensor, verts_gt: tor
                  seed: int = 0) -> dict:
     """{'chamfer', 'f1', 'iou', 'normal_error'} of a reconstruction against its ground truth, all device tensors (verts [nv,3],
     faces [nf,3] integer).  Chamfer is -1.0 and the normal error NaN when either mesh has no samplable area (metrics.py:127-128)."""
-    _need_device(verts_rec, faces_rec, verts_gt, faces_gt)
+    _lib.need_device('evaluation', verts_rec, faces_rec, verts_gt, faces_gt)
     dev = verts_rec.device
     vr, fr = _upload(verts_rec, faces_rec, dev)
     vg, fg = _upload(verts_gt, faces_gt, dev)

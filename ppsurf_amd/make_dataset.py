@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, meshio
-from .geometry import (_device, _need_device, _ptr, _stream, area_prefix, closest_point_on_corners, face_stats, first_hit, sample_surface,
+from .geometry import (_device, area_prefix, closest_point_on_corners, face_stats, first_hit, sample_surface,
                        winding_number)
 
 DEFAULTS = {'num_scans_per_mesh_min': 5, 'num_scans_per_mesh_max': 30, 'scanner_noise_sigma_min': 0.0, 'scanner_noise_sigma_max': 0.05,
@@ -134,12 +134,12 @@ def scan_cameras(bb_min, bb_max, settings: dict, rng: np.random.Generator) -> np
 
 def scan_rays(cams: torch.Tensor, res: int):
     """One ray per pixel of every camera (device f32 [n_scans,16]) -> (orig, dirs f32 [n_scans res^2, 3])."""
-    _need_device(cams)
+    _lib.need_device('make_dataset', cams)
     cams = cams.to(torch.float32).contiguous()
     m = cams.shape[0] * res * res
     orig = torch.empty((m, 3), dtype=torch.float32, device=cams.device)
     dirs = torch.empty((m, 3), dtype=torch.float32, device=cams.device)
-    _lib.check(_lib.lib().pps_scan_rays(cams.data_ptr(), cams.shape[0], int(res), orig.data_ptr(), dirs.data_ptr(), _stream(cams)), 'pps_scan_rays')
+    _lib.call('pps_scan_rays', cams, cams.shape[0], int(res), orig, dirs)
     return orig, dirs
 
 
@@ -147,19 +147,17 @@ def scan_points(corners: torch.Tensor, cams: torch.Tensor, res: int, seed: int, 
                 keep_misses: bool = False) -> torch.Tensor:
     """The scans of the cameras cams (device f32 [n_scans,16]) of the mesh corners [nf,9] -> points f32 [k,3] of the hits in (scan, pixel)
     order (keep_misses: every pixel, NaN for a miss)."""
-    _need_device(corners, cams)
+    _lib.need_device('make_dataset', corners, cams)
     cams = cams.to(torch.float32).contiguous()
     orig, dirs = scan_rays(cams, res)
     t, face = first_hit(corners, orig, dirs, slices)
     pts = torch.empty_like(orig)
-    _lib.check(_lib.lib().pps_scan_points(orig.data_ptr(), dirs.data_ptr(), t.data_ptr(), face.data_ptr(), cams.data_ptr(), cams.shape[0], int(res),
-                                          int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), pts.data_ptr(), _stream(cams)),
-               'pps_scan_points')
+    _lib.call('pps_scan_points', orig, dirs, t, face, cams, cams.shape[0], int(res), int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 64 - 1), pts)
     return pts if keep_misses else pts[face >= 0]
 
 
 def _mesh_tables(verts: torch.Tensor, faces: torch.Tensor):
-    _need_device(verts, faces)
+    _lib.need_device('make_dataset', verts, faces)
     v = verts.to(torch.float32).contiguous()
     f = faces.to(torch.int32).contiguous()
     return face_stats(v, f)
@@ -190,14 +188,13 @@ def query_points(verts: torch.Tensor, faces: torch.Tensor, name: str, n: int = D
         if corners.shape[0] == 0 or not float(prefix[-1]) > 0.0:
             raise ValueError('the mesh has no samplable area')
         pts, face = sample_surface(corners, prefix, n_near, seed, (shape_stream(name) << 2) | 2)
-    _lib.check(_lib.lib().pps_scan_queries(_ptr(pts), _ptr(face), normal.data_ptr(), n_far, n_near, int(seed) & (2 ** 64 - 1),
-                                           (shape_stream(name) << 2) | 1, float(radius), out.data_ptr(), _stream(out)), 'pps_scan_queries')
+    _lib.call('pps_scan_queries', pts, face, normal, n_far, n_near, int(seed) & (2 ** 64 - 1), (shape_stream(name) << 2) | 1, float(radius), out)
     return out
 
 
 def signed_distance(verts: torch.Tensor, faces: torch.Tensor, query: torch.Tensor) -> torch.Tensor:
     """Signed distance f32 [m] of query [m,3] to the mesh, all device tensors: the exact distance, positive inside (|winding number| > 0.5)."""
-    _need_device(verts, faces, query)
+    _lib.need_device('make_dataset', verts, faces, query)
     _, _, corners = _mesh_tables(verts, faces)
     query = query.to(torch.float32).contiguous()
     _, d, _ = closest_point_on_corners(corners, query)

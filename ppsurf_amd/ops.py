@@ -2,22 +2,19 @@
 import torch
 
 from . import _lib
-from .geometry import _stream
 
 
 def knn_point_major(pts: torch.Tensor, query: torch.Tensor, k: int, return_d2: bool = False, out: torch.Tensor = None):
     """pts [n,3], query [m,3] float32 contiguous on the GPU -> int64 [m,k] (sorted by (d2, index)); k <= min(n, 64).
     `out`: optional preallocated int64 [m,k] (stream-pipelined callers)."""
-    if not (pts.is_cuda and query.is_cuda):
-        raise _lib.PpsError('pps_knn_f32 needs device tensors; there is no CPU fallback')
+    _lib.need_device('knn_point_major', pts, query)
     pts = pts.contiguous().float()
     query = query.contiguous().float()
     m = query.shape[0]
     idx = out if out is not None else torch.empty((m, k), dtype=torch.int64, device=pts.device)
     assert idx.dtype == torch.int64 and idx.is_contiguous() and tuple(idx.shape) == (m, k)
     d2 = torch.empty((m, k), dtype=torch.float32, device=pts.device) if return_d2 else None
-    _lib.check(_lib.lib().pps_knn_f32(pts.data_ptr(), pts.shape[0], query.data_ptr(), m, int(k), idx.data_ptr(),
-                                      d2.data_ptr() if return_d2 else None, _stream(pts)), 'pps_knn_f32')
+    _lib.call('pps_knn_f32', pts, pts.shape[0], query, m, int(k), idx, d2)
     return (idx, d2) if return_d2 else idx
 
 
@@ -31,13 +28,12 @@ def knn_batch_point_major(pts_list, query_list, k_list):
         nt = len(ps)
         P, I64, I = ctypes.c_void_p * nt, ctypes.c_int64 * nt, ctypes.c_int * nt
         pts, qry, out, ns, ms, kk = P(), P(), P(), I64(), I64(), I()
+        _lib.need_device('knn_batch_point_major', *ps, *qs)
         for t in range(nt):
-            if not (ps[t].is_cuda and qs[t].is_cuda):
-                raise _lib.PpsError('pps_knn_multi_f32 needs device tensors; there is no CPU fallback')
             o = torch.empty((qs[t].shape[0], ks[t]), dtype=torch.int64, device=ps[t].device)
             outs.append(o)
             pts[t], qry[t], out[t], ns[t], ms[t], kk[t] = ps[t].data_ptr(), qs[t].data_ptr(), o.data_ptr(), ps[t].shape[0], qs[t].shape[0], ks[t]
-        _lib.check(_lib.lib().pps_knn_multi_f32(nt, pts, ns, qry, ms, kk, out, _stream(ps[0])), 'pps_knn_multi_f32')
+        _lib.call('pps_knn_multi_f32', nt, pts, ns, qry, ms, kk, out, on=ps[0])
     return outs
 
 
@@ -95,8 +91,7 @@ def knn_blocked_batch(kinds):
             pts[t], orig[t], bbox[t], win[t] = pl.pts.data_ptr(), pl.orig.data_ptr(), pl.bbox.data_ptr(), pl.win.data_ptr() if pl.win is not None else None
             qry[t], qorig[t], out[t] = q_t.data_ptr(), qo_t.data_ptr() if qo_t is not None else None, o.data_ptr()
             nb[t], nwin[t], qstride[t], ms[t], ks[t] = pl.nb, pl.n_win, stride, m, k
-        _lib.check(_lib.lib().pps_knn_blocked_batch_f32(nt, part[0][0].b, pts, orig, bbox, nb, win, nwin, qry, qorig, qstride, ms, ks, out,
-                                                        _stream(part[0][0].pts)), 'pps_knn_blocked_batch_f32')
+        _lib.call('pps_knn_blocked_batch_f32', nt, part[0][0].b, pts, orig, bbox, nb, win, nwin, qry, qorig, qstride, ms, ks, out, on=part[0][0].pts)
     return outs
 
 
@@ -109,8 +104,7 @@ def patch_normalize(raw: torch.Tensor, query: torch.Tensor, idx: torch.Tensor, p
     if out is None:
         out = torch.empty((q, p, 3), dtype=torch.float32, device=raw.device)
     assert out.is_contiguous() and tuple(out.shape) == (q, p, 3)
-    _lib.check(_lib.lib().pps_patch_normalize_f32(raw.data_ptr(), query.data_ptr(), idx.data_ptr(), idx.stride(0), q, int(p),
-                                                  out.data_ptr(), _stream(raw)), 'pps_patch_normalize_f32')
+    _lib.call('pps_patch_normalize_f32', raw, query, idx, idx.stride(0), q, int(p), out)
     return out
 
 
@@ -120,20 +114,13 @@ class KnnBlocks:
     to knn_point_major."""
 
     def __init__(self, pts: torch.Tensor):
-        if not pts.is_cuda:
-            raise _lib.PpsError('KnnBlocks needs a device tensor; there is no CPU fallback')
+        _lib.need_device('KnnBlocks', pts)
         pts = pts.contiguous().float()
         n = pts.shape[0]
         lo = pts.min(dim=0)[0]
         span = (pts.max(dim=0)[0] - lo).max().clamp_min(1e-20)
         cell = ((pts - lo) / span * 1023.0).to(torch.int64).clamp_(0, 1023)
-
-        def spread(v):                                   # 10 bits -> every third bit
-            v = (v | (v << 16)) & 0x030000FF
-            v = (v | (v << 8)) & 0x0300F00F
-            v = (v | (v << 4)) & 0x030C30C3
-            return (v | (v << 2)) & 0x09249249
-        code = spread(cell[:, 0]) | (spread(cell[:, 1]) << 1) | (spread(cell[:, 2]) << 2)
+        code = _morton_spread(cell[:, 0]) | (_morton_spread(cell[:, 1]) << 1) | (_morton_spread(cell[:, 2]) << 2)
         order = torch.sort(code, stable=True)[1]
         nb = (n + 63) // 64
         pad = nb * 64 - n
@@ -170,10 +157,8 @@ class KnnBlocks:
         assert idx.dtype == torch.int64 and idx.is_contiguous() and tuple(idx.shape) == (m, k)
         d2 = torch.empty((m, k), dtype=torch.float32, device=query.device) if return_d2 else None
         win = self._windows((int(k) + 63) // 64) if 1 <= int(k) <= 256 else None
-        _lib.check(_lib.lib().pps_knn_blocked_groups_f32(self.pts.data_ptr(), self.orig.data_ptr(), self.bbox.data_ptr(), self.nb, self.n,
-                                                         win.data_ptr() if win is not None else None, win.shape[0] if win is not None else 0,
-                                                         self.gbox.data_ptr() if self.groups else None, query.data_ptr(), m, int(k), idx.data_ptr(),
-                                                         d2.data_ptr() if return_d2 else None, _stream(query)), 'pps_knn_blocked_groups_f32')
+        _lib.call('pps_knn_blocked_groups_f32', self.pts, self.orig, self.bbox, self.nb, self.n, win, win.shape[0] if win is not None else 0,
+                  self.gbox if self.groups else None, query, m, int(k), idx, d2)
         return (idx, d2) if return_d2 else idx
 
 
@@ -183,8 +168,7 @@ def dilate_box(mask: torch.Tensor, r: int) -> torch.Tensor:
     assert mask.dtype == torch.bool and mask.dim() == 3 and mask.is_cuda
     src = mask.contiguous()
     dst, tmp = torch.empty_like(src), torch.empty_like(src)
-    _lib.check(_lib.lib().pps_dilate_box_u8(src.data_ptr(), dst.data_ptr(), tmp.data_ptr(), src.shape[0], src.shape[1], src.shape[2], int(r), _stream(src)),
-               'pps_dilate_box_u8')
+    _lib.call('pps_dilate_box_u8', src, dst, tmp, src.shape[0], src.shape[1], src.shape[2], int(r))
     return dst
 
 
@@ -194,8 +178,7 @@ def grow_frontier(volume: torch.Tensor, neg: torch.Tensor, pos: torch.Tensor, to
     for m in (neg, pos, to_see):
         assert m.dtype == torch.bool and m.shape == volume.shape and m.is_contiguous()
     out = torch.empty_like(to_see)
-    _lib.check(_lib.lib().pps_grow_frontier_f64(volume.data_ptr(), neg.data_ptr(), pos.data_ptr(), to_see.data_ptr(), out.data_ptr(), volume.numel(),
-                                                _stream(volume)), 'pps_grow_frontier_f64')
+    _lib.call('pps_grow_frontier_f64', volume, neg, pos, to_see, out, volume.numel())
     return out
 
 
@@ -203,7 +186,7 @@ def grow_band_todo(volume: torch.Tensor, band: torch.Tensor) -> torch.Tensor:
     """band & isnan(volume) in one pass."""
     assert volume.dtype == torch.float64 and volume.is_cuda and volume.is_contiguous() and band.dtype == torch.bool and band.is_contiguous()
     out = torch.empty_like(band)
-    _lib.check(_lib.lib().pps_grow_band_todo_f64(volume.data_ptr(), band.data_ptr(), out.data_ptr(), volume.numel(), _stream(volume)), 'pps_grow_band_todo_f64')
+    _lib.call('pps_grow_band_todo_f64', volume, band, out, volume.numel())
     return out
 
 
@@ -225,10 +208,8 @@ def marching_cubes(volume: torch.Tensor, level: float):
     flags = torch.empty(nedge, dtype=torch.uint8, device=dev)
     counts = torch.empty(2 * nbc + nbe, dtype=torch.int32, device=dev)
     bt, bc, bv = counts[:nbc], counts[nbc:2 * nbc], counts[2 * nbc:]
-    st = _stream(volume)
     lvl = ctypes.c_double(float(level))
-    _lib.check(L.pps_mc_count_f64(volume.data_ptr(), nx, ny, nz, lvl, tri.data_ptr(), mcubes.TABLE_WIDTH, ntri.data_ptr(), amb.data_ptr(),
-                                  tun_index.data_ptr(), tun_cand.data_ptr(), flags.data_ptr(), bt.data_ptr(), bc.data_ptr(), bv.data_ptr(), st), 'pps_mc_count_f64')
+    _lib.call('pps_mc_count_f64', volume, nx, ny, nz, lvl, tri, mcubes.TABLE_WIDTH, ntri, amb, tun_index, tun_cand, flags, bt, bc, bv)
     inc = [torch.cumsum(x, 0, dtype=torch.int64) for x in (bt, bc, bv)]
     n_tri, n_cen, n_vert = [int(v) for v in torch.stack([i[-1] for i in inc]).tolist()]
     verts = torch.empty((n_vert + n_cen, 3), dtype=torch.float64, device=dev)
@@ -237,9 +218,8 @@ def marching_cubes(volume: torch.Tensor, level: float):
         return verts[:0], faces
     off = [(i - x).contiguous() for i, x in zip(inc, (bt, bc, bv))]
     vidx = torch.empty(nedge, dtype=torch.int32, device=dev)
-    _lib.check(L.pps_mc_emit_f64(volume.data_ptr(), nx, ny, nz, lvl, tri.data_ptr(), mcubes.TABLE_WIDTH, ntri.data_ptr(), amb.data_ptr(), tun_index.data_ptr(),
-                                 tun_cand.data_ptr(), flags.data_ptr(), off[0].data_ptr(), off[1].data_ptr(), off[2].data_ptr(), n_vert, vidx.data_ptr(), verts.data_ptr(), faces.data_ptr(), st),
-               'pps_mc_emit_f64')
+    _lib.call('pps_mc_emit_f64', volume, nx, ny, nz, lvl, tri, mcubes.TABLE_WIDTH, ntri, amb, tun_index, tun_cand, flags, off[0], off[1], off[2], n_vert, vidx,
+              verts, faces)
     return verts, faces
 
 
@@ -254,7 +234,7 @@ def mesh_small_components(faces: torch.Tensor, nv: int, k: int):
         return small.bool()
     faces = faces.contiguous()
     ws = torch.empty(L.pps_mesh_components_ws_bytes(nf), dtype=torch.uint8, device=faces.device)
-    _lib.check(L.pps_mesh_small_components(faces.data_ptr(), nf, int(nv), int(k), small.data_ptr(), ws.data_ptr(), _stream(faces)), 'pps_mesh_small_components')
+    _lib.call('pps_mesh_small_components', faces, nf, int(nv), int(k), small, ws)
     return small.bool()
 
 
@@ -271,8 +251,7 @@ def mesh_corner_weld(verts: torch.Tensor, digits: int = 8):
     hot = torch.empty(nv, dtype=torch.uint8, device=dev)
     counters = torch.empty(2, dtype=torch.int32, device=dev)
     ws = torch.empty(L.pps_mesh_weld_ws_bytes(nv), dtype=torch.uint8, device=dev)
-    _lib.check(L.pps_mesh_corner_weld(verts.data_ptr(), nv, int(digits), remap.data_ptr(), hot.data_ptr(), counters.data_ptr(), ws.data_ptr(), _stream(verts)),
-               'pps_mesh_corner_weld')
+    _lib.call('pps_mesh_corner_weld', verts, nv, int(digits), remap, hot, counters, ws)
     merged, out_of_range = counters.tolist()
     if out_of_range:
         raise _lib.PpsError('pps_mesh_corner_weld: vertex coordinates outside [0, 524287] (not a mesh in grid index space)')
@@ -290,5 +269,5 @@ def mesh_face_filter(faces: torch.Tensor, hot: torch.Tensor):
         return keep.bool()
     faces = faces.contiguous()
     ws = torch.empty(L.pps_mesh_face_filter_ws_bytes(nf), dtype=torch.uint8, device=faces.device)
-    _lib.check(L.pps_mesh_face_filter(faces.data_ptr(), nf, hot.data_ptr(), keep.data_ptr(), ws.data_ptr(), _stream(faces)), 'pps_mesh_face_filter')
+    _lib.call('pps_mesh_face_filter', faces, nf, hot, keep, ws)
     return keep.bool()

@@ -123,19 +123,14 @@ class AdamW(torch.optim.AdamW):
             super().step()                                            # torch's fused multi-tensor step (same arithmetic, same state)
             return loss
         grad_scale, found_inf = getattr(self, 'grad_scale', None), getattr(self, 'found_inf', None)
-        lib = _lib.lib()
         for group, (_, pieces, steps, n_pieces, n_steps, _q) in plan:
             lr = group['lr']
             lr_dev = lr if torch.is_tensor(lr) and lr.is_cuda else None
             beta1, beta2 = group['betas']
             dev = pieces.device
             with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(lib.pps_adamw_step(pieces.data_ptr(), n_pieces, steps.data_ptr(), n_steps,
-                                              lr_dev.data_ptr() if lr_dev is not None else None, 0.0 if lr_dev is not None else float(lr),
-                                              float(beta1), float(beta2), float(group['eps']), float(group['weight_decay']),
-                                              grad_scale.data_ptr() if grad_scale is not None else None,
-                                              found_inf.data_ptr() if found_inf is not None else None, stream), 'pps_adamw_step')
+                _lib.call('pps_adamw_step', pieces, n_pieces, steps, n_steps, lr_dev, 0.0 if lr_dev is not None else float(lr), float(beta1), float(beta2),
+                          float(group['eps']), float(group['weight_decay']), grad_scale, found_inf)
         self.fast_steps += 1
         return loss
 

@@ -23,7 +23,6 @@ import numpy as np
 import torch
 
 from . import _lib, meshio
-from .geometry import _stream
 
 MAX_AXIS = 1 << 20
 PLACEMENTS = ('quadric', 'mean')
@@ -47,8 +46,7 @@ def _csr(ids: torch.Tensor, rows: int):
     offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
     nbytes = L.pps_csr_ws_bytes(n, rows)
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    _lib.check(L.pps_csr_build(ids.data_ptr(), n, 0, 0, int(rows), 0, None, order.data_ptr(), offsets.data_ptr(), ws.data_ptr(), nbytes, _stream(ids)),
-               'pps_csr_build')
+    _lib.call('pps_csr_build', ids, n, 0, 0, int(rows), 0, None, order, offsets, ws, nbytes)
     return order, offsets
 
 
@@ -57,8 +55,7 @@ class ClusterGrid:
     simplification itself.  `capacity` (a power of two > nv) is a test switch: results do not depend on it."""
 
     def __init__(self, verts: torch.Tensor, faces: torch.Tensor, capacity=None):
-        if not (torch.is_tensor(verts) and verts.is_cuda and torch.is_tensor(faces) and faces.is_cuda):
-            raise _lib.PpsError('the cluster grid needs device tensors; there is no CPU fallback')
+        _lib.need_device('ClusterGrid', verts, faces)
         assert verts.dim() == 2 and verts.shape[1] == 3 and verts.shape[0] >= 1 and faces.dim() == 2 and faces.shape[1] == 3
         self.verts = verts.to(torch.float64).contiguous()
         self.faces = faces.to(torch.int64).contiguous()
@@ -85,22 +82,19 @@ class ClusterGrid:
         h = np.float64(self.ext) / np.float64(G)
         return h, np.float64(1.0) / h
 
-    def leaders_rc(self, h, inv_h):
+    def leaders_rc(self, h, inv_h, unchecked=True):
         """(status, leader int64 [nv] (device, reused by the next call), occupied cells) of pps_simplify_leaders."""
         self._scratch()
-        rc = _lib.lib().pps_simplify_leaders(self.verts.data_ptr(), self.nv, _d3(self.lo), _d3(self.hi), float(h), float(inv_h), self._table.data_ptr(),
-                                             self._best.data_ptr(), self.capacity, self._leader.data_ptr(), self._count.data_ptr(), _stream(self.verts))
+        rc = _lib.call('pps_simplify_leaders', self.verts, self.nv, _d3(self.lo), _d3(self.hi), float(h), float(inv_h), self._table, self._best,
+                       self.capacity, self._leader, self._count, unchecked=unchecked)
         return rc, self._leader, (int(self._count.item()) if rc == 0 else -1)
 
     def leaders(self, h, inv_h=None):
         inv_h = np.float64(1.0) / np.float64(h) if inv_h is None else inv_h
-        rc, leader, cells = self.leaders_rc(h, inv_h)
-        _lib.check(rc, 'pps_simplify_leaders')
-        return leader, cells
+        return self.leaders_rc(h, inv_h, unchecked=False)[1:]
 
     def survivors(self, leader):
-        _lib.check(_lib.lib().pps_simplify_count(self.faces.data_ptr(), self.nf, leader.data_ptr(), self.nv, self._count.data_ptr(), _stream(self.verts)),
-                   'pps_simplify_count')
+        _lib.call('pps_simplify_count', self.faces, self.nf, leader, self.nv, self._count)
         return int(self._count.item())
 
     def count_step(self, h, inv_h=None):
@@ -156,10 +150,8 @@ class ClusterGrid:
         A = torch.empty((ncell, 6), dtype=torch.float64, device=dev)
         b, xhat, pos = (torch.empty((ncell, 3), dtype=torch.float64, device=dev) for _ in range(3))
         fell = torch.empty(ncell, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().pps_simplify_place(self.verts.data_ptr(), self.nv, self.faces.data_ptr(), self.nf, cid.data_ptr(), ncell,
-                                                 c_order.data_ptr(), c_off.data_ptr(), v_order.data_ptr(), v_off.data_ptr(), _d3(self.lo), _d3(self.hi),
-                                                 float(h), float(inv_h), 1 if placement == 'mean' else 0, A.data_ptr(), b.data_ptr(), xhat.data_ptr(),
-                                                 pos.data_ptr(), fell.data_ptr(), _stream(self.verts)), 'pps_simplify_place')
+        _lib.call('pps_simplify_place', self.verts, self.nv, self.faces, self.nf, cid, ncell, c_order, c_off, v_order, v_off, _d3(self.lo), _d3(self.hi),
+                  float(h), float(inv_h), 1 if placement == 'mean' else 0, A, b, xhat, pos, fell)
         new = corner_ids.reshape(-1, 3)
         alive = (new[:, 0] != new[:, 1]) & (new[:, 1] != new[:, 2]) & (new[:, 0] != new[:, 2])
         src = torch.nonzero(alive).reshape(-1)                                  # input face of every survivor
@@ -214,8 +206,7 @@ def simplify_mesh(verts, faces, max_faces=None, voxel_size=None, placement='quad
         dv = torch.from_numpy(np.ascontiguousarray(v_in)).to(device)
         df = torch.from_numpy(np.ascontiguousarray(f_in.astype(np.int64))).to(device)
     else:
-        if not (verts.is_cuda and torch.is_tensor(faces) and faces.is_cuda):
-            raise _lib.PpsError('simplify_mesh needs device tensors or host arrays to upload; there is no CPU fallback')
+        _lib.need_device('simplify_mesh', verts, faces)
         dv, df = verts, faces
     nv, nf = int(dv.shape[0]), int(df.shape[0])
     report = {'faces_in': nf, 'verts_in': nv, 'G': None, 'h': None, 'cells': None, 'survivors': nf, 'faces_out': nf, 'verts_out': nv,

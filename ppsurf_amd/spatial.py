@@ -89,18 +89,14 @@ def voxel_sample_point_major(pts_pm: torch.Tensor, target: int, rotations: torch
     pr = _prio(priority, pts_pm.device)
     out = torch.empty((target,), dtype=torch.int64, device=pts_pm.device)
     L = _lib.lib()
-    st = torch.cuda.current_stream(pts_pm.device).cuda_stream
     if n > L.pps_voxel_sample_max_points():
         # beyond the LDS tables of the one-launch kernel: the same procedure with its tables in a device workspace (any cloud size stays on the GPU)
         nbytes = L.pps_voxel_sample_large_ws_bytes(n)
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=pts_pm.device)
-        _lib.check(L.pps_voxel_sample_large_f32(pts_pm.data_ptr(), n, int(target), ctypes.c_float(-1.0), rot.data_ptr(), rot.shape[0],
-                                                ctypes.c_uint32(seed & 0xffffffff), pr.data_ptr() if pr is not None else None, out.data_ptr(), None,
-                                                ws.data_ptr(), nbytes, st), 'pps_voxel_sample_large_f32')
+        _lib.call('pps_voxel_sample_large_f32', pts_pm, n, int(target), ctypes.c_float(-1.0), rot, rot.shape[0], ctypes.c_uint32(seed & 0xffffffff), pr, out,
+                  None, ws, nbytes)
         return out
-    _lib.check(L.pps_voxel_sample_f32(pts_pm.data_ptr(), n, int(target), ctypes.c_float(-1.0), rot.data_ptr(), rot.shape[0],
-                                      ctypes.c_uint32(seed & 0xffffffff), pr.data_ptr() if pr is not None else None, out.data_ptr(), None, st),
-               'pps_voxel_sample_f32')
+    _lib.call('pps_voxel_sample_f32', pts_pm, n, int(target), ctypes.c_float(-1.0), rot, rot.shape[0], ctypes.c_uint32(seed & 0xffffffff), pr, out, None)
     return out
 
 
@@ -110,9 +106,7 @@ def voxel_sample_batch_point_major(pts_bpm: torch.Tensor, target: int) -> torch.
     rot = draw_rotations(batch=b).reshape(b, -1, 27).contiguous().to(pts_bpm.device, non_blocking=True)
     seed = random.getrandbits(31)
     out = torch.empty((b, target), dtype=torch.int64, device=pts_bpm.device)
-    _lib.check(_lib.lib().pps_voxel_sample_batch_f32(pts_bpm.data_ptr(), b, n, int(target), rot.data_ptr(), rot.shape[1],
-                                                     ctypes.c_uint32(seed & 0xffffffff), None, out.data_ptr(), None,
-                                                     torch.cuda.current_stream(pts_bpm.device).cuda_stream), 'pps_voxel_sample_batch_f32')
+    _lib.call('pps_voxel_sample_batch_f32', pts_bpm, b, n, int(target), rot, rot.shape[1], ctypes.c_uint32(seed & 0xffffffff), None, out, None)
     return out
 
 

@@ -90,7 +90,7 @@ def _cast_all(params, dtype):
         cached = (key, torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows))
         _cast_tables[(dev, dtype, key)] = cached
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pps_cast_pieces(cached[1].data_ptr(), cached[2], code, torch.cuda.current_stream(dev).cuda_stream), 'pps_cast_pieces')
+        _lib.call('pps_cast_pieces', cached[1], cached[2], code)
     return True
 
 
@@ -120,8 +120,7 @@ def _transpose_all(params, dtype):
         cached = (key, torch.from_numpy(np.asarray(rows, dtype=np.int64)).to(dev), len(rows), tile0)
         _tr_tables[(dev, dtype, key)] = cached
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pps_transpose_cast_pieces(cached[1].data_ptr(), cached[2], cached[3], code, torch.cuda.current_stream(dev).cuda_stream),
-                   'pps_transpose_cast_pieces')
+        _lib.call('pps_transpose_cast_pieces', cached[1], cached[2], cached[3], code)
     return True
 
 

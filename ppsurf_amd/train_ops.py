@@ -24,10 +24,6 @@ import torch
 from . import _lib
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 LOW = (torch.bfloat16, torch.float16)          # 16-bit storage types of the fused training ops (trainer.precision bf16-mixed / 16-mixed)
 
 
@@ -46,10 +42,9 @@ def _low(t, like=None):
     return t.to(dt if dt in LOW else torch.bfloat16).contiguous()
 
 
-def _need_cuda(*tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise _lib.PpsError('ppsurf_amd.train_ops runs on the GPU only (got a {} tensor): there is no CPU path'.format(t.device))
+def _row1(affine, c):
+    """Address of the second row of an fp32 pair [2, c] (the shift of a stored activation's affine part); None stays None."""
+    return None if affine is None else affine.data_ptr() + 4 * c
 
 
 _csr_cache = {}
@@ -83,7 +78,7 @@ def csr_build(idx_flat: torch.Tensor, n: int):
 def csr_build_table(ids: torch.Tensor, per_item: int, rows_per_item: int, rows: int, clamp_negative: bool, want_flat: bool = True):
     """(flat, order, offsets) of an id table [B, M, K] of a fit batch in one call: flat row numbers ids + item * rows_per_item (per_item = M * K
     entries per batch item; -1 -> row 0 with clamp_negative), and their CSR.  per_item = 0: `ids` are flat rows already."""
-    _need_cuda(ids)
+    _lib.need_device('train_ops', ids)
     if ids.dtype != torch.int64:
         raise _lib.PpsError('csr_build: id tables are int64')
     ids = ids.contiguous()
@@ -95,9 +90,7 @@ def csr_build_table(ids: torch.Tensor, per_item: int, rows_per_item: int, rows: 
     offsets = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
     nbytes = L.pps_csr_ws_bytes(entries, rows)
     ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-    _lib.check(L.pps_csr_build(ids.data_ptr(), entries, int(per_item), int(rows_per_item), int(rows), 1 if clamp_negative else 0,
-                               flat.data_ptr() if flat is not None else None, order.data_ptr(), offsets.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-               'pps_csr_build')
+    _lib.call('pps_csr_build', ids, entries, int(per_item), int(rows_per_item), int(rows), 1 if clamp_negative else 0, flat, order, offsets, ws, nbytes)
     return flat, order, offsets
 
 
@@ -111,15 +104,14 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, idx):
-        _need_cuda(x, idx)
+        _lib.need_device('train_ops', x, idx)
         if x.dtype not in (torch.float32,) + LOW or (x.dtype in LOW and x.shape[1] % 2):
             x = x.float()
         x = x.contiguous()
         idx = idx.contiguous()
         out = torch.empty((idx.numel(), x.shape[1]), device=x.device, dtype=x.dtype)
         words = x.shape[1] if x.dtype == torch.float32 else x.shape[1] // 2
-        _lib.check(_lib.lib().pps_gather_rows_f32(x.data_ptr(), idx.data_ptr(), idx.numel(), words, out.data_ptr(), _stream()),
-                   'pps_gather_rows_f32')
+        _lib.call('pps_gather_rows_f32', x, idx, idx.numel(), words, out)
         ctx.save_for_backward(idx)
         ctx.n = x.shape[0]
         ctx.dtype = x.dtype
@@ -134,12 +126,10 @@ class _GatherRows(torch.autograd.Function):
         dout = dout.contiguous()
         dx = torch.empty((ctx.n, dout.shape[1]), device=dout.device, dtype=torch.float32)
         if dout.dtype in LOW and dout.shape[1] % 4 == 0:
-            _lib.check(_lib.lib().pps_segment_sum_rows_16(dout.data_ptr(), order.data_ptr(), offsets.data_ptr(), ctx.n, dout.shape[1],
-                                                          _code(dout.dtype), dx.data_ptr(), _stream()), 'pps_segment_sum_rows_16')
+            _lib.call('pps_segment_sum_rows_16', dout, order, offsets, ctx.n, dout.shape[1], _code(dout.dtype), dx)
         else:
             dout = dout.float()
-            _lib.check(_lib.lib().pps_segment_sum_rows_f32(dout.data_ptr(), order.data_ptr(), offsets.data_ptr(), ctx.n, dout.shape[1],
-                                                           dx.data_ptr(), _stream()), 'pps_segment_sum_rows_f32')
+            _lib.call('pps_segment_sum_rows_f32', dout, order, offsets, ctx.n, dout.shape[1], dx)
         return dx.to(ctx.dtype), None
 
 
@@ -149,16 +139,14 @@ class _HeadInput(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, ids, pts, query, k, wx):
-        _need_cuda(table, ids, pts, query, wx)
-        L = _lib.lib()
+        _lib.need_device('train_ops', table, ids, pts, query, wx)
         table = _low(table)
         ids = ids.contiguous()
         pts32, q32 = pts.detach().float().contiguous(), query.detach().float().contiguous()
         wx32 = wx.detach().float().contiguous()
         nq, c = q32.shape[0], table.shape[1]
         h1 = torch.empty((nq * k, c), device=table.device, dtype=table.dtype)
-        _lib.check(L.pps_head_input_fwd(table.data_ptr(), ids.data_ptr(), pts32.data_ptr(), q32.data_ptr(), nq, k, c, _code(table.dtype), wx32.data_ptr(),
-                                        h1.data_ptr(), _stream()), 'pps_head_input_fwd')
+        _lib.call('pps_head_input_fwd', table, ids, pts32, q32, nq, k, c, _code(table.dtype), wx32, h1)
         ctx.save_for_backward(ids, pts32, q32)
         ctx.meta = (table.shape[0], k, c, wx.dtype, wx.shape, table.dtype)
         return h1
@@ -173,14 +161,12 @@ class _HeadInput(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             order, offsets = csr(ids, n)
             dt32 = torch.empty((n, c), device=dh1.device, dtype=torch.float32)
-            _lib.check(L.pps_segment_sum_rows_16(dh1.data_ptr(), order.data_ptr(), offsets.data_ptr(), n, c, _code(dt), dt32.data_ptr(), _stream()),
-                       'pps_segment_sum_rows_16')
+            _lib.call('pps_segment_sum_rows_16', dh1, order, offsets, n, c, _code(dt), dt32)
             dtable = dt32.to(dt)
         if ctx.needs_input_grad[5]:
             dwx = torch.empty((c, 3), device=dh1.device, dtype=torch.float32)
             ws = torch.empty((L.pps_head_input_ws_bytes(c),), device=dh1.device, dtype=torch.uint8)
-            _lib.check(L.pps_head_input_dwx(dh1.data_ptr(), ids.data_ptr(), pts32.data_ptr(), q32.data_ptr(), q32.shape[0], k, c, _code(dt), dwx.data_ptr(),
-                                            ws.data_ptr(), _stream()), 'pps_head_input_dwx')
+            _lib.call('pps_head_input_dwx', dh1, ids, pts32, q32, q32.shape[0], k, c, _code(dt), dwx, ws)
             dwx = dwx.reshape(wshape).to(wdt)
         return dtable, None, None, None, None, dwx
 
@@ -200,7 +186,7 @@ class _NeighbourMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, idx):
-        _need_cuda(x, idx)
+        _lib.need_device('train_ops', x, idx)
         if x.dtype not in LOW:
             x = x.float()
         x = x.contiguous()
@@ -210,11 +196,9 @@ class _NeighbourMax(torch.autograd.Function):
         out = torch.empty((m, c), device=x.device, dtype=x.dtype)
         arg = torch.empty((m, c), device=x.device, dtype=torch.int32)
         if x.dtype in LOW:
-            _lib.check(_lib.lib().pps_gather_max_arg_16(x.data_ptr(), idx.data_ptr(), m, k, c, _code(x.dtype), out.data_ptr(), arg.data_ptr(),
-                                                        _stream()), 'pps_gather_max_arg_16')
+            _lib.call('pps_gather_max_arg_16', x, idx, m, k, c, _code(x.dtype), out, arg)
         else:
-            _lib.check(_lib.lib().pps_gather_max_arg_f32(x.data_ptr(), idx.data_ptr(), m, k, c, out.data_ptr(), arg.data_ptr(), _stream()),
-                       'pps_gather_max_arg_f32')
+            _lib.call('pps_gather_max_arg_f32', x, idx, m, k, c, out, arg)
         ctx.save_for_backward(idx, arg)
         ctx.n = x.shape[0]
         ctx.dtype = x.dtype
@@ -228,11 +212,9 @@ class _NeighbourMax(torch.autograd.Function):
         c = dout.shape[1]
         dx = torch.empty((ctx.n, c), device=dout.device, dtype=ctx.dtype)
         if ctx.dtype in LOW:
-            _lib.check(_lib.lib().pps_gather_max_bwd_16(dout.data_ptr(), arg.data_ptr(), order.data_ptr(), offsets.data_ptr(), ctx.n,
-                                                        idx.shape[1], c, _code(ctx.dtype), dx.data_ptr(), _stream()), 'pps_gather_max_bwd_16')
+            _lib.call('pps_gather_max_bwd_16', dout, arg, order, offsets, ctx.n, idx.shape[1], c, _code(ctx.dtype), dx)
         else:
-            _lib.check(_lib.lib().pps_gather_max_bwd_f32(dout.data_ptr(), arg.data_ptr(), order.data_ptr(), offsets.data_ptr(), ctx.n,
-                                                         idx.shape[1], c, dx.data_ptr(), _stream()), 'pps_gather_max_bwd_f32')
+            _lib.call('pps_gather_max_bwd_f32', dout, arg, order, offsets, ctx.n, idx.shape[1], c, dx)
         return dx, None
 
 
@@ -242,7 +224,7 @@ class _NeighbourContract(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, idx, g):
-        _need_cuda(x, idx, g)
+        _lib.need_device('train_ops', x, idx, g)
         m, k = idx.shape
         c = x.shape[1]
         low = x.dtype in LOW and bool(_lib.lib().pps_neighbour_contract_16_supported(k, c))
@@ -252,8 +234,7 @@ class _NeighbourContract(torch.autograd.Function):
         if g.shape != (m, k, 16):
             raise ValueError('neighbour_contract: g must be [m, k, 16], got {}'.format(tuple(g.shape)))
         out = torch.empty((m, c * 16), device=x.device, dtype=x.dtype)
-        _lib.check(_lib.lib().pps_neighbour_contract_fwd(x.data_ptr(), idx.data_ptr(), g.data_ptr(), m, k, c, _code(x.dtype) if low else 0,
-                                                         out.data_ptr(), _stream()), 'pps_neighbour_contract_fwd')
+        _lib.call('pps_neighbour_contract_fwd', x, idx, g, m, k, c, _code(x.dtype) if low else 0, out)
         ctx.save_for_backward(x, idx, g)
         ctx.low = low
         return out
@@ -268,15 +249,12 @@ class _NeighbourContract(torch.autograd.Function):
         dxg = torch.empty((m * k, c), device=x.device, dtype=torch.float32) if need_x else None
         dg = torch.empty((m, k, 16), device=x.device, dtype=torch.float32) if need_g else None
         if need_x or need_g:
-            _lib.check(_lib.lib().pps_neighbour_contract_bwd(x.data_ptr(), idx.data_ptr(), g.data_ptr(), dout.data_ptr(), m, k, c,
-                                                             _code(x.dtype) if ctx.low else 0, dxg.data_ptr() if need_x else None,
-                                                             dg.data_ptr() if need_g else None, _stream()), 'pps_neighbour_contract_bwd')
+            _lib.call('pps_neighbour_contract_bwd', x, idx, g, dout, m, k, c, _code(x.dtype) if ctx.low else 0, dxg if need_x else None, dg if need_g else None)
         dx = None
         if need_x:
             order, offsets = csr(idx.view(-1), n)
             dx = torch.empty((n, c), device=x.device, dtype=torch.float32)
-            _lib.check(_lib.lib().pps_segment_sum_rows_f32(dxg.data_ptr(), order.data_ptr(), offsets.data_ptr(), n, c, dx.data_ptr(),
-                                                           _stream()), 'pps_segment_sum_rows_f32')
+            _lib.call('pps_segment_sum_rows_f32', dxg, order, offsets, n, c, dx)
         return dx, None, dg
 
 
@@ -287,7 +265,7 @@ class _FkaGeometry(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
     def forward(ctx, geo, pts, sup, idx, b, m, momentum, owned=False):
-        _need_cuda(geo, pts, sup, idx)
+        _lib.need_device('train_ops', geo, pts, sup, idx)
         pts, sup, idx = pts.contiguous(), sup.contiguous(), idx.contiguous()
         k = idx.shape[1]
         if geo.numel() != GEO_FLOATS or idx.shape[0] != b * m or sup.shape[0] != b * m:
@@ -297,9 +275,7 @@ class _FkaGeometry(torch.autograd.Function):
         g = torch.empty((b * m, k, 16), device=pts.device, dtype=torch.float32)
         stat = torch.empty((2, b, 32), device=pts.device, dtype=torch.float32)
         ws = torch.empty((_lib.lib().pps_fka_train_ws_bytes(b, m, k),), device=pts.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_fka_geometry_fwd_f32(pts.data_ptr(), sup.data_ptr(), idx.data_ptr(), b, m, k, geo_w.data_ptr(),
-                                                       float(momentum), g.data_ptr(), stat.data_ptr(), ws.data_ptr(), _stream()),
-                   'pps_fka_geometry_fwd_f32')
+        _lib.call('pps_fka_geometry_fwd_f32', pts, sup, idx, b, m, k, geo_w, float(momentum), g, stat, ws)
         ctx.save_for_backward(pts, sup, idx, geo_w, stat)
         ctx.dims = (b, m, k)
         radius = geo_w[0:1]                                     # (a view: the caller copies it into the layer's buffer)
@@ -317,9 +293,7 @@ class _FkaGeometry(torch.autograd.Function):
         dg = dg.contiguous().float()
         dgeo = torch.empty((GEO_FLOATS,), device=dg.device, dtype=torch.float32)
         ws = torch.empty((_lib.lib().pps_fka_train_ws_bytes(b, m, k),), device=dg.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_fka_geometry_bwd_f32(pts.data_ptr(), sup.data_ptr(), idx.data_ptr(), b, m, k, geo_w.data_ptr(),
-                                                       stat.data_ptr(), dg.data_ptr(), dgeo.data_ptr(), ws.data_ptr(), _stream()),
-                   'pps_fka_geometry_bwd_f32')
+        _lib.call('pps_fka_geometry_bwd_f32', pts, sup, idx, b, m, k, geo_w, stat, dg, dgeo, ws)
         return dgeo, None, None, None, None, None, None, None
 
 
@@ -334,7 +308,7 @@ def fka_geometry(geo, pts, sup, idx, b, m, momentum, owned=False):
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu):
-        _need_cuda(x, weight, bias)
+        _lib.need_device('train_ops', x, weight, bias)
         if x.dtype not in (torch.float32,) + LOW:
             x = x.float()
         x = x.contiguous()
@@ -346,10 +320,8 @@ class _BnAct(torch.autograd.Function):
         if nbytes == 0 and rows > 0:
             raise ValueError('bn_act: unsupported shape [{}, {}]'.format(rows, c))
         ws = torch.empty((max(nbytes, 1),), device=x.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_bn_train_fwd(x.data_ptr(), rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32.data_ptr(), b32.data_ptr(),
-                                               running_mean.data_ptr() if running_mean is not None else None,
-                                               running_var.data_ptr() if running_var is not None else None, float(momentum), float(eps),
-                                               int(bool(relu)), y.data_ptr(), save.data_ptr(), ws.data_ptr(), _stream()), 'pps_bn_train_fwd')
+        _lib.call('pps_bn_train_fwd', x, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, running_mean, running_var, float(momentum), float(eps),
+                  int(bool(relu)), y, save, ws)
         ctx.save_for_backward(x, w32, b32, save)
         ctx.relu = bool(relu)
         ctx.dtypes = (weight.dtype, bias.dtype)
@@ -364,9 +336,7 @@ class _BnAct(torch.autograd.Function):
         dgamma = torch.empty((c,), device=x.device, dtype=torch.float32)
         dbeta = torch.empty((c,), device=x.device, dtype=torch.float32)
         ws = torch.empty((max(_lib.lib().pps_bn_train_ws_bytes(rows, c), 1),), device=x.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_bn_train_bwd(x.data_ptr(), dy.data_ptr(), rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32.data_ptr(),
-                                               b32.data_ptr(), save.data_ptr(), int(ctx.relu), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                               ws.data_ptr(), _stream()), 'pps_bn_train_bwd')
+        _lib.call('pps_bn_train_bwd', x, dy, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, save, int(ctx.relu), dx, dgamma, dbeta, ws)
         return dx, dgamma.to(ctx.dtypes[0]), dbeta.to(ctx.dtypes[1]), None, None, None, None, None
 
 
@@ -375,7 +345,7 @@ class _BnAddRelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps):
-        _need_cuda(x, res, weight, bias)
+        _lib.need_device('train_ops', x, res, weight, bias)
         if x.dtype not in (torch.float32,) + LOW:
             x = x.float()
         x = x.contiguous()
@@ -388,10 +358,8 @@ class _BnAddRelu(torch.autograd.Function):
         if nbytes == 0 and rows > 0:
             raise ValueError('bn_add_relu: unsupported shape [{}, {}]'.format(rows, c))
         ws = torch.empty((max(nbytes, 1),), device=x.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_bn_add_relu_fwd(x.data_ptr(), res.data_ptr(), rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32.data_ptr(), b32.data_ptr(),
-                                                  running_mean.data_ptr() if running_mean is not None else None,
-                                                  running_var.data_ptr() if running_var is not None else None, float(momentum), float(eps),
-                                                  y.data_ptr(), save.data_ptr(), ws.data_ptr(), _stream()), 'pps_bn_add_relu_fwd')
+        _lib.call('pps_bn_add_relu_fwd', x, res, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, running_mean, running_var, float(momentum),
+                  float(eps), y, save, ws)
         ctx.save_for_backward(x, res, w32, b32, save)
         ctx.dtypes = (weight.dtype, bias.dtype)
         return y
@@ -405,9 +373,7 @@ class _BnAddRelu(torch.autograd.Function):
         dgamma = torch.empty((c,), device=x.device, dtype=torch.float32)
         dbeta = torch.empty((c,), device=x.device, dtype=torch.float32)
         ws = torch.empty((max(_lib.lib().pps_bn_train_ws_bytes(rows, c), 1),), device=x.device, dtype=torch.uint8)
-        _lib.check(_lib.lib().pps_bn_add_relu_bwd(x.data_ptr(), res.data_ptr(), dy.data_ptr(), rows, c, _code(x.dtype) if x.dtype in LOW else 0,
-                                                  w32.data_ptr(), b32.data_ptr(), save.data_ptr(), dx.data_ptr(), dres.data_ptr(), dgamma.data_ptr(),
-                                                  dbeta.data_ptr(), ws.data_ptr(), _stream()), 'pps_bn_add_relu_bwd')
+        _lib.call('pps_bn_add_relu_bwd', x, res, dy, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, save, dx, dres, dgamma, dbeta, ws)
         return dx, dres, dgamma.to(ctx.dtypes[0]), dbeta.to(ctx.dtypes[1]), None, None, None, None
 
 
@@ -431,8 +397,7 @@ def col_sum(x):
         return None
     out = torch.empty((c,), device=x.device, dtype=torch.float32)
     ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
-    _lib.check(_lib.lib().pps_col_sum_strided(x.data_ptr(), rows, c, ld, _code(x.dtype) if x.dtype in LOW else 0, out.data_ptr(), ws.data_ptr(),
-                                              _stream()), 'pps_col_sum_strided')
+    _lib.call('pps_col_sum_strided', x, rows, c, ld, _code(x.dtype) if x.dtype in LOW else 0, out, ws)
     return out
 
 
@@ -495,7 +460,7 @@ def gemm_supported(x, k):
 
 def gemm_nt(x, w, bias=None, out_f32=False):
     """x [M, K] @ w [N, K]^T (+ bias [N] fp32) -> [M, N] in x's 16-bit type (or fp32): pps_gemm_nt_16.  No autograd (called from autograd functions)."""
-    _need_cuda(x, w)
+    _lib.need_device('train_ops', x, w)
     assert x.dim() == 2 and w.dim() == 2 and x.shape[1] == w.shape[1] and x.dtype == w.dtype and x.dtype in LOW
     if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
         x = x.contiguous()
@@ -505,14 +470,13 @@ def gemm_nt(x, w, bias=None, out_f32=False):
     n = w.shape[0]
     y = torch.empty((m, n), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
     b32 = None if bias is None else bias.detach().float().contiguous()
-    _lib.check(_lib.lib().pps_gemm_nt_16(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), None if b32 is None else b32.data_ptr(), y.data_ptr(), n,
-                                         m, n, k, _code(x.dtype), int(bool(out_f32)), _stream()), 'pps_gemm_nt_16')
+    _lib.call('pps_gemm_nt_16', x, x.stride(0), w, w.stride(0), b32, y, n, m, n, k, _code(x.dtype), int(bool(out_f32)))
     return y
 
 
 def gemm_tn(g, x):
     """g [M, N]^T @ x [M, K] -> fp32 [N, K] (the weight gradient of a row layer: contraction over the rows): pps_gemm_tn_16.  N, K multiples of 8."""
-    _need_cuda(g, x)
+    _lib.need_device('train_ops', g, x)
     assert g.dim() == 2 and x.dim() == 2 and g.shape[0] == x.shape[0] and g.dtype == x.dtype and g.dtype in LOW
     if g.stride(1) != 1 or g.stride(0) % 8 or g.data_ptr() % 16:
         g = g.contiguous()
@@ -523,8 +487,7 @@ def gemm_tn(g, x):
     L = _lib.lib()
     dw = torch.empty((n, k), device=g.device, dtype=torch.float32)
     ws = torch.empty((max(int(L.pps_gemm_tn_ws_bytes(m, n, k)), 16),), device=g.device, dtype=torch.uint8)
-    _lib.check(L.pps_gemm_tn_16(g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), m, n, k, _code(g.dtype), dw.data_ptr(), ws.data_ptr(), _stream()),
-               'pps_gemm_tn_16')
+    _lib.call('pps_gemm_tn_16', g, g.stride(0), x, x.stride(0), m, n, k, _code(g.dtype), dw, ws)
     return dw
 
 
@@ -534,15 +497,14 @@ class _AttnPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qy, h, relu_h=False):
-        _need_cuda(qy, h)
+        _lib.need_device('train_ops', qy, h)
         ctx.relu_h = int(bool(relu_h))
         dt = h.dtype if h.dtype in (torch.float32,) + LOW else torch.float32
         qy, h = qy.to(dt).contiguous(), h.to(dt).contiguous()
         q, k, heads = qy.shape
         c = h.shape[2]
         pooled = torch.empty((q, c), device=h.device, dtype=dt)
-        _lib.check(_lib.lib().pps_attn_pool_fwd(qy.data_ptr(), h.data_ptr(), q, k, heads, c, _code(dt) if dt in LOW else 0, ctx.relu_h, pooled.data_ptr(), _stream()),
-                   'pps_attn_pool_fwd')
+        _lib.call('pps_attn_pool_fwd', qy, h, q, k, heads, c, _code(dt) if dt in LOW else 0, ctx.relu_h, pooled)
         ctx.save_for_backward(qy, h)
         return pooled
 
@@ -553,8 +515,7 @@ class _AttnPool(torch.autograd.Function):
         c = h.shape[2]
         dpooled = dpooled.to(h.dtype).contiguous()
         dqy, dh = torch.empty_like(qy), torch.empty_like(h)
-        _lib.check(_lib.lib().pps_attn_pool_bwd(qy.data_ptr(), h.data_ptr(), dpooled.data_ptr(), q, k, heads, c, _code(h.dtype) if h.dtype in LOW else 0,
-                                                ctx.relu_h, dqy.data_ptr(), dh.data_ptr(), _stream()), 'pps_attn_pool_bwd')
+        _lib.call('pps_attn_pool_bwd', qy, h, dpooled, q, k, heads, c, _code(h.dtype) if h.dtype in LOW else 0, ctx.relu_h, dqy, dh)
         return dqy, dh, None
 
 
@@ -579,7 +540,7 @@ class _RowsLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps):
-        _need_cuda(x, w)
+        _lib.need_device('train_ops', x, w)
         L = _lib.lib()
         x = _low(x)
         rows, cin = x.shape
@@ -594,11 +555,9 @@ class _RowsLayer(torch.autograd.Function):
         out_affine = torch.empty((2, cout), device=x.device, dtype=torch.float32) if bn else None
         save = torch.empty((2, cout), device=x.device, dtype=torch.float32) if bn else None
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=x.device, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_fwd(x.data_ptr(), rows, cin, _code(x.dtype), ptr(aff), None if aff is None else aff.data_ptr() + 4 * cin, int(bool(in_relu)),
-                                        w32.data_ptr(), ptr(b32), cout, y.data_ptr(), ptr(g32), ptr(be32), ptr(running_mean), ptr(running_var),
-                                        float(momentum or 0.0), float(eps or 0.0), ptr(out_affine), ptr(save), ws.data_ptr(), _stream()),
-                   'pps_rows_layer_fwd')
+        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
+                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine,
+                  save, ws)
         ctx.save_for_backward(x, aff, w32, g32, save, y)
         ctx.meta = (bool(in_relu), b is not None, bn, w.dtype, None if b is None else b.dtype)
         return y, out_affine
@@ -622,11 +581,8 @@ class _RowsLayer(torch.autograd.Function):
         dgamma = torch.empty((cout,), device=dev, dtype=torch.float32) if bn else None
         dbeta = torch.empty((cout,), device=dev, dtype=torch.float32) if bn else None
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), rows, cin, cout, _code(x.dtype), ptr(aff),
-                                        None if aff is None else aff.data_ptr() + 4 * cin, int(in_relu), w32.data_ptr(), ptr(g32), ptr(save),
-                                        ptr(g_affine) if bn else None, ptr(dx), None, ptr(d_in), dw.data_ptr(), ptr(db), ptr(dgamma), ptr(dbeta),
-                                        ws.data_ptr(), _stream()), 'pps_rows_layer_bwd')
+        _lib.call('pps_rows_layer_bwd', x, y, gy, rows, cin, cout, _code(x.dtype), aff, _row1(aff, cin), int(in_relu),
+                  w32, g32, save, g_affine if bn else None, dx, None, d_in, dw, db, dgamma, dbeta, ws)
         return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None)
 
 
@@ -638,7 +594,7 @@ class _RowsLayerMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps, relu, groups, p):
-        _need_cuda(x, w)
+        _lib.need_device('train_ops', x, w)
         L = _lib.lib()
         x = _low(x)
         rows, cin = x.shape
@@ -652,15 +608,11 @@ class _RowsLayerMax(torch.autograd.Function):
         out_affine = torch.empty((2, cout), device=dev, dtype=torch.float32)
         save = torch.empty((2, cout), device=dev, dtype=torch.float32)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_fwd(x.data_ptr(), rows, cin, _code(x.dtype), ptr(aff), None if aff is None else aff.data_ptr() + 4 * cin, int(bool(in_relu)),
-                                        w32.data_ptr(), ptr(b32), cout, y.data_ptr(), g32.data_ptr(), be32.data_ptr(), ptr(running_mean), ptr(running_var),
-                                        float(momentum or 0.0), float(eps or 0.0), out_affine.data_ptr(), save.data_ptr(), ws.data_ptr(), _stream()),
-                   'pps_rows_layer_fwd')
+        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
+                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine, save, ws)
         mx, mn = torch.empty((groups, cout), device=dev), torch.empty((groups, cout), device=dev)
         amx, amn = torch.empty((groups, cout), device=dev, dtype=torch.int32), torch.empty((groups, cout), device=dev, dtype=torch.int32)
-        _lib.check(L.pps_rows_extrema_16(y.data_ptr(), groups, p, cout, _code(y.dtype), mx.data_ptr(), mn.data_ptr(), amx.data_ptr(), amn.data_ptr(), _stream()),
-                   'pps_rows_extrema_16')
+        _lib.call('pps_rows_extrema_16', y, groups, p, cout, _code(y.dtype), mx, mn, amx, amn)
         scale, shift = out_affine[0], out_affine[1]
         up = scale >= 0
         ext, arg = torch.where(up, mx, mn), torch.where(up, amx, amn).to(torch.uint8)
@@ -693,11 +645,8 @@ class _RowsLayerMax(torch.autograd.Function):
         db = torch.empty((cout,), device=dev, dtype=torch.float32) if has_b else None
         dgamma, dbeta = torch.empty((cout,), device=dev, dtype=torch.float32), torch.empty((cout,), device=dev, dtype=torch.float32)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_bwd_pooled(x.data_ptr(), y.data_ptr(), gval.data_ptr(), arg.data_ptr(), p, rows, cin, cout, _code(x.dtype), ptr(aff),
-                                               None if aff is None else aff.data_ptr() + 4 * cin, int(in_relu), w32.data_ptr(), g32.data_ptr(), save.data_ptr(),
-                                               g_affine.data_ptr(), ptr(dx), ptr(d_in), dw.data_ptr(), ptr(db), dgamma.data_ptr(), dbeta.data_ptr(),
-                                               ws.data_ptr(), _stream()), 'pps_rows_layer_bwd_pooled')
+        _lib.call('pps_rows_layer_bwd_pooled', x, y, gval, arg, p, rows, cin, cout, _code(x.dtype), aff, _row1(aff, cin),
+                  int(in_relu), w32, g32, save, g_affine, dx, d_in, dw, db, dgamma, dbeta, ws)
         return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None, None, None, None)
 
 
@@ -706,7 +655,7 @@ class _Rows3Layer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, momentum, eps):
-        _need_cuda(x, w)
+        _lib.need_device('train_ops', x, w)
         L = _lib.lib()
         x = x.detach().float().contiguous()
         rows = x.shape[0]
@@ -717,9 +666,8 @@ class _Rows3Layer(torch.autograd.Function):
         y = torch.empty((rows, 64), device=x.device, dtype=dt if dt in LOW else torch.bfloat16)
         aff, save = torch.empty((2, 64), device=x.device), torch.empty((2, 64), device=x.device)
         ws = torch.empty((L.pps_rows3_ws_bytes(),), device=x.device, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows3_fwd(x.data_ptr(), rows, w32.data_ptr(), ptr(b32), _code(y.dtype), y.data_ptr(), g32.data_ptr(), be32.data_ptr(), ptr(running_mean),
-                                   ptr(running_var), float(momentum), float(eps), aff.data_ptr(), save.data_ptr(), ws.data_ptr(), _stream()), 'pps_rows3_fwd')
+        _lib.call('pps_rows3_fwd', x, rows, w32, b32, _code(y.dtype), y, g32, be32, running_mean, running_var, float(momentum), float(eps), aff,
+                  save, ws)
         ctx.save_for_backward(x, y, g32, save)
         ctx.meta = (b is not None, w.dtype, None if b is None else b.dtype)
         return y, aff
@@ -736,8 +684,7 @@ class _Rows3Layer(torch.autograd.Function):
         db = torch.empty((64,), device=dev) if has_b else None
         dgamma, dbeta = torch.empty((64,), device=dev), torch.empty((64,), device=dev)
         ws = torch.empty((L.pps_rows3_ws_bytes(),), device=dev, dtype=torch.uint8)
-        _lib.check(L.pps_rows3_bwd(x.data_ptr(), y.data_ptr(), gy.data_ptr(), x.shape[0], _code(y.dtype), g32.data_ptr(), save.data_ptr(), g_aff.data_ptr(), dw.data_ptr(),
-                                   None if db is None else db.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), _stream()), 'pps_rows3_bwd')
+        _lib.call('pps_rows3_bwd', x, y, gy, x.shape[0], _code(y.dtype), g32, save, g_aff, dw, db, dgamma, dbeta, ws)
         return None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None
 
 
@@ -753,15 +700,14 @@ class _PatchTransform(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, affine, relu, t, p):
-        _need_cuda(x, t)
-        L = _lib.lib()
+        _lib.need_device('train_ops', x, t)
         x = _low(x)
         t16 = t.to(x.dtype).contiguous()
         nq = t16.shape[0]
         aff = None if affine is None else affine.detach().float().contiguous()
         out = torch.empty_like(x)
-        _lib.check(L.pps_patch_transform_fwd(x.data_ptr(), None if aff is None else aff.data_ptr(), None if aff is None else aff.data_ptr() + 256,
-                                             int(bool(relu)), t16.data_ptr(), 1, nq, p, _code(x.dtype), out.data_ptr(), _stream()), 'pps_patch_transform_fwd')
+        _lib.call('pps_patch_transform_fwd', x, aff, _row1(aff, 64), int(bool(relu)), t16, 1,
+                  nq, p, _code(x.dtype), out)
         ctx.save_for_backward(x, aff, t16)
         ctx.meta = (bool(relu), p, t.dtype)
         return out
@@ -777,9 +723,8 @@ class _PatchTransform(torch.autograd.Function):
         need_daff = aff is not None and ctx.needs_input_grad[1]
         daff = torch.empty((2, 64), device=x.device) if need_daff else None
         ws = torch.empty((L.pps_patch_transform_ws_bytes(),), device=x.device, dtype=torch.uint8)
-        _lib.check(L.pps_patch_transform_bwd(x.data_ptr(), None if aff is None else aff.data_ptr(), None if aff is None else aff.data_ptr() + 256,
-                                             int(relu), t16.data_ptr(), 1, g.data_ptr(), nq, p, _code(x.dtype), dx.data_ptr(), dt.data_ptr(),
-                                             None if daff is None else daff.data_ptr(), ws.data_ptr(), _stream()), 'pps_patch_transform_bwd')
+        _lib.call('pps_patch_transform_bwd', x, aff, _row1(aff, 64), int(relu), t16, 1, g,
+                  nq, p, _code(x.dtype), dx, dt, daff, ws)
         return dx, daff, None, dt.to(tdt), None
 
 
@@ -801,12 +746,12 @@ class _PatchAttn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, v):
-        _need_cuda(h, v)
+        _lib.need_device('train_ops', h, v)
         h = _low(h)
         v32 = v.detach().float().contiguous()
         q, k, c = h.shape
         pooled = torch.empty((q, c), device=h.device, dtype=torch.float32)
-        _lib.check(_lib.lib().pps_patch_attn_fwd(h.data_ptr(), v32.data_ptr(), q, k, c, _code(h.dtype), pooled.data_ptr(), _stream()), 'pps_patch_attn_fwd')
+        _lib.call('pps_patch_attn_fwd', h, v32, q, k, c, _code(h.dtype), pooled)
         ctx.save_for_backward(h, v32)
         ctx.vdtype = v.dtype
         return pooled
@@ -819,8 +764,7 @@ class _PatchAttn(torch.autograd.Function):
         dpooled = dpooled.float().contiguous()
         dh = torch.empty_like(h)
         part = torch.empty((L.pps_patch_attn_partials(q), c), device=h.device, dtype=torch.float32)
-        _lib.check(L.pps_patch_attn_bwd(h.data_ptr(), v32.data_ptr(), dpooled.data_ptr(), q, k, c, _code(h.dtype), dh.data_ptr(), part.data_ptr(), _stream()),
-                   'pps_patch_attn_bwd')
+        _lib.call('pps_patch_attn_bwd', h, v32, dpooled, q, k, c, _code(h.dtype), dh, part)
         return dh, sum_rows(part).to(ctx.vdtype)
 
 
@@ -838,14 +782,13 @@ class _ActMax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw, affine, relu, groups, p):
-        _need_cuda(raw)
+        _lib.need_device('train_ops', raw)
         raw = _low(raw)
         c = raw.shape[1]
         dev = raw.device
         mx, mn = torch.empty((groups, c), device=dev), torch.empty((groups, c), device=dev)
         amx, amn = torch.empty((groups, c), device=dev, dtype=torch.int32), torch.empty((groups, c), device=dev, dtype=torch.int32)
-        _lib.check(_lib.lib().pps_rows_extrema_16(raw.data_ptr(), groups, p, c, _code(raw.dtype), mx.data_ptr(), mn.data_ptr(), amx.data_ptr(), amn.data_ptr(),
-                                                  _stream()), 'pps_rows_extrema_16')
+        _lib.call('pps_rows_extrema_16', raw, groups, p, c, _code(raw.dtype), mx, mn, amx, amn)
         if affine is None:
             ext, arg, out = mx, amx, mx
             scale = None
@@ -916,7 +859,7 @@ class _RowsLayerPatchAttn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps, wq, groups, p):
-        _need_cuda(x, w, wq)
+        _lib.need_device('train_ops', x, w, wq)
         L = _lib.lib()
         x = _low(x)
         rows, cin = x.shape
@@ -930,15 +873,12 @@ class _RowsLayerPatchAttn(torch.autograd.Function):
         out_affine = torch.empty((2, cout), device=dev, dtype=torch.float32)
         save = torch.empty((2, cout), device=dev, dtype=torch.float32)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_fwd(x.data_ptr(), rows, cin, _code(x.dtype), ptr(aff), None if aff is None else aff.data_ptr() + 4 * cin, int(bool(in_relu)),
-                                        w32.data_ptr(), ptr(b32), cout, y.data_ptr(), g32.data_ptr(), be32.data_ptr(), ptr(running_mean), ptr(running_var),
-                                        float(momentum or 0.0), float(eps or 0.0), out_affine.data_ptr(), save.data_ptr(), ws.data_ptr(), _stream()),
-                   'pps_rows_layer_fwd')
+        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
+                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine, save, ws)
         wq32 = wq.detach().float().reshape(-1).contiguous()
         v = wq32 * out_affine[0]                                                     # the logit's weights on the raw output
         pooled = torch.empty((groups, cout), device=dev, dtype=torch.float32)
-        _lib.check(L.pps_patch_attn_fwd(y.data_ptr(), v.data_ptr(), groups, p, cout, _code(y.dtype), pooled.data_ptr(), _stream()), 'pps_patch_attn_fwd')
+        _lib.call('pps_patch_attn_fwd', y, v, groups, p, cout, _code(y.dtype), pooled)
         ctx.save_for_backward(x, aff, w32, g32, save, y, v, wq32, out_affine)
         ctx.meta = (bool(in_relu), b is not None, w.dtype, None if b is None else b.dtype, wq.dtype, tuple(wq.shape), groups, p)
         return pooled, out_affine
@@ -951,13 +891,11 @@ class _RowsLayerPatchAttn(torch.autograd.Function):
         rows, cin = x.shape
         cout = w32.shape[0]
         dev = x.device
-        st = _stream()
         f32e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
         dpooled = torch.zeros((groups, cout), device=dev, dtype=torch.float32) if dpooled is None else dpooled.float().contiguous()
         a, dl = f32e(rows), f32e(rows)
         part = f32e(L.pps_patch_attn_partials(groups), cout)
-        _lib.check(L.pps_patch_attn_bwd_weights(y.data_ptr(), v.data_ptr(), dpooled.data_ptr(), groups, p, cout, _code(y.dtype), a.data_ptr(), dl.data_ptr(),
-                                                part.data_ptr(), st), 'pps_patch_attn_bwd_weights')
+        _lib.call('pps_patch_attn_bwd_weights', y, v, dpooled, groups, p, cout, _code(y.dtype), a, dl, part)
         dv = sum_rows(part)
         # v = w_q * scale: d w_q = dv * scale, and the scale of the layer's own BatchNorm gets dv * w_q on top of what its consumers hand back
         dwq = (dv * out_affine[0]).reshape(qshape).to(qdt)
@@ -970,11 +908,8 @@ class _RowsLayerPatchAttn(torch.autograd.Function):
         db = f32e(cout) if has_b else None
         dgamma, dbeta = f32e(cout), f32e(cout)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_bwd_rank2(x.data_ptr(), y.data_ptr(), a.data_ptr(), dl.data_ptr(), dpooled.data_ptr(), v.data_ptr(), p, rows, cin, cout,
-                                              _code(x.dtype), ptr(aff), None if aff is None else aff.data_ptr() + 4 * cin, int(in_relu), w32.data_ptr(),
-                                              g32.data_ptr(), save.data_ptr(), g_affine.data_ptr(), ptr(dx), ptr(d_in), dw.data_ptr(), ptr(db),
-                                              dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), st), 'pps_rows_layer_bwd_rank2')
+        _lib.call('pps_rows_layer_bwd_rank2', x, y, a, dl, dpooled, v, p, rows, cin, cout, _code(x.dtype), aff,
+                  _row1(aff, cin), int(in_relu), w32, g32, save, g_affine, dx, d_in, dw, db, dgamma, dbeta, ws)
         return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None, dwq, None, None)
 
 
@@ -989,7 +924,7 @@ def rows_layer_patch_attn(act, w, b, bn, wq, groups, p):
                                      groups, p)
 
 
-def _query_attn_bwd(L, y3, qy, dpooled, wq32, k, dwq, dbq, ws, st):
+def _query_attn_bwd(y3, qy, dpooled, wq32, k, dwq, dbq, ws):
     """Backward of (fc_query, attention pooling) on the stored raw output y3 of fc3 -> d y3 [Q*k, 256]; dwq / dbq are filled.  y3 has two
     consumers.  The pooling's gradient relu'(y3) * a[q, j] * dpooled[q, c] is one multiply per element, so it is NOT stored: pps_attn_pool_bwd_weights
     returns a [Q, k] and the input-gradient kernel of fc_query rebuilds the product where it adds the two gradients (pps_rows_layer_bwd_attn) --
@@ -998,19 +933,14 @@ def _query_attn_bwd(L, y3, qy, dpooled, wq32, k, dwq, dbq, ws, st):
     rows, c = y3.shape
     heads = wq32.shape[0]
     code = _code(y3.dtype)
-    ptr = lambda t: None if t is None else t.data_ptr()
     dqy, dy3 = torch.empty_like(qy), torch.empty_like(y3)
     if os.environ.get('PPS_ATTN_GRAD', 'rebuilt') != 'stored' and rows * k < 1 << 32:
         a = torch.empty((rows,), device=y3.device, dtype=torch.float32)
-        _lib.check(L.pps_attn_pool_bwd_weights(qy.data_ptr(), y3.data_ptr(), dpooled.data_ptr(), rows // k, k, heads, c, code, 1, dqy.data_ptr(), a.data_ptr(),
-                                               st), 'pps_attn_pool_bwd_weights')
-        _lib.check(L.pps_rows_layer_bwd_attn(y3.data_ptr(), dqy.data_ptr(), rows, c, heads, code, wq32.data_ptr(), a.data_ptr(), dpooled.data_ptr(), k,
-                                             dy3.data_ptr(), dwq.data_ptr(), ptr(dbq), ws.data_ptr(), st), 'pps_rows_layer_bwd_attn')
+        _lib.call('pps_attn_pool_bwd_weights', qy, y3, dpooled, rows // k, k, heads, c, code, 1, dqy, a)
+        _lib.call('pps_rows_layer_bwd_attn', y3, dqy, rows, c, heads, code, wq32, a, dpooled, k, dy3, dwq, dbq, ws)
         return dy3
-    _lib.check(L.pps_attn_pool_bwd(qy.data_ptr(), y3.data_ptr(), dpooled.data_ptr(), rows // k, k, heads, c, code, 1, dqy.data_ptr(), dy3.data_ptr(), st),
-               'pps_attn_pool_bwd')
-    _lib.check(L.pps_rows_layer_bwd(y3.data_ptr(), qy.data_ptr(), dqy.data_ptr(), rows, c, heads, code, None, None, 1, wq32.data_ptr(), None, None, None,
-                                    dy3.data_ptr(), dy3.data_ptr(), None, dwq.data_ptr(), ptr(dbq), None, None, ws.data_ptr(), st), 'pps_rows_layer_bwd')
+    _lib.call('pps_attn_pool_bwd', qy, y3, dpooled, rows // k, k, heads, c, code, 1, dqy, dy3)
+    _lib.call('pps_rows_layer_bwd', y3, qy, dqy, rows, c, heads, code, None, None, 1, wq32, None, None, None, dy3, dy3, None, dwq, dbq, None, None, ws)
     return dy3
 
 
@@ -1021,7 +951,7 @@ class _QueryAttnPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y3, wq, bq, k):
-        _need_cuda(y3, wq)
+        _lib.need_device('train_ops', y3, wq)
         L = _lib.lib()
         y3 = _low(y3)
         rows, c = y3.shape
@@ -1030,11 +960,9 @@ class _QueryAttnPool(torch.autograd.Function):
         b32 = None if bq is None else bq.detach().float().contiguous()
         qy = torch.empty((rows, heads), device=y3.device, dtype=y3.dtype)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(c, heads),), device=y3.device, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_rows_layer_fwd(y3.data_ptr(), rows, c, _code(y3.dtype), None, None, 1, w32.data_ptr(), ptr(b32), heads, qy.data_ptr(),
-                                        None, None, None, None, 0.0, 0.0, None, None, ws.data_ptr(), _stream()), 'pps_rows_layer_fwd')
+        _lib.call('pps_rows_layer_fwd', y3, rows, c, _code(y3.dtype), None, None, 1, w32, b32, heads, qy, None, None, None, None, 0.0, 0.0, None, None, ws)
         pooled = torch.empty((rows // k, c), device=y3.device, dtype=y3.dtype)
-        _lib.check(L.pps_attn_pool_fwd(qy.data_ptr(), y3.data_ptr(), rows // k, k, heads, c, _code(y3.dtype), 1, pooled.data_ptr(), _stream()), 'pps_attn_pool_fwd')
+        _lib.call('pps_attn_pool_fwd', qy, y3, rows // k, k, heads, c, _code(y3.dtype), 1, pooled)
         ctx.save_for_backward(y3, w32, qy)
         ctx.meta = (k, bq is not None, wq.dtype, None if bq is None else bq.dtype)
         return pooled
@@ -1051,7 +979,7 @@ class _QueryAttnPool(torch.autograd.Function):
         dw = torch.empty((heads, c), device=dev, dtype=torch.float32)
         db = torch.empty((heads,), device=dev, dtype=torch.float32) if has_b else None
         ws = torch.empty((L.pps_rows_layer_ws_bytes(c, heads),), device=dev, dtype=torch.uint8)
-        dy3 = _query_attn_bwd(L, y3, qy, dpooled, w32, k, dw, db, ws, _stream())
+        dy3 = _query_attn_bwd(y3, qy, dpooled, w32, k, dw, db, ws)
         return dy3, dw.to(wdt), None if db is None else db.to(bdt), None
 
 
@@ -1068,7 +996,7 @@ class _HeadChain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, ids, pts, query, k, wx, w2, b2, w3, b3, wq, bq):
-        _need_cuda(table, ids, pts, query, wx, w2, w3, wq)
+        _lib.need_device('train_ops', table, ids, pts, query, wx, w2, w3, wq)
         L = _lib.lib()
         table = _low(table)
         ids = ids.contiguous()
@@ -1082,12 +1010,9 @@ class _HeadChain(torch.autograd.Function):
         h1, y2, y3 = (torch.empty((pad, c), device=dev, dtype=dt)[:rows] for _ in range(3))
         qy = torch.empty((pad, heads), device=dev, dtype=dt)[:rows]
         ws = torch.empty((L.pps_head_chain_ws_bytes(),), device=dev, dtype=torch.uint8)
-        ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(L.pps_head_chain_fwd(table.data_ptr(), ids.data_ptr(), pts32.data_ptr(), q32.data_ptr(), nq, k, _code(dt), wx32.data_ptr(), w2_32.data_ptr(),
-                                        ptr(b2_32), w3_32.data_ptr(), ptr(b3_32), wq32.data_ptr(), ptr(bq32), h1.data_ptr(), y2.data_ptr(), y3.data_ptr(),
-                                        qy.data_ptr(), ws.data_ptr(), _stream()), 'pps_head_chain_fwd')
+        _lib.call('pps_head_chain_fwd', table, ids, pts32, q32, nq, k, _code(dt), wx32, w2_32, b2_32, w3_32, b3_32, wq32, bq32, h1, y2, y3, qy, ws)
         pooled = torch.empty((nq, c), device=dev, dtype=dt)
-        _lib.check(L.pps_attn_pool_fwd(qy.data_ptr(), y3.data_ptr(), nq, k, heads, c, _code(dt), 1, pooled.data_ptr(), _stream()), 'pps_attn_pool_fwd')
+        _lib.call('pps_attn_pool_fwd', qy, y3, nq, k, heads, c, _code(dt), 1, pooled)
         ctx.save_for_backward(ids, pts32, q32, w2_32, w3_32, wq32, h1, y2, y3, qy)
         ctx.meta = (table.shape[0], k, wx.dtype, tuple(wx.shape), w2.dtype, w3.dtype, wq.dtype, None if b2 is None else b2.dtype,
                     None if b3 is None else b3.dtype, None if bq is None else bq.dtype)
@@ -1102,38 +1027,33 @@ class _HeadChain(torch.autograd.Function):
         heads = wq32.shape[0]
         dev, dt = y3.device, y3.dtype
         code = _code(dt)
-        st = _stream()
-        ptr = lambda t: None if t is None else t.data_ptr()
         dpooled = dpooled.to(dt).contiguous()
         # attention pooling + fc_query: the two gradients of y3 are summed inside fc_query's input-gradient kernel
         f32e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
         dwq, dbq = f32e(heads, c), (f32e(heads) if bqdt is not None else None)
         ws = torch.empty((L.pps_rows_layer_ws_bytes(c, c),), device=dev, dtype=torch.uint8)        # (the largest of the three layers)
-        dy3 = _query_attn_bwd(L, y3, qy, dpooled, wq32, k, dwq, dbq, ws, st)
+        dy3 = _query_attn_bwd(y3, qy, dpooled, wq32, k, dwq, dbq, ws)
         # fc3
         dy2 = torch.empty_like(y2)
         dw3, db3 = f32e(c, c), (f32e(c) if b3dt is not None else None)
-        _lib.check(L.pps_rows_layer_bwd(y2.data_ptr(), y3.data_ptr(), dy3.data_ptr(), rows, c, c, code, None, None, 1, w3_32.data_ptr(), None, None, None,
-                                        dy2.data_ptr(), None, None, dw3.data_ptr(), ptr(db3), None, None, ws.data_ptr(), st), 'pps_rows_layer_bwd')
+        _lib.call('pps_rows_layer_bwd', y2, y3, dy3, rows, c, c, code, None, None, 1, w3_32, None, None, None, dy2, None, None, dw3, db3, None, None, ws)
         del dy3
         # fc2
         dh1 = torch.empty_like(h1)
         dw2, db2 = f32e(c, c), (f32e(c) if b2dt is not None else None)
-        _lib.check(L.pps_rows_layer_bwd(h1.data_ptr(), y2.data_ptr(), dy2.data_ptr(), rows, c, c, code, None, None, 1, w2_32.data_ptr(), None, None, None,
-                                        dh1.data_ptr(), None, None, dw2.data_ptr(), ptr(db2), None, None, ws.data_ptr(), st), 'pps_rows_layer_bwd')
+        _lib.call('pps_rows_layer_bwd', h1, y2, dy2, rows, c, c, code, None, None, 1, w2_32, None, None, None, dh1, None, None, dw2, db2, None, None, ws)
         del dy2
         # head input: d table by the segmented sum of the gather, d wx
         dtable = dwx = None
         if ctx.needs_input_grad[0]:
             order, offsets = csr(ids, n)
             dt32 = f32e(n, c)
-            _lib.check(L.pps_segment_sum_rows_16(dh1.data_ptr(), order.data_ptr(), offsets.data_ptr(), n, c, code, dt32.data_ptr(), st), 'pps_segment_sum_rows_16')
+            _lib.call('pps_segment_sum_rows_16', dh1, order, offsets, n, c, code, dt32)
             dtable = dt32.to(dt)
         if ctx.needs_input_grad[5]:
             dwx = f32e(c, 3)
             ws2 = torch.empty((L.pps_head_input_ws_bytes(c),), device=dev, dtype=torch.uint8)
-            _lib.check(L.pps_head_input_dwx(dh1.data_ptr(), ids.data_ptr(), pts32.data_ptr(), q32.data_ptr(), q32.shape[0], k, c, code, dwx.data_ptr(),
-                                            ws2.data_ptr(), st), 'pps_head_input_dwx')
+            _lib.call('pps_head_input_dwx', dh1, ids, pts32, q32, q32.shape[0], k, c, code, dwx, ws2)
             dwx = dwx.reshape(wxshape).to(wxdt)
         cast = lambda t, d: None if (t is None or d is None) else t.to(d)
         return (dtable, None, None, None, None, dwx, dw2.to(w2dt), cast(db2, b2dt), dw3.to(w3dt), cast(db3, b3dt), dwq.to(wqdt), cast(dbq, bqdt))
@@ -1175,9 +1095,7 @@ def head_chain_trusted(dtype):
         h1, y2, y3 = (torch.zeros((pad, 256), device=dev, dtype=dtype) for _ in range(3))
         qy = torch.zeros((pad, 64), device=dev, dtype=dtype)
         ws = torch.empty((L.pps_head_chain_ws_bytes(),), device=dev, dtype=torch.uint8)
-        _lib.check(L.pps_head_chain_fwd(table.data_ptr(), ids.data_ptr(), pts.data_ptr(), query.data_ptr(), nq, k, _code(dtype), wx.data_ptr(), w2.data_ptr(),
-                                        b2.data_ptr(), w3.data_ptr(), b3.data_ptr(), wq.data_ptr(), bq.data_ptr(), h1.data_ptr(), y2.data_ptr(),
-                                        y3.data_ptr(), qy.data_ptr(), ws.data_ptr(), _stream()), 'pps_head_chain_fwd')
+        _lib.call('pps_head_chain_fwd', table, ids, pts, query, nq, k, _code(dtype), wx, w2, b2, w3, b3, wq, bq, h1, y2, y3, qy, ws)
         return h1[:rows], y2[:rows], y3[:rows], qy[:rows]
 
     with torch.no_grad(), torch.autocast('cuda', dtype=dtype):

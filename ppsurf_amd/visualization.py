@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib, meshio
-from .geometry import _device, _need_device, _ptr, _stream, closest_point_on_mesh
+from .geometry import _device, closest_point_on_mesh
 from .meshio import call_necessary, load_mesh_any
 
 NEAR = 0.01
@@ -171,7 +171,7 @@ def _clear_keys(h, w, dev):
 
 def raster_faces(verts: torch.Tensor, faces: torch.Tensor, cam: np.ndarray, width: int, height: int, keys: torch.Tensor = None) -> torch.Tensor:
     """Key buffer int64 [H,W] (bits of uint64 (depth bits << 32) | face id; -1 = empty) of the mesh on the device."""
-    _need_device(verts, faces)
+    _lib.need_device('visualization', verts, faces)
     verts = verts.to(torch.float32).contiguous()
     faces = faces.to(torch.int32).contiguous()
     dev = verts.device
@@ -180,26 +180,24 @@ def raster_faces(verts: torch.Tensor, faces: torch.Tensor, cam: np.ndarray, widt
     ws_bytes = L.pps_vis_raster_ws_bytes(verts.shape[0], faces.shape[0])
     ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=dev)
     cam = np.ascontiguousarray(cam, dtype=np.float32)
-    _lib.check(L.pps_vis_raster_faces(verts.data_ptr(), verts.shape[0], faces.data_ptr(), faces.shape[0], cam.ctypes.data, width, height,
-                                      ws.data_ptr(), ws_bytes, keys.data_ptr(), _stream(verts)), 'pps_vis_raster_faces')
+    _lib.call('pps_vis_raster_faces', verts, verts.shape[0], faces, faces.shape[0], cam.ctypes.data, width, height, ws, ws_bytes, keys)
     return keys
 
 
 def raster_points(pts: torch.Tensor, cam: np.ndarray, width: int, height: int, radius: float, keys: torch.Tensor = None) -> torch.Tensor:
     """Key buffer int64 [H,W] of points drawn as discs of `radius` pixels (key id = point index)."""
-    _need_device(pts)
+    _lib.need_device('visualization', pts)
     pts = pts.to(torch.float32).contiguous()
     keys = _clear_keys(height, width, pts.device) if keys is None else keys
     cam = np.ascontiguousarray(cam, dtype=np.float32)
-    _lib.check(_lib.lib().pps_vis_raster_points(pts.data_ptr(), pts.shape[0], cam.ctypes.data, width, height, float(radius), keys.data_ptr(),
-                                                _stream(pts)), 'pps_vis_raster_points')
+    _lib.call('pps_vis_raster_points', pts, pts.shape[0], cam.ctypes.data, width, height, float(radius), keys)
     return keys
 
 
 def shade(keys: torch.Tensor, verts: torch.Tensor, faces: typing.Optional[torch.Tensor], cam: np.ndarray, colors: torch.Tensor = None,
           rgb=GREY) -> torch.Tensor:
     """uint8 [H,W,3] image of a key buffer: faces given -> mesh shading, faces None -> points."""
-    _need_device(keys, verts)
+    _lib.need_device('visualization', keys, verts)
     h, w = keys.shape
     out = torch.empty((h, w, 3), dtype=torch.uint8, device=keys.device)
     verts = verts.to(torch.float32).contiguous()
@@ -209,8 +207,7 @@ def shade(keys: torch.Tensor, verts: torch.Tensor, faces: typing.Optional[torch.
         colors = colors.to(torch.uint8).contiguous()
     packed = (int(rgb[0]) << 16) | (int(rgb[1]) << 8) | int(rgb[2])
     cam = np.ascontiguousarray(cam, dtype=np.float32)
-    _lib.check(_lib.lib().pps_vis_shade(keys.data_ptr(), w, h, verts.data_ptr(), _ptr(faces), _ptr(colors), packed, cam.ctypes.data, out.data_ptr(),
-                                        _stream(keys)), 'pps_vis_shade')
+    _lib.call('pps_vis_shade', keys, w, h, verts, faces, colors, packed, cam.ctypes.data, out)
     return out
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/ppsurf_amd.h.
+"""ctypes binding of the C ABI declared in include/ppsurf_amd.h and of its extension entries (prefix `ppsx_`) in include/ppsurf_amd_ext.h.
 
 The product path has NO fallback: if libppsurf_amd.so is missing or fails to load, importing an op raises.
 """
@@ -14,6 +14,7 @@ if os.environ.get('PPS_LIB_VARIANT'):          # development aid: an ablation / 
     LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), 'libppsurf_amd_{}.so'.format(os.environ['PPS_LIB_VARIANT']))
 
 HEADER_PATH = os.path.join(os.path.dirname(HERE), 'include', 'ppsurf_amd.h')
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HERE), 'include', 'ppsurf_amd_ext.h')          # entries added after ABI version 2
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'uint32_t': ctypes.c_uint32, 'uint64_t': ctypes.c_uint64}
@@ -23,12 +24,12 @@ class PpsError(RuntimeError):
     pass
 
 
-def parse_header(text):
-    """(SIGNATURES, PARAMS) of the `pps_*` declarations of a C header: name -> (restype, argtypes) and name -> parameter names.
-    No C grammar: one regex over the text without comments; a type with `*` or `[` is a pointer, any other must be in _SCALARS."""
+def parse_header(text, prefix='pps_'):
+    """(SIGNATURES, PARAMS) of the `pps_*` declarations (of the `prefix*` ones) of a C header: name -> (restype, argtypes) and name ->
+    parameter names.  No C grammar: one regex over the text without comments; a type with `*` or `[` is a pointer, any other must be in _SCALARS."""
     text = re.sub(r'/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*', ' ', text, flags=re.S | re.M)
     signatures, names = {}, {}
-    for ret, name, params in re.findall(r'([\w \t*]+?)\b(pps_\w+)\s*\(([^()]*)\)\s*;', text):
+    for ret, name, params in re.findall(r'([\w \t*]+?)\b(' + re.escape(prefix) + r'\w+)\s*\(([^()]*)\)\s*;', text):
         params = [p.split() for p in params.split(',') if p.strip() not in ('', 'void')]
         try:
             argtypes = [ctypes.c_void_p if '*' in ''.join(p) or '[' in p[-1] else _SCALARS[' '.join(w for w in p[:-1] if w != 'const')] for p in params]
@@ -41,30 +42,38 @@ def parse_header(text):
 
 with open(HEADER_PATH) as _f:
     SIGNATURES, PARAMS = parse_header(_f.read())          # read from include/ppsurf_amd.h, the header the library is compiled against
+with open(EXT_HEADER_PATH) as _f:
+    EXT_SIGNATURES, EXT_PARAMS = parse_header(_f.read(), prefix='ppsx_')
 
 _lib = None            # the loaded library
 _entries = None        # name -> (function, takes a stream): what `call` needs of an entry, resolved once by bind()
+_ext_entries = {}      # the same for the extension entries, filled by lib(): empty while something else installs _entries directly
 
 
-def bind(handle):
-    """Types every declared entry of `handle` and returns the table `call` dispatches through."""
+def _bind(handle, signatures, params):
     entries = {}
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in signatures.items():
         fn = getattr(handle, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-        entries[name] = (fn, PARAMS[name][-1:] == ['stream'])
+        entries[name] = (fn, params[name][-1:] == ['stream'])
     return entries
 
 
+def bind(handle):
+    """Types every entry of `handle` that the main header declares and returns the table `call` dispatches through."""
+    return _bind(handle, SIGNATURES, PARAMS)
+
+
 def lib():
-    global _lib, _entries
+    global _lib, _entries, _ext_entries
     if _lib is None:
         if not os.path.isfile(LIB_PATH):
             raise PpsError('{} not found: build it with `python -m ppsurf_amd.build` (hipcc, gfx950). '
                            'There is no CPU fallback.'.format(LIB_PATH))
         handle = ctypes.CDLL(LIB_PATH)
         _entries = bind(handle)
+        _ext_entries = _bind(handle, EXT_SIGNATURES, EXT_PARAMS)
         _lib = handle
     return _lib
 
@@ -118,8 +127,10 @@ def call(name, *args, on=None, unchecked=False):
         lib()
     try:
         fn, takes_stream = _entries[name]
-    except KeyError:
-        raise PpsError('{} is not declared in {}'.format(name, HEADER_PATH)) from None
+    except KeyError:                                   # the main table, then the extension table: one set of rules for both
+        if name not in _ext_entries:
+            raise PpsError('{} is not declared in {}'.format(name, EXT_HEADER_PATH if name.startswith('ppsx_') else HEADER_PATH)) from None
+        fn, takes_stream = _ext_entries[name]
     if takes_stream:
         if on is not None:
             dev = on.device if isinstance(on, torch.Tensor) else on

@@ -55,13 +55,14 @@ def load_shape_data_pc(in_file, padding_factor, shape_name, normalize=False, pre
         if idx.shape[0] == 0:
             raise ValueError('no point of {} is left after the preparation'.format(pts_file))
         pts = pts[idx]
+    kept_rows = idx if prepare else None
     if pts.shape[1] > 3:
         nrm = pts[:, 3:6]
         normals = nrm / np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-20)
         pts = pts[:, :3]
     else:
         normals = np.zeros(pts.shape, dtype=np.float64)            # the reference's zeros_like of trimesh's float64 vertices
-    out = {}
+    out = {} if kept_rows is None else {'_kept_rows': kept_rows}          # rows of the file behind pts_ms: predict_step gathers the colours
     if normalize:
         bb_min, bb_max = pts.min(axis=0), pts.max(axis=0)
         if prepare:                                                # predict_step de-normalises with these instead of reloading the file

@@ -88,8 +88,11 @@ class PocoModel(_Base):
 
     def __init__(self, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir, padding_factor, name,
                  network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global, rec_batch_size,
-                 gen_refine_iter, workers, gen_max_faces=None):
+                 gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None):
         super().__init__()
+        if gen_color_k is not None and not 1 <= int(gen_color_k) <= 256:
+            raise ValueError('gen_color_k must be in 1..256 (neighbours blended per vertex), got {}'.format(gen_color_k))
+        self.gen_color_k = None if gen_color_k is None else int(gen_color_k)          # colours of the written mesh (ppsurf_amd/transfer.py)
         if gen_max_faces is not None and int(gen_max_faces) < 4:
             raise ValueError('gen_max_faces must be at least 4 (the faces of a tetrahedron), got {}'.format(gen_max_faces))
         self.gen_max_faces = None if gen_max_faces is None else int(gen_max_faces)      # face budget of the written mesh (ppsurf_amd/simplify.py)
@@ -103,6 +106,7 @@ class PocoModel(_Base):
         self.network = self._make_network()
         self.test_step_outputs = []
         self.last_prediction = None                 # (verts, faces) of the most recent predict_step, for callers/tests
+        self.last_colors = None                     # uint8 [nv,4] of that mesh when gen_color_k coloured it
 
     def _make_network(self):
         return PocoNetwork(in_channels=self.in_channels, latent_size=self.network_latent_size, out_channels=self.out_channels, k=self.k)
@@ -458,10 +462,12 @@ class PocoModel(_Base):
             input_points=pts_cf.t().cpu().numpy(), refine_iter=self.gen_refine_iter, out_value=1, prog_bar=bar, pc_file_in=pc_file_in,
             **({} if self.gen_max_faces is None else {'max_faces': self.gen_max_faces}))
         self.last_prediction = mesh
+        self.last_colors = None
         if getattr(self, 'shard_queries', False) and sharding.world()[0] != 0:
             return 0                                                   # every rank holds the same mesh; rank 0 writes it
         if mesh is not None:
             verts, faces = mesh
+            colors = self._vertex_colors(batch, pc_file_in, pts_cf, verts) if self.gen_color_k is not None else None
             double = False
             if not in_file_is_dataset(self.in_file):               # de-normalise single files (poco_model.py:256-265)
                 if '_bb_center' in batch:                           # a prepared cloud: the box of the KEPT points, carried by the item
@@ -474,7 +480,9 @@ class PocoModel(_Base):
                 # geo-referenced coordinates: doubles when float32 would move a vertex by more than 1e-3 of the grid step (file units)
                 moved = np.abs(np.asarray(verts, dtype=np.float64) - np.asarray(verts, dtype=np.float32).astype(np.float64))
                 double = bool(moved.size) and float(moved.max()) > 1e-3 * float(scale) / self.gen_resolution_global
-            if double:
+            if colors is not None:
+                meshio.write_ply_mesh_colored(out_file_rec, verts, faces, colors, double=double)
+            elif double:
                 meshio.write_ply_mesh(out_file_rec, verts, faces, double=True)
             else:
                 meshio.write_ply_mesh(out_file_rec, verts, faces)
@@ -482,19 +490,37 @@ class PocoModel(_Base):
             print('No reconstruction for {}'.format(pc_file_in))
         return 0
 
+    def _vertex_colors(self, batch, pc_file_in, pts_cf, verts):
+        """uint8 [nv,4] for the model-space vertices from the colours of the input file, or None with a notice when the
+        file carries none.  The cloud is pts_cf, the points the network saw; a prepared cloud brings the rows of the file it kept."""
+        from . import meshio, transfer
+        rgb = meshio.load_pts_colors(pc_file_in)
+        if rgb is None:
+            print('No colours in {}: the mesh is written without'.format(pc_file_in))
+            return None
+        if '_kept_rows' in batch:
+            rgb = rgb[np.asarray(batch['_kept_rows'])]
+        cloud = pts_cf.t().contiguous()
+        if rgb.shape[0] != cloud.shape[0]:
+            raise ValueError('{} colours for {} points of {}'.format(rgb.shape[0], cloud.shape[0], pc_file_in))
+        v = torch.from_numpy(np.ascontiguousarray(np.asarray(verts, dtype=np.float32))).to(cloud.device)
+        rgba, _ = transfer.transfer_colors(cloud, rgb, v, k=self.gen_color_k)
+        self.last_colors = rgba.cpu().numpy()
+        return self.last_colors
+
 
 class PPSurfModel(PocoModel):
 
     def __init__(self, pointnet_latent_size, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir,
                  padding_factor, name, network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global,
-                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None):
+                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None):
         self._pps = (num_pts_local, pointnet_latent_size)
         super().__init__(output_names=output_names, in_channels=in_channels, out_channels=out_channels, k=k, lambda_l1=lambda_l1,
                          debug=debug, in_file=in_file, results_dir=results_dir, padding_factor=padding_factor, name=name,
                          workers=workers, rec_batch_size=rec_batch_size, gen_refine_iter=gen_refine_iter,
                          gen_subsample_manifold=gen_subsample_manifold, gen_resolution_global=gen_resolution_global,
                          gen_subsample_manifold_iter=gen_subsample_manifold_iter, network_latent_size=network_latent_size,
-                         gen_max_faces=gen_max_faces)
+                         gen_max_faces=gen_max_faces, gen_color_k=gen_color_k)
         self.num_pts_local, self.pointnet_latent_size = num_pts_local, pointnet_latent_size
 
     def _make_network(self):

@@ -1,4 +1,5 @@
-"""Minimal PLY / XYZ / NPY / LAS / STL / OFF / OBJ / PCD IO for the predict path and the mesh evaluation (the reference uses trimesh, absent here).
+"""Minimal PLY / XYZ / NPY / LAS / STL / OFF / OBJ / PCD IO for the predict path and the mesh evaluation (the reference uses trimesh, absent here);
+`load_pts_colors` is the colour half of `load_pts`.
 
 Point clouds of datasets/abc_minimal are binary little-endian PLY written by trimesh
 (`element vertex n`, `property float x/y/z`, optional normals, `element face 0`); meshes are written the same way
@@ -202,11 +203,8 @@ def _fan_uniform(v):
     return np.stack([np.repeat(v[:, :1], k - 2, axis=1), v[:, 1:-1], v[:, 2:]], axis=2).reshape(-1, 3)
 
 
-def read_las_points(path):
-    """x, y, z float64 [n,3] of an uncompressed LAS 1.0-1.4 file, point formats 0-10 (ASPRS LAS specification, public header block):
-    offset to point data (byte 96), point format (104), record length (105), legacy number of points (107; for 1.4 the 64-bit field at 247
-    when the legacy one is 0), scale (131) and offset (155).  Every record starts with int32 X, Y, Z; xyz = int32 * scale + offset in float64,
-    as laspy's `las.xyz`.  Colours, intensity and classification are not read."""
+def _las_records(path):
+    """(point format, record length, number of records, the records' bytes, scale, offset) of an uncompressed LAS 1.0-1.4 file."""
     import struct
     with open(path, 'rb') as f:
         head = f.read(375)
@@ -227,8 +225,46 @@ def read_las_points(path):
         raw = f.read(n * rec_len)
     if len(raw) < n * rec_len:
         raise ValueError('LAS file ends before its {} point records: {}'.format(n, path))
+    return fmt, rec_len, n, raw, scale, offset
+
+
+def read_las_points(path):
+    """x, y, z float64 [n,3] of an uncompressed LAS 1.0-1.4 file, point formats 0-10 (ASPRS LAS specification, public header block):
+    offset to point data (byte 96), point format (104), record length (105), legacy number of points (107; for 1.4 the 64-bit field at 247
+    when the legacy one is 0), scale (131) and offset (155).  Every record starts with int32 X, Y, Z; xyz = int32 * scale + offset in float64,
+    as laspy's `las.xyz`.  Colours and intensity are read by read_las_colors; classification is not read."""
+    fmt, rec_len, n, raw, scale, offset = _las_records(path)
     ints = np.ndarray((n, 3), dtype='<i4', buffer=raw, strides=(rec_len, 4)) if n else np.zeros((0, 3), dtype='<i4')
     return ints.astype(np.float64) * scale[None] + offset[None]
+
+
+_LAS_RGB_AT = {2: 20, 3: 28, 5: 28, 7: 30, 8: 30, 10: 30}          # format 0 is 20 bytes, GPS time adds 8, format 6 is 30 (ASPRS record layouts)
+
+
+def read_las_colors(path):
+    """Colours uint8 [n,3] of the records read_las_points returns, or None.  RGB: three uint16 at record offset 20 (format 2), 28 (3, 5) or 30
+    (7, 8, 10), `v >> 8` when the file's largest value exceeds 255 and `v` itself otherwise (many writers store 0..255).  A format without
+    RGB, or RGB that is 0 everywhere, falls back to a grey from the intensity I (uint16 at offset 12): (I * 255 + Imax // 2) // Imax in
+    integers, Imax the file's maximum; None when that is 0.  A record too short for the field raises ValueError."""
+    fmt, rec_len, n, raw, _, _ = _las_records(path)
+    if n == 0:
+        return None
+    at = _LAS_RGB_AT.get(fmt)
+    if at is not None:
+        if rec_len < at + 6:
+            raise ValueError('LAS point format {} with records of {} bytes, too short for RGB at offset {}: {}'.format(fmt, rec_len, at, path))
+        rgb = np.ndarray((n, 3), dtype='<u2', buffer=raw, offset=at, strides=(rec_len, 2)).astype(np.uint16)
+        top = int(rgb.max())
+        if top > 0:
+            return (rgb >> 8 if top > 255 else rgb).astype(np.uint8)
+    if rec_len < 14:
+        raise ValueError('LAS records of {} bytes, too short for the intensity at offset 12: {}'.format(rec_len, path))
+    inten = np.ndarray((n,), dtype='<u2', buffer=raw, offset=12, strides=(rec_len,)).astype(np.int64)
+    imax = int(inten.max())
+    if imax == 0:
+        return None
+    g = ((inten * 255 + imax // 2) // imax).astype(np.uint8)
+    return np.stack([g, g, g], axis=1)
 
 
 def read_stl_vertices(path):
@@ -249,9 +285,8 @@ def read_stl_vertices(path):
     return v
 
 
-def read_off_vertices(path):
-    """Vertices float64 [nv,3] of an OFF / COFF / NOFF file: the `OFF` keyword (the counts `nv nf ne` on the same or the next line), then nv
-    lines that start with x y z (colours or normals after them are skipped); `#` comments and empty lines anywhere."""
+def _off_vertex_lines(path):
+    """(keyword, token lists of the nv vertex lines) of an OFF / COFF / NOFF file."""
     with open(path, 'r') as f:
         lines = [t for t in (line.split('#', 1)[0].split() for line in f) if t]
     if not lines or not lines[0][0].upper().endswith('OFF'):
@@ -260,21 +295,51 @@ def read_off_vertices(path):
     first = 1 if len(lines[0]) > 1 else 2
     try:
         nv = int(counts[0])
-        v = np.array([t[:3] for t in lines[first:first + nv]], dtype=np.float64).reshape(-1, 3)
     except (IndexError, ValueError):
         raise ValueError('malformed OFF file: {}'.format(path))
-    if v.shape[0] != nv:
+    rows = lines[first:first + nv]
+    if len(rows) != nv:
         raise ValueError('OFF file ends before its {} vertices: {}'.format(nv, path))
+    return lines[0][0].upper(), rows
+
+
+def read_off_vertices(path):
+    """Vertices float64 [nv,3] of an OFF / COFF / NOFF file: the `OFF` keyword (the counts `nv nf ne` on the same or the next line), then nv
+    lines that start with x y z (normals after them are skipped, colours are read by read_off_colors); `#` comments and empty lines anywhere."""
+    _, rows = _off_vertex_lines(path)
+    try:
+        v = np.array([t[:3] for t in rows], dtype=np.float64).reshape(-1, 3)
+    except ValueError:
+        raise ValueError('malformed OFF file: {}'.format(path))
     return v
+
+
+def read_off_colors(path):
+    """Colours uint8 [nv,3] of the vertices of an OFF file whose keyword contains `C` (COFF, CNOFF, ...), or None.  The colour columns follow
+    x y z, and the normal where the keyword contains `N`; an alpha column is ignored.  Tokens with `.`, `e` or `E` anywhere make the file's
+    colours floats in [0, 1], converted with rint(clip * 255); otherwise they are integers 0..255."""
+    keyword, rows = _off_vertex_lines(path)
+    word = keyword[:-3]
+    if 'C' not in word or not rows:
+        return None
+    at = 6 if 'N' in word else 3
+    try:
+        tok = [t[at:at + 3] for t in rows]
+        if any(len(t) != 3 for t in tok):
+            raise ValueError
+        if any(ch in c for t in tok for c in t for ch in '.eE'):
+            return np.rint(np.clip(np.array(tok, dtype=np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+        return np.clip(np.array(tok, dtype=np.int64), 0, 255).astype(np.uint8)
+    except ValueError:
+        raise ValueError('malformed colours in OFF file: {}'.format(path))
 
 
 _PCD_TYPES = {('F', 4): 'f4', ('F', 8): 'f8', ('I', 1): 'i1', ('I', 2): 'i2', ('I', 4): 'i4', ('I', 8): 'i8',
               ('U', 1): 'u1', ('U', 2): 'u2', ('U', 4): 'u4', ('U', 8): 'u8'}
 
 
-def read_pcd_points(path):
-    """x, y, z [n,3] of a PCD 0.7 file (Point Cloud Library), `DATA ascii` or `DATA binary`, any field list that holds x y z as 4- or 8-byte
-    floats (float64 out when they are 8-byte, float32 otherwise)."""
+def _pcd_parts(path):
+    """(fields, sizes, types, counts, n, mode, body) of a PCD 0.7 file."""
     with open(path, 'rb') as f:
         head = {}
         while True:
@@ -295,23 +360,64 @@ def read_pcd_points(path):
         mode = head['DATA'][0].lower()
     except (KeyError, IndexError, ValueError):
         raise ValueError('incomplete PCD header: {}'.format(path))
+    return fields, sizes, types, counts, n, mode, body
+
+
+def _pcd_ascii_rows(body, n, path):
+    rows = [line.split() for line in body.decode('ascii', 'replace').split('\n') if line.strip()][:n]
+    if len(rows) < n:
+        raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
+    return rows
+
+
+def _pcd_records(fields, sizes, types, counts, n, body, path):
+    dt = np.dtype([(name, '<' + _PCD_TYPES[(t.upper(), s)], (c,)) for name, s, t, c in zip(fields, sizes, types, counts)])
+    if len(body) < n * dt.itemsize:
+        raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
+    return np.frombuffer(body, dtype=dt, count=n)
+
+
+def read_pcd_points(path):
+    """x, y, z [n,3] of a PCD 0.7 file (Point Cloud Library), `DATA ascii` or `DATA binary`, any field list that holds x y z as 4- or 8-byte
+    floats (float64 out when they are 8-byte, float32 otherwise)."""
+    fields, sizes, types, counts, n, mode, body = _pcd_parts(path)
     for k in 'xyz':
         if k not in fields or types[fields.index(k)].upper() != 'F' or sizes[fields.index(k)] not in (4, 8) or counts[fields.index(k)] != 1:
             raise ValueError('PCD without float x y z fields: {}'.format(path))
     out_type = np.float64 if any(sizes[fields.index(k)] == 8 for k in 'xyz') else np.float32
     if mode == 'ascii':
         starts = np.concatenate([[0], np.cumsum(counts)])
-        rows = [line.split() for line in body.decode('ascii', 'replace').split('\n') if line.strip()][:n]
-        if len(rows) < n:
-            raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
+        rows = _pcd_ascii_rows(body, n, path)
         return np.array([[r[starts[fields.index(k)]] for k in 'xyz'] for r in rows], dtype=out_type).reshape(n, 3)
     if mode != 'binary':
         raise ValueError('PCD DATA {} is not supported (ascii and binary are): {}'.format(mode, path))
-    dt = np.dtype([(name, '<' + _PCD_TYPES[(t.upper(), s)], (c,)) for name, s, t, c in zip(fields, sizes, types, counts)])
-    if len(body) < n * dt.itemsize:
-        raise ValueError('PCD file ends before its {} points: {}'.format(n, path))
-    rec = np.frombuffer(body, dtype=dt, count=n)
+    rec = _pcd_records(fields, sizes, types, counts, n, body, path)
     return np.stack([rec[k][:, 0].astype(out_type) for k in 'xyz'], axis=1)
+
+
+def read_pcd_colors(path):
+    """Colours uint8 [n,3] of a PCD file with a 4-byte field `rgb` or `rgba` of TYPE F, U or I (COUNT 1), or None.  The field's four bytes are
+    the uint32 0x..RRGGBB (PCL's packing); an ascii value of TYPE F is parsed as float32 and its bits are taken."""
+    fields, sizes, types, counts, n, mode, body = _pcd_parts(path)
+    name = 'rgb' if 'rgb' in fields else 'rgba' if 'rgba' in fields else None
+    if name is None:
+        return None
+    at = fields.index(name)
+    if sizes[at] != 4 or counts[at] != 1 or types[at].upper() not in ('F', 'U', 'I'):
+        return None
+    if mode not in ('ascii', 'binary'):
+        raise ValueError('PCD DATA {} is not supported (ascii and binary are): {}'.format(mode, path))
+    if mode == 'ascii':
+        col = int(np.sum(counts[:at]))
+        tok = [r[col] for r in _pcd_ascii_rows(body, n, path)]
+        if types[at].upper() == 'F':
+            packed = np.array(tok, dtype=np.float32).view(np.uint32)
+        else:
+            packed = (np.array([int(t) for t in tok], dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    else:
+        packed = np.ascontiguousarray(_pcd_records(fields, sizes, types, counts, n, body, path)[name][:, 0]).view(np.uint32)
+    packed = packed.reshape(n)
+    return np.stack([(packed >> 16) & 0xFF, (packed >> 8) & 0xFF, packed & 0xFF], axis=1).astype(np.uint8)
 
 
 def load_pts(pts_file: str) -> np.ndarray:
@@ -339,6 +445,23 @@ def load_pts(pts_file: str) -> np.ndarray:
     if ext == '.pcd':
         return read_pcd_points(pts_file)
     raise ValueError('Unknown point cloud type: {}'.format(pts_file))
+
+
+def load_pts_colors(pts_file: str):
+    """Colours uint8 [n,3] of the rows `load_pts(pts_file)` returns, one to one, or None when the file carries none.  PLY red/green/blue, LAS
+    RGB (or a grey from the intensity), PCD packed rgb / rgba, COFF and `v x y z r g b` of an OBJ; .xyz / .npy columns 3-5 are normals."""
+    ext = os.path.splitext(pts_file)[1].lower()
+    if ext == '.ply':
+        return read_ply_vertex_colors(pts_file)
+    if ext == '.las':
+        return read_las_colors(pts_file)
+    if ext == '.pcd':
+        return read_pcd_colors(pts_file)
+    if ext == '.off':
+        return read_off_colors(pts_file)
+    if ext == '.obj':
+        return read_obj_mesh(pts_file, colors=True)[2]
+    return None
 
 
 def write_ply_mesh(path, verts: np.ndarray, faces: np.ndarray, double=False):
@@ -369,19 +492,20 @@ def write_ply_points(path, pts: np.ndarray):
         f.write(pts.tobytes())
 
 
-def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8: np.ndarray):
+def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8: np.ndarray, double=False):
     """Binary little-endian PLY mesh with per-vertex `uchar red/green/blue/alpha` (the layout trimesh exports for vertex colours).
-    colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]."""
+    colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]; double=True stores `property double x/y/z` as in write_ply_mesh."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    verts = np.asarray(verts, dtype='<f4').reshape(-1, 3)
+    ftype = '<f8' if double else '<f4'
+    verts = np.asarray(verts, dtype=ftype).reshape(-1, 3)
     faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
     colors = np.asarray(colors_u8, dtype=np.uint8).reshape(verts.shape[0], -1)
     if colors.shape[1] == 3:
         colors = np.concatenate([colors, np.full((colors.shape[0], 1), 255, dtype=np.uint8)], axis=1)
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {}\nproperty float x\nproperty float y\n'
-              'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face {}\n'
-              'property list uchar int vertex_indices\nend_header\n').format(verts.shape[0], faces.shape[0])
-    vrec = np.empty(verts.shape[0], dtype=[('p', '<f4', (3,)), ('c', 'u1', (4,))])
+    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {2} x\nproperty {2} y\n'
+              'property {2} z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face {1}\n'
+              'property list uchar int vertex_indices\nend_header\n').format(verts.shape[0], faces.shape[0], 'double' if double else 'float')
+    vrec = np.empty(verts.shape[0], dtype=[('p', ftype, (3,)), ('c', 'u1', (4,))])
     vrec['p'] = verts
     vrec['c'] = colors[:, :4]
     frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
@@ -393,10 +517,12 @@ def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8
         f.write(frec.tobytes())
 
 
-def read_obj_mesh(path):
+def read_obj_mesh(path, colors=False):
     """Vertices float32 [nv,3] and triangles int32 [nf,3] of a Wavefront OBJ: `v x y z` and `f` lines only (`a`, `a/b`, `a//c`, `a/b/c`
-    corners, 1-based or negative (relative) indices, polygons fan-triangulated).  Raises ValueError on an index outside the vertices."""
-    verts, polys = [], []
+    corners, 1-based or negative (relative) indices, polygons fan-triangulated).  Raises ValueError on an index outside the vertices.
+    colors=True: a third result, uint8 [nv,3] from `v x y z r g b` with r g b floats in [0, 1] (rint(clip * 255)) when EVERY `v` line has
+    them, else None."""
+    verts, polys, rgb = [], [], []
     with open(path, 'r') as f:
         for line in f:
             tok = line.split()
@@ -404,6 +530,8 @@ def read_obj_mesh(path):
                 continue
             if tok[0] == 'v':
                 verts.append([float(t) for t in tok[1:4]])
+                if colors and len(tok) >= 7:
+                    rgb.append(tok[4:7])
             elif tok[0] == 'f':
                 poly = []
                 for c in tok[1:]:
@@ -414,6 +542,11 @@ def read_obj_mesh(path):
     faces = _fan(polys)
     if faces.size and (faces.min() < 0 or faces.max() >= v.shape[0]):
         raise ValueError('OBJ face index out of range: {}'.format(path))
+    if colors:
+        col = None
+        if rgb and len(rgb) == len(verts):
+            col = np.rint(np.clip(np.array(rgb, dtype=np.float64), 0.0, 1.0) * 255.0).astype(np.uint8)
+        return v, faces.astype(np.int32), col
     return v, faces.astype(np.int32)
 
 
@@ -424,8 +557,7 @@ def load_mesh_any(path: str):
         pts = np.load(path)
         return np.asarray(pts, dtype=np.float32)[:, :3], np.zeros((0, 3), dtype=np.int32), None
     if ext == '.obj':
-        v, f = read_obj_mesh(path)
-        return v, f, None
+        return read_obj_mesh(path, colors=True)
     if ext == '.ply':
         v, f = read_ply_mesh(path)
         return v, f, read_ply_vertex_colors(path)

@@ -272,6 +272,7 @@ static int launch_rows_gemm(const float* in1, const int64_t* idx1, int c1, const
     const int obt = ((n + 31) / 32) * 2;                    // packed output blocks (out padded to 32)
     const unsigned gx = (unsigned)((m + 63) / 64);
     // few row tiles -> narrow output tiles so that the weight stream is spread over more CUs
+    // (tests/encoder_spec.py rows_gemm_template restates this condition to pick shapes on either side of it: change both together)
     if (gx * (obt / 4) >= 256 && obt % 4 == 0)
         hipLaunchKernelGGL(rows_gemm_kernel<4>, dim3(gx, obt / 4), dim3(256), 0, st, in1, idx1, c1, in2, idx2, c2, (const f32x4*)wpack,
                            bias, residual, act, m, n, out);

@@ -27,72 +27,39 @@ import numpy as np
 import torch
 
 from . import _lib, meshio, ops
-
-MAX_AXIS = 1 << 20
-
-
-def _f3(v):
-    import ctypes
-    return (ctypes.c_float * 3)(*[float(x) for x in v])
+from .cells import CellGrid
 
 
-class VoxelGrid:
-    """The voxel stage for one float32 device cloud [n,3]: box, scratch tables and the two entry points.  `capacity` (a power of two > n) is a
-    test switch: results do not depend on it."""
+class VoxelGrid(CellGrid):
+    """The voxel stage for one float32 device cloud [n,3]: the cell grid and the two entry points."""
 
     def __init__(self, pts: torch.Tensor, capacity=None):
         _lib.need_device('VoxelGrid', pts)
         assert pts.dim() == 2 and pts.shape[1] == 3 and pts.shape[0] >= 1
         self.pts = pts.contiguous().float()
         self.n = int(self.pts.shape[0])
-        lo, hi = self.pts.min(dim=0)[0], self.pts.max(dim=0)[0]
-        self.lo, self.hi = lo.cpu().numpy(), hi.cpu().numpy()                 # float32
-        self.ext = np.float32((self.hi - self.lo).max())
-        self.capacity = int(capacity) if capacity is not None else int(_lib.lib().pps_cloud_table_capacity(self.n))
-        self._table = self._best = None
-        self._count = torch.zeros(1, dtype=torch.int64, device=pts.device)
-
-    def _scratch(self, best=False):
-        if self._table is None:
-            self._table = torch.empty(self.capacity, dtype=torch.int64, device=self.pts.device)
-        if best and self._best is None:
-            self._best = torch.empty(self.capacity, dtype=torch.int64, device=self.pts.device)
-
-    def step(self, G):
-        """h, 1 / h (float32) of the grid with G cells along the longest edge: the quotient in fp64, rounded once."""
-        h = np.float32(np.float64(self.ext) / np.float64(G))
-        return h, np.float32(1.0) / h
+        super().__init__(self.pts, capacity)
 
     def count_rc(self, h, inv_h, unchecked=True):
         """(status, number of occupied cells) of pps_cloud_voxel_count; the count is meaningless unless status == 0."""
         self._scratch()
-        rc = _lib.call('pps_cloud_voxel_count', self.pts, self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h), self._table, self.capacity,
-                       self._count, unchecked=unchecked)
+        rc = _lib.call('pps_cloud_voxel_count', self.pts, self.n, self._vec3(self.lo), self._vec3(self.hi), float(h), float(inv_h), self._table,
+                       self.capacity, self._count, unchecked=unchecked)
         return rc, (int(self._count.item()) if rc == 0 else -1)
 
     def count(self, h, inv_h=None):
-        inv_h = np.float32(1.0) / np.float32(h) if inv_h is None else inv_h
-        return self.count_rc(h, inv_h, unchecked=False)[1]
+        return self.count_rc(h, self._inv(h, inv_h), unchecked=False)[1]
+
+    def count_at(self, G):
+        return self.count(*self.step(G))
 
     def select(self, h, inv_h=None):
         """Ascending int64 indices (device) of the point kept by every occupied cell."""
-        inv_h = np.float32(1.0) / np.float32(h) if inv_h is None else inv_h
         self._scratch(best=True)
         keep = torch.empty(self.n, dtype=torch.uint8, device=self.pts.device)
-        _lib.call('pps_cloud_voxel_select', self.pts, self.n, _f3(self.lo), _f3(self.hi), float(h), float(inv_h), self._table, self._best, self.capacity,
-                  self._count, keep)
+        _lib.call('pps_cloud_voxel_select', self.pts, self.n, self._vec3(self.lo), self._vec3(self.hi), float(h), float(self._inv(h, inv_h)),
+                  self._table, self._best, self.capacity, self._count, keep)
         return torch.nonzero(keep).reshape(-1)
-
-    def search(self, max_points):
-        """The budget search: G_lo of the bisection with cells(G_lo) <= max_points < cells(G_hi), 20 counting passes."""
-        g_lo, g_hi = 1, MAX_AXIS
-        while g_hi - g_lo > 1:
-            mid = (g_lo + g_hi) // 2
-            if self.count(*self.step(mid)) <= max_points:
-                g_lo = mid
-            else:
-                g_hi = mid
-        return g_lo
 
 
 def mean_knn_distance(d2: torch.Tensor) -> torch.Tensor:

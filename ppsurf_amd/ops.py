@@ -271,3 +271,29 @@ def mesh_face_filter(faces: torch.Tensor, hot: torch.Tensor):
     ws = torch.empty(L.pps_mesh_face_filter_ws_bytes(nf), dtype=torch.uint8, device=faces.device)
     _lib.call('pps_mesh_face_filter', faces, nf, hot, keep, ws)
     return keep.bool()
+
+
+def csr_build(idx_flat: torch.Tensor, n: int):
+    """(order, offsets) of a flat id table, not cached: entries stably sorted by target row (ascending entry number inside a row), offsets int64
+    [n+1] -- a counting sort on the device (pps_csr_build: count, scan, fill, rank; csrc/pps_csr.hip), the same arrays torch.sort(stable) +
+    torch.searchsorted returned until round 5 (tests/test_gpu_train.py::test_csr_build_*)."""
+    return csr_build_table(idx_flat.reshape(-1), 0, 0, n, False, want_flat=False)[1:]
+
+
+def csr_build_table(ids: torch.Tensor, per_item: int, rows_per_item: int, rows: int, clamp_negative: bool, want_flat: bool = True):
+    """(flat, order, offsets) of an id table [B, M, K] of a fit batch in one call: flat row numbers ids + item * rows_per_item (per_item = M * K
+    entries per batch item; -1 -> row 0 with clamp_negative), and their CSR.  per_item = 0: `ids` are flat rows already."""
+    _lib.need_device('csr_build', ids)
+    if ids.dtype != torch.int64:
+        raise _lib.PpsError('csr_build: id tables are int64')
+    ids = ids.contiguous()
+    entries = ids.numel()
+    L = _lib.lib()
+    dev = ids.device
+    flat = torch.empty((entries,), dtype=torch.int64, device=dev) if want_flat else None
+    order = torch.empty((entries,), dtype=torch.int64, device=dev)
+    offsets = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
+    nbytes = L.pps_csr_ws_bytes(entries, rows)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    _lib.call('pps_csr_build', ids, entries, int(per_item), int(rows_per_item), int(rows), 1 if clamp_negative else 0, flat, order, offsets, ws, nbytes)
+    return flat, order, offsets

@@ -14,7 +14,6 @@ the models' `gen_max_faces`.
   4. faces are remapped, collapsed and duplicate ones (same unordered triple, first kept) are dropped, then unreferenced vertices.
 The result is a pure function of the mesh and G: integer atomics only, fixed order of the fp64 operations.
 """
-import ctypes
 import json
 import os
 import sys
@@ -22,14 +21,10 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio
+from . import _lib, meshio, ops
+from .cells import CellGrid
 
-MAX_AXIS = 1 << 20
 PLACEMENTS = ('quadric', 'mean')
-
-
-def _d3(v):
-    return (ctypes.c_double * 3)(*[float(x) for x in v])
 
 
 def _cross(u, w):
@@ -37,22 +32,8 @@ def _cross(u, w):
     return torch.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], dim=1)
 
 
-def _csr(ids: torch.Tensor, rows: int):
-    """(order, offsets) of the entries of ids int64 [n] by row, ascending inside a row (pps_csr_build with per_item = 0: the stable counting
-    sort of csrc/pps_csr.hip)."""
-    L = _lib.lib()
-    n, dev = int(ids.numel()), ids.device
-    order = torch.empty(n, dtype=torch.int64, device=dev)
-    offsets = torch.empty(rows + 1, dtype=torch.int64, device=dev)
-    nbytes = L.pps_csr_ws_bytes(n, rows)
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    _lib.call('pps_csr_build', ids, n, 0, 0, int(rows), 0, None, order, offsets, ws, nbytes)
-    return order, offsets
-
-
-class ClusterGrid:
-    """The clustering of one device mesh (verts f64 [nv,3], faces int64 [nf,3]): box, scratch tables, counting pass, budget search and the
-    simplification itself.  `capacity` (a power of two > nv) is a test switch: results do not depend on it."""
+class ClusterGrid(CellGrid):
+    """The clustering of one device mesh (verts f64 [nv,3], faces int64 [nf,3]): the cell grid, counting pass and the simplification itself."""
 
     def __init__(self, verts: torch.Tensor, faces: torch.Tensor, capacity=None):
         _lib.need_device('ClusterGrid', verts, faces)
@@ -64,34 +45,21 @@ class ClusterGrid:
             raise ValueError('simplification needs finite vertices')
         if self.nf and (int(self.faces.min()) < 0 or int(self.faces.max()) >= self.nv):
             raise ValueError('face index outside the vertices')
-        self.lo, self.hi = self.verts.min(dim=0)[0].cpu().numpy(), self.verts.max(dim=0)[0].cpu().numpy()      # float64
-        self.ext = np.float64((self.hi - self.lo).max())
-        self.capacity = int(capacity) if capacity is not None else int(_lib.lib().pps_cloud_table_capacity(self.nv))
-        dev = self.verts.device
-        self._table = self._best = None
-        self._count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._leader = torch.empty(self.nv, dtype=torch.int64, device=dev)
+        super().__init__(self.verts, capacity)
+        self._leader = torch.empty(self.nv, dtype=torch.int64, device=self.device)
 
     def _scratch(self):
-        if self._table is None:
-            self._table = torch.empty(self.capacity, dtype=torch.int64, device=self.verts.device)
-            self._best = torch.empty(self.capacity, dtype=torch.int64, device=self.verts.device)
-
-    def step(self, G):
-        """h, 1 / h (float64) of the grid with G cells along the longest edge."""
-        h = np.float64(self.ext) / np.float64(G)
-        return h, np.float64(1.0) / h
+        super()._scratch(best=True)
 
     def leaders_rc(self, h, inv_h, unchecked=True):
         """(status, leader int64 [nv] (device, reused by the next call), occupied cells) of pps_simplify_leaders."""
         self._scratch()
-        rc = _lib.call('pps_simplify_leaders', self.verts, self.nv, _d3(self.lo), _d3(self.hi), float(h), float(inv_h), self._table, self._best,
-                       self.capacity, self._leader, self._count, unchecked=unchecked)
+        rc = _lib.call('pps_simplify_leaders', self.verts, self.nv, self._vec3(self.lo), self._vec3(self.hi), float(h), float(inv_h), self._table,
+                       self._best, self.capacity, self._leader, self._count, unchecked=unchecked)
         return rc, self._leader, (int(self._count.item()) if rc == 0 else -1)
 
     def leaders(self, h, inv_h=None):
-        inv_h = np.float64(1.0) / np.float64(h) if inv_h is None else inv_h
-        return self.leaders_rc(h, inv_h, unchecked=False)[1:]
+        return self.leaders_rc(h, self._inv(h, inv_h), unchecked=False)[1:]
 
     def survivors(self, leader):
         _lib.call('pps_simplify_count', self.faces, self.nf, leader, self.nv, self._count)
@@ -106,16 +74,7 @@ class ClusterGrid:
     def count(self, G):
         return self.count_step(*self.step(G)) if self.ext > 0 else 0
 
-    def search(self, max_faces):
-        """The budget search: G_lo of the bisection with count(G_lo) <= max_faces < count(G_hi), 20 counting passes."""
-        g_lo, g_hi = 1, MAX_AXIS
-        while g_hi - g_lo > 1:
-            mid = (g_lo + g_hi) // 2
-            if self.count(mid) <= max_faces:
-                g_lo = mid
-            else:
-                g_hi = mid
-        return g_lo
+    count_at = count
 
     def run(self, G=None, placement='quadric', h=None, keep=False):
         """Simplify on the grid of G cells along the longest edge (or of step h) -> (verts f64 [V,3], faces int64 [F,3], report).  keep=True adds
@@ -145,13 +104,13 @@ class ClusterGrid:
         flag = leader == torch.arange(self.nv, dtype=torch.int64, device=dev)
         cid = (torch.cumsum(flag, 0) - 1)[leader].contiguous()                  # rank of the cell's leader among the leaders
         corner_ids = cid[self.faces.reshape(-1)].contiguous()
-        c_order, c_off = _csr(corner_ids, ncell)
-        v_order, v_off = _csr(cid, ncell)
+        c_order, c_off = ops.csr_build(corner_ids, ncell)
+        v_order, v_off = ops.csr_build(cid, ncell)
         A = torch.empty((ncell, 6), dtype=torch.float64, device=dev)
         b, xhat, pos = (torch.empty((ncell, 3), dtype=torch.float64, device=dev) for _ in range(3))
         fell = torch.empty(ncell, dtype=torch.uint8, device=dev)
-        _lib.call('pps_simplify_place', self.verts, self.nv, self.faces, self.nf, cid, ncell, c_order, c_off, v_order, v_off, _d3(self.lo), _d3(self.hi),
-                  float(h), float(inv_h), 1 if placement == 'mean' else 0, A, b, xhat, pos, fell)
+        _lib.call('pps_simplify_place', self.verts, self.nv, self.faces, self.nf, cid, ncell, c_order, c_off, v_order, v_off, self._vec3(self.lo),
+                  self._vec3(self.hi), float(h), float(inv_h), 1 if placement == 'mean' else 0, A, b, xhat, pos, fell)
         new = corner_ids.reshape(-1, 3)
         alive = (new[:, 0] != new[:, 1]) & (new[:, 1] != new[:, 2]) & (new[:, 0] != new[:, 2])
         src = torch.nonzero(alive).reshape(-1)                                  # input face of every survivor

@@ -22,6 +22,7 @@ import os
 import torch
 
 from . import _lib
+from .ops import csr_build, csr_build_table           # csr() below calls csr_build through this module's name
 
 
 LOW = (torch.bfloat16, torch.float16)          # 16-bit storage types of the fused training ops (trainer.precision bf16-mixed / 16-mixed)
@@ -66,32 +67,6 @@ def csr(idx_flat: torch.Tensor, n: int):
 def csr_register(idx_flat, n, order, offsets):
     """Enter a CSR built elsewhere (with the batch, train_graph.table_extras) so that the backward pass finds it."""
     _csr_cache[(idx_flat.data_ptr(), idx_flat._version, idx_flat.numel(), n)] = (idx_flat, order, offsets)
-
-
-def csr_build(idx_flat: torch.Tensor, n: int):
-    """(order, offsets) of a flat id table, not cached: entries stably sorted by target row (ascending entry number inside a row), offsets int64
-    [n+1] -- a counting sort on the device (pps_csr_build: count, scan, fill, rank; csrc/pps_csr.hip), the same arrays torch.sort(stable) +
-    torch.searchsorted returned until round 5 (tests/test_gpu_train.py::test_csr_build_*)."""
-    return csr_build_table(idx_flat.reshape(-1), 0, 0, n, False, want_flat=False)[1:]
-
-
-def csr_build_table(ids: torch.Tensor, per_item: int, rows_per_item: int, rows: int, clamp_negative: bool, want_flat: bool = True):
-    """(flat, order, offsets) of an id table [B, M, K] of a fit batch in one call: flat row numbers ids + item * rows_per_item (per_item = M * K
-    entries per batch item; -1 -> row 0 with clamp_negative), and their CSR.  per_item = 0: `ids` are flat rows already."""
-    _lib.need_device('train_ops', ids)
-    if ids.dtype != torch.int64:
-        raise _lib.PpsError('csr_build: id tables are int64')
-    ids = ids.contiguous()
-    entries = ids.numel()
-    L = _lib.lib()
-    dev = ids.device
-    flat = torch.empty((entries,), dtype=torch.int64, device=dev) if want_flat else None
-    order = torch.empty((entries,), dtype=torch.int64, device=dev)
-    offsets = torch.empty((rows + 1,), dtype=torch.int64, device=dev)
-    nbytes = L.pps_csr_ws_bytes(entries, rows)
-    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-    _lib.call('pps_csr_build', ids, entries, int(per_item), int(rows_per_item), int(rows), 1 if clamp_negative else 0, flat, order, offsets, ws, nbytes)
-    return flat, order, offsets
 
 
 def clear_cache():

@@ -3,35 +3,25 @@ GPU is held to, bit for bit.  Every float32 step is one numpy float32 operation,
 """
 import numpy as np
 
+import grid_spec
+from grid_spec import MAX_AXIS
+
 F = np.float32
-MAX_AXIS = 1 << 20
 RED = 512                                       # threads of the one-workgroup reduction
 
 
 def grid_step(ext, G):
     """h and 1 / h of a grid with G cells along the longest box edge `ext` (float32): the quotient in fp64, rounded once to float32."""
-    h = F(np.float64(F(ext)) / np.float64(G))
-    return h, F(1.0) / h
+    return grid_spec.grid_step(ext, G, F)
 
 
 def grid_dims(lo, hi, inv_h):
-    """G_a = int(floorf((hi_a - lo_a) * inv_h)) + 1, or None where an axis would need more than 2^20 cells."""
-    t = np.floor((hi.astype(F) - lo.astype(F)) * F(inv_h))
-    if not np.all(t < MAX_AXIS):
-        return None
-    return t.astype(np.int64) + 1
+    return grid_spec.grid_dims(lo, hi, inv_h, F)
 
 
 def cells(pts, lo, hi, h, inv_h):
     """Cell coordinates int64 [n,3], dims [3] and 64-bit keys [n] of float32 points."""
-    pts, lo = pts.astype(F), lo.astype(F)
-    G = grid_dims(lo, hi, inv_h)
-    if G is None:
-        raise ValueError('more than 2^20 cells along an axis')
-    t = np.floor((pts - lo[None]) * F(inv_h))
-    c = np.minimum(t.astype(np.int64), (G - 1)[None])
-    key = (c[:, 2] * G[1] + c[:, 1]) * G[0] + c[:, 0]
-    return c, G, key
+    return grid_spec.cells(pts, lo, hi, inv_h, F)
 
 
 def voxel_select(pts, lo, hi, h, inv_h):
@@ -53,28 +43,15 @@ def voxel_count(pts, lo, hi, h, inv_h):
 
 
 def box(pts):
-    pts = pts.astype(F)
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    return lo, hi, F((hi - lo).max())
+    return grid_spec.box(pts, F)
 
 
 def budget_search(pts, max_points, count=None):
-    """Bisection of the integer G in [1, 2^20] with cells(G_lo) <= max_points < cells(G_hi): 20 counting passes, the answer is G_lo.
-    `count(h, inv_h)` defaults to the numpy count; the device driver passes its own."""
+    """grid_spec.bisect on the number of occupied cells.  `count(h, inv_h)` defaults to the numpy count; the device driver passes its own."""
     lo, hi, ext = box(pts)
     if count is None:
         count = lambda h, inv_h: voxel_count(pts, lo, hi, h, inv_h)
-    g_lo, g_hi, passes = 1, MAX_AXIS, 0
-    while g_hi - g_lo > 1:
-        mid = (g_lo + g_hi) // 2
-        h, inv_h = grid_step(ext, mid)
-        passes += 1
-        if count(h, inv_h) <= max_points:
-            g_lo = mid
-        else:
-            g_hi = mid
-    assert passes == 20
-    return g_lo
+    return grid_spec.bisect(lambda G: count(*grid_step(ext, G)), max_points)
 
 
 def subsample(pts, max_points):

@@ -5,38 +5,28 @@ ascending order, one rounding per addition.
 """
 import numpy as np
 
+import grid_spec
+from grid_spec import MAX_AXIS
+
 D = np.float64
-MAX_AXIS = 1 << 20
 
 
 def box(verts):
-    verts = np.asarray(verts, dtype=D)
-    lo, hi = verts.min(axis=0), verts.max(axis=0)
-    return lo, hi, D((hi - lo).max())
+    return grid_spec.box(verts, D)
 
 
 def grid_step(ext, G):
     """h and 1 / h of a grid with G cells along the longest box edge `ext`, both in fp64."""
-    h = D(ext) / D(G)
-    return h, D(1.0) / h
+    return grid_spec.grid_step(ext, G, D)
 
 
 def grid_dims(lo, hi, inv_h):
-    """G_a = int(floor((hi_a - lo_a) * inv_h)) + 1, or None where an axis would need more than 2^20 cells."""
-    t = np.floor((hi - lo) * D(inv_h))
-    if not np.all(t < MAX_AXIS):
-        return None
-    return t.astype(np.int64) + 1
+    return grid_spec.grid_dims(lo, hi, inv_h, D)
 
 
 def cells(verts, lo, hi, inv_h):
     """Cell coordinates int64 [n,3], dims [3] and 64-bit keys [n]."""
-    dims = grid_dims(lo, hi, inv_h)
-    if dims is None:
-        raise ValueError('more than 2^20 cells along an axis')
-    t = np.floor((verts - lo[None]) * D(inv_h))
-    c = np.minimum(t.astype(np.int64), (dims - 1)[None])
-    return c, dims, (c[:, 2] * dims[1] + c[:, 1]) * dims[0] + c[:, 0]
+    return grid_spec.cells(verts, lo, hi, inv_h, D)
 
 
 def leaders(key):
@@ -179,20 +169,8 @@ def simplify(verts, faces, G=None, placement='quadric', h=None):
 
 
 def budget_search(verts, faces, max_faces, count_fn=None):
-    """Bisection of the integer G in [1, 2^20] with count(G_lo) <= max_faces < count(G_hi): 20 counting passes, the answer is G_lo.
-    `count_fn(G)` defaults to the numpy count; the device driver passes its own."""
-    if count_fn is None:
-        count_fn = lambda G: count(verts, faces, G)
-    g_lo, g_hi, passes = 1, MAX_AXIS, 0
-    while g_hi - g_lo > 1:
-        mid = (g_lo + g_hi) // 2
-        passes += 1
-        if count_fn(mid) <= max_faces:
-            g_lo = mid
-        else:
-            g_hi = mid
-    assert passes == 20
-    return g_lo
+    """grid_spec.bisect on the survivor count.  `count_fn(G)` defaults to the numpy count; the device driver passes its own."""
+    return grid_spec.bisect(count_fn if count_fn is not None else (lambda G: count(verts, faces, G)), max_faces)
 
 
 def simplify_budget(verts, faces, max_faces, placement='quadric'):

@@ -12,6 +12,7 @@ import torch
 
 import cloud_spec as S
 from golden_util import GOLDEN, REPO
+from grid_spec import wall_clouds
 from test_cloud_cpu import ABC, planted, write_las
 
 pytestmark = pytest.mark.gpu
@@ -25,11 +26,7 @@ def _abc():
 
 
 def _voxel_cases():
-    rng = np.random.RandomState(21)
-    rand = (rng.rand(50000, 3) * np.array([1.0, 0.6, 0.3]) - 0.5).astype(np.float32)
-    # exact duplicates and points exactly on cell walls: multiples of 1/8 are exact in float32, walls of the h = 0.125 and h = 0.25 grids
-    lattice = (rng.randint(0, 17, size=(4000, 3)) / 8.0).astype(np.float32)
-    dup = np.concatenate([lattice, lattice[:1000], (rng.rand(3000, 3) * 2.0).astype(np.float32)])
+    rand, dup = wall_clouds()                                    # exact duplicates and points exactly on cell walls
     # two points of one cell at exactly the same distance from its centre (0.25, 0.25, 0.25), the farther index first in memory order
     tie = np.array([[0.375, 0.25, 0.25], [0.125, 0.25, 0.25], [0.125, 0.25, 0.25], [0.0, 0.0, 0.0], [1.0, 1.0, 1.0], [0.5, 0.5, 0.5]], dtype=np.float32)
     return {'random': (rand, [0.25, 0.031, 0.0047, 0.0009]), 'abc': (_abc(), [0.2, 0.02, 0.004]),

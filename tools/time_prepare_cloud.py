@@ -70,7 +70,7 @@ def main():
     kept = pts[sel].contiguous()
     print('{} points, budget {}: G {} h {:.6g} kept {}; table of {} slots'.format(args.points, args.budget, G, float(h), sel.shape[0], grid.capacity))
     lib, st = cloud._lib.lib(), torch.cuda.current_stream().cuda_stream
-    lo, hi = cloud._f3(grid.lo), cloud._f3(grid.hi)
+    lo, hi = grid._vec3(grid.lo), grid._vec3(grid.hi)
     grid._scratch(best=True)
     keep = torch.empty(grid.n, dtype=torch.uint8, device=dev)
 

@@ -31,6 +31,31 @@ extern "C" {
 int ppsx_blend_rgba_u8(const int64_t* idx, const float* d2, int64_t m, int k, const uint8_t* rgba, int64_t n, double eps, uint8_t* out,
                        void* stream);
 
+/* ---- trim by support: faces of a mesh that a scan point stands for (csrc/pps_trim.hip) ------------------------------------------------------
+ * new capability: replaces nothing -- the reference closes every surface.  Driven by ppsurf_amd/trim.py; the rule is written out at the top
+ * of csrc/pps_trim.hip and in DESIGN.md section 15.  lo, hi are HOST arrays of three floats (the cloud's box), h, inv_h the cell edge and
+ * 1 / h of the grid of csrc/pps_cells.h, table uint64 [capacity] with capacity a power of two > n.
+ *   ppsx_trim_cell_slots    slot int64 [n]: the table slot of the cell of every point of pts f32 [n,3]; fills table.  Which slot a cell gets
+ *                           depends on timing, which points share a slot does not.  A NULL pointer, n < 1, a capacity that is no power of
+ *                           two > n, or a grid the rule of pps_cells.h refuses (h or inv_h not > 0, hi < lo, more than 2^20 cells along an
+ *                           axis): PPS_ERR_ARG, nothing is launched or written.
+ *   ppsx_trim_face_support  support u8 [nf]: 1 when the face faces[f] = (i0, i1, i2) int64 of verts f32 [nv,3] has every index in [0, nv),
+ *                           finite corners and a point p of pts f32 [n,3] with d2(p, triangle) <= r * r, else 0; d2 is the squared
+ *                           distance to the closest point of the triangle in fp64 (closest_on_triangle<double> of csrc/pps_tri.h on the
+ *                           widened inputs, every operation rounded on its own).  order int64 [n] lists the points sorted by slot, offsets
+ *                           int64 [capacity + 1] the start of every slot's run in it (table, slots from ppsx_trim_cell_slots with the same
+ *                           lo, hi, h, inv_h, capacity).  A pure function of (pts, verts, faces, r): it does not depend on h, capacity,
+ *                           slots or the launch; one wave per face, no atomics.  Indices outside [0, nv) are never read through, and
+ *                           entries of offsets / order outside [0, n] / [0, n) are skipped.
+ *                           nf < 0, nv < 0, n < 0, r not finite or not > 0, h < r, or -- with nf > 0 and n > 0 -- a NULL pointer, a bad
+ *                           capacity or a refused grid: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *                           n == 0 (nf > 0, support not NULL): 0, support is zeroed. */
+int ppsx_trim_cell_slots(const float* pts, int64_t n, const float* lo, const float* hi, float h, float inv_h, uint64_t* table, int64_t capacity,
+                         int64_t* slot, void* stream);
+int ppsx_trim_face_support(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* pts, int64_t n, const float* lo,
+                           const float* hi, float h, float inv_h, const uint64_t* table, int64_t capacity, const int64_t* order,
+                           const int64_t* offsets, double r, uint8_t* support, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 //
 // Closest point -- replaces source/base/proximity.py:20-36 (trimesh.proximity.closest_point in batches of 1000 on the CPU), called from
 // source/base/visualization.py:91-93.  Point-triangle closest point by Voronoi-region classification (Ericson, Real-Time Collision
-// Detection, 5.1.5).  A face with |e1 x e2|^2 <= 1e-12 |e1|^2 |e2|^2 (zero or next to zero area) is its longest edge.  Pass 1 picks, per
+// Detection, 5.1.5; in pps_tri.h).  A face with |e1 x e2|^2 <= 1e-12 |e1|^2 |e2|^2 (zero or next to zero area) is its longest edge.  Pass 1 picks, per
 // query and face slice, the smallest squared distance, ties to the lowest face: in fp32 (the interior region measured as the plane
 // distance (ap.n)^2 / n.n), or in fp64 for a thin face (height below 0.1 x its longest edge), whose fp32 region tests are unreliable.
 // Pass 2 takes the minimum over the slices in slice order (ties to the lower face again) and recomputes distance and closest point of
@@ -30,70 +30,13 @@
 
 #include "pps_common.h"
 #include "pps_sweep.h"
+#include "pps_tri.h"
 #include "../../include/ppsurf_amd.h"
 
 namespace {
 
 constexpr float NEAR = 0.01f;
 constexpr float SLIVER = 0.01f;                               // |e1 x e2|^2 < SLIVER lmax^4 (height < 0.1 x longest edge): pass 1 in fp64
-
-template <typename T> struct V3 { T x, y, z; };
-template <typename T> __host__ __device__ __forceinline__ V3<T> sub(V3<T> a, V3<T> b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-template <typename T> __host__ __device__ __forceinline__ T dot(V3<T> a, V3<T> b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-template <typename T> __host__ __device__ __forceinline__ V3<T> cross(V3<T> a, V3<T> b) {
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-template <typename T> __device__ __forceinline__ T clamp01(T v) { return v < T(0) ? T(0) : (v > T(1) ? T(1) : v); }
-
-// Closest point of p on triangle (a, b, c) as a + s ab + t ac; d2 = its squared distance (the interior region as the plane distance).
-template <typename T>
-__device__ __forceinline__ void closest_on_triangle(V3<T> p, V3<T> a, V3<T> b, V3<T> c, T& s, T& t, T& d2) {
-    const V3<T> ab = sub(b, a), ac = sub(c, a), bc = sub(c, b);
-    const V3<T> n = cross(ab, ac);
-    const T nn = dot(n, n), lab = dot(ab, ab), lac = dot(ac, ac);
-    if (!(nn > T(1e-12) * (lab * lac))) {                     // degenerate: the longest edge (face-uniform branch)
-        const T lbc = dot(bc, bc);
-        V3<T> o = a, e = ab;
-        T le = lab;
-        int which = 0;
-        if (lac > le) { e = ac; le = lac; which = 1; }
-        if (lbc > le) { o = b; e = bc; le = lbc; which = 2; }
-        const T u = le > T(0) ? clamp01(dot(sub(p, o), e) / le) : T(0);
-        s = which == 0 ? u : (which == 1 ? T(0) : T(1) - u);
-        t = which == 0 ? T(0) : u;
-        const V3<T> q = {o.x + u * e.x, o.y + u * e.y, o.z + u * e.z};
-        const V3<T> dq = sub(p, q);
-        d2 = dot(dq, dq);
-        return;
-    }
-    const V3<T> ap = sub(p, a), bp = sub(p, b), cp = sub(p, c);
-    const T d1 = dot(ab, ap), d2_ = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
-    const T vc = d1 * d4 - d3 * d2_, vb = d5 * d2_ - d1 * d6, va = d3 * d6 - d5 * d4;
-    bool interior = false;
-    if (d1 <= T(0) && d2_ <= T(0)) { s = T(0); t = T(0); }                                    // vertex a
-    else if (d3 >= T(0) && d4 <= d3) { s = T(1); t = T(0); }                                  // vertex b
-    else if (vc <= T(0) && d1 >= T(0) && d3 <= T(0)) { s = clamp01(d1 / (d1 - d3)); t = T(0); }   // edge ab
-    else if (d6 >= T(0) && d5 <= d6) { s = T(0); t = T(1); }                                  // vertex c
-    else if (vb <= T(0) && d2_ >= T(0) && d6 <= T(0)) { s = T(0); t = clamp01(d2_ / (d2_ - d6)); }  // edge ac
-    else if (va <= T(0) && (d4 - d3) >= T(0) && (d5 - d6) >= T(0)) {                           // edge bc
-        const T w = clamp01((d4 - d3) / ((d4 - d3) + (d5 - d6)));
-        s = T(1) - w; t = w;
-    } else {                                                                                  // interior
-        const T den = va + vb + vc;
-        s = den > T(0) ? clamp01(vb / den) : T(0);
-        t = den > T(0) ? clamp01(vc / den) : T(0);
-        if (s + t > T(1)) { const T k = T(1) / (s + t); s *= k; t *= k; }
-        interior = true;
-    }
-    if (interior) {
-        const T h = dot(ap, n);
-        d2 = h * h / nn;
-    } else {
-        const V3<T> q = {(a.x + s * ab.x) + t * ac.x, (a.y + s * ab.y) + t * ac.y, (a.z + s * ab.z) + t * ac.z};
-        const V3<T> dq = sub(p, q);
-        d2 = dot(dq, dq);
-    }
-}
 
 // Pass 1 (pps_sweep.h): the smallest squared distance of every query over the faces of its slice.  Strict < keeps the lowest face of equal
 // distance; face -1 means no finite distance in the slice.  The face is classified once for the lane's whole tile.  The running minimum

@@ -167,6 +167,15 @@ def simplify_clean(verts: torch.Tensor, faces: torch.Tensor, max_faces: int):
     return small_components_removed(verts, faces)
 
 
+def trim_supported(cloud: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, factor: float, spacing_k=8):
+    """The trim by support of a written mesh, in model space against the points the network saw: radius = float64(factor) x the cloud's
+    spacing, unsupported faces dropped, then the small-component rule and the compaction (ppsurf_amd/trim.py).  Device tensors in and out."""
+    from . import trim
+    spacing = trim.cloud_spacing(cloud, spacing_k)
+    verts, faces, _ = trim.trim_mesh(cloud, verts, faces, float(np.float64(factor) * np.float64(spacing)), spacing=spacing)
+    return verts, faces
+
+
 def small_components_removed(verts: torch.Tensor, faces: torch.Tensor, min_component_faces=6):
     """Faces of connected components of at most `min_component_faces` faces dropped (pps_mesh_small_components), unreferenced vertices
     dropped, order kept: the last stage of mcubes.clean_mesh_torch without its merging by position."""
@@ -180,11 +189,13 @@ def small_components_removed(verts: torch.Tensor, faces: torch.Tensor, min_compo
 def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts_raw_ms, resolution: int, padding=0, mc_value=0,
                                                       num_pts=50000, num_pts_local=None, refine_iter=10, input_points=None,
                                                       out_value=np.nan, dilation_size=2, prog_bar=None, pc_file_in: str = 'unknown',
-                                                      max_faces=None):
+                                                      trim_factor=None, max_faces=None):
     """poco_utils.py:26-175.  Returns (vertices float32 [V,3], faces int64 [F,3]) in model space, or None when the occupancy
     never crosses `mc_value`.  (The reference wraps the same arrays into a trimesh.Trimesh; ppsurf_amd.meshio writes PLY.)
     `max_faces` (not in the reference): a face budget; the cleaned mesh is simplified to it on the device (ppsurf_amd/simplify.py) and passes
-    the small-component rule once more."""
+    the small-component rule once more.
+    `trim_factor` (not in the reference): faces without a point of latent['pts'] within trim_factor x the cloud's spacing are dropped before
+    that (ppsurf_amd/trim.py); None when no face survives."""
     if latent['pts'].shape[0] != 1:
         raise ValueError('Reconstruction must be done with batch size = 0!')     # message kept from poco_utils.py:50
     progress = None
@@ -208,6 +219,10 @@ def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts
     verts, faces = mcubes.clean_mesh_torch(verts, faces, min_component_faces=6, welded=True, grid_coords=True)
     verts = refine_vertices(lambda q: sharding.sharded_map(field, q), verts, volume, step, bmin_pad, refine_iter, progress)
     verts, faces = mcubes.clean_mesh_torch(verts, faces, min_component_faces=6, welded=True, grid_coords=False)
+    if trim_factor is not None:
+        verts, faces = trim_supported(field.pts, verts.to(torch.float32), faces, float(trim_factor))
+        if faces.shape[0] == 0:
+            return None
     if max_faces is not None:
         # on the float32 vertices this function returns: the result is the one `python -m ppsurf_amd.simplify` gives on the unsimplified output
         verts, faces = simplify_clean(verts.to(torch.float32), faces, int(max_faces))

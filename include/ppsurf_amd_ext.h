@@ -56,6 +56,28 @@ int ppsx_trim_face_support(const float* verts, int64_t nv, const int64_t* faces,
                            const float* hi, float h, float inv_h, const uint64_t* table, int64_t capacity, const int64_t* order,
                            const int64_t* offsets, double r, uint8_t* support, void* stream);
 
+/* ---- Taubin lambda|mu smoothing of a mesh (csrc/pps_smooth.hip) ----------------------------------------------------------------------------
+ * new capability: replaces nothing -- the reference has no smoothing.  Driven by ppsurf_amd/smooth.py; the rule is written out at the top of
+ * csrc/pps_smooth.hip and in DESIGN.md section 16.
+ *   ppsx_smooth_half_edges  keys int64 [6 nf]: per face (a, b, c) of faces int64 [nf,3] the half-edges a->b, b->a, b->c, c->b, c->a, a->c as
+ *                           (src << 32) | dst.  A face with an index outside [0, nv) or two equal indices is invalid: its six keys are
+ *                           INT64_MAX, so they sort last.  nv <= 2^31 - 1 keeps every other key positive.
+ *                           nf < 0, nv < 0, nv > 2^31 - 1, or a NULL pointer with nf > 0: PPS_ERR_ARG, nothing is launched or written.
+ *                           nf == 0: 0, nothing is launched.
+ *   ppsx_smooth_pass        out f64 [nv,3]: one Jacobi pass with factor s over x f64 [nv,3].  Row i of the adjacency is the entries
+ *                           offsets[i] .. offsets[i + 1] - 1 (offsets int64 [nv + 1]) of nbr int32 [ne] (the neighbours, ascending) and
+ *                           mult int32 [ne] (the number of valid faces on the edge).  A row with an entry of multiplicity 1 belongs to a
+ *                           border vertex and admits only its entries of multiplicity 1; any other row admits all.  Per component in fp64,
+ *                           in row order, every operation rounded on its own: acc = 0.0; acc = acc + x[j]; m = acc / double(count);
+ *                           out[i] = x[i] + s * (m - x[i]).  A vertex that admits no neighbour: out[i] = x[i].  A pure function of its
+ *                           inputs: one thread per vertex, no atomics.  A row whose offsets are not 0 <= offsets[i] <= offsets[i + 1] <= ne
+ *                           is skipped whole and a neighbour outside [0, nv) is skipped; neither is read through.
+ *                           nv < 0, ne < 0, s not finite, out == x, or -- with nv > 0 -- a NULL x, offsets or out, or with ne > 0 a NULL
+ *                           nbr or mult: PPS_ERR_ARG, nothing is launched or written.  nv == 0: 0, nothing is launched. */
+int ppsx_smooth_half_edges(const int64_t* faces, int64_t nf, int64_t nv, int64_t* keys, void* stream);
+int ppsx_smooth_pass(const double* x, int64_t nv, const int64_t* offsets, const int32_t* nbr, const int32_t* mult, int64_t ne, double s,
+                     double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

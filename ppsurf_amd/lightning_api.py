@@ -88,8 +88,13 @@ class PocoModel(_Base):
 
     def __init__(self, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir, padding_factor, name,
                  network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global, rec_batch_size,
-                 gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_trim_factor=None):
+                 gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_trim_factor=None, gen_smooth_iters=None):
         super().__init__()
+        if gen_smooth_iters is not None:
+            n = float(gen_smooth_iters)
+            if not (math.isfinite(n) and n == int(n) and 1 <= n <= 1000):
+                raise ValueError('gen_smooth_iters must be an integer in 1..1000 (Taubin iterations), got {}'.format(gen_smooth_iters))
+        self.gen_smooth_iters = None if gen_smooth_iters is None else int(float(gen_smooth_iters))   # smoothing (ppsurf_amd/smooth.py)
         if gen_trim_factor is not None and not (math.isfinite(float(gen_trim_factor)) and float(gen_trim_factor) > 0):
             raise ValueError('gen_trim_factor must be a finite number > 0 (support radius in units of the cloud\'s spacing), got {}'.format(gen_trim_factor))
         self.gen_trim_factor = None if gen_trim_factor is None else float(gen_trim_factor)   # trim by support (ppsurf_amd/trim.py)
@@ -464,7 +469,8 @@ class PocoModel(_Base):
             resolution=self.gen_resolution_global, padding=1, mc_value=0, num_pts=self.rec_batch_size, num_pts_local=self.num_pts_local,
             input_points=pts_cf.t().cpu().numpy(), refine_iter=self.gen_refine_iter, out_value=1, prog_bar=bar, pc_file_in=pc_file_in,
             **({} if self.gen_max_faces is None else {'max_faces': self.gen_max_faces}),
-            **({} if self.gen_trim_factor is None else {'trim_factor': self.gen_trim_factor}))
+            **({} if self.gen_trim_factor is None else {'trim_factor': self.gen_trim_factor}),
+            **({} if self.gen_smooth_iters is None else {'smooth_iters': self.gen_smooth_iters}))
         self.last_prediction = mesh
         self.last_colors = None
         if getattr(self, 'shard_queries', False) and sharding.world()[0] != 0:
@@ -517,14 +523,15 @@ class PPSurfModel(PocoModel):
 
     def __init__(self, pointnet_latent_size, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir,
                  padding_factor, name, network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global,
-                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_trim_factor=None):
+                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_trim_factor=None, gen_smooth_iters=None):
         self._pps = (num_pts_local, pointnet_latent_size)
         super().__init__(output_names=output_names, in_channels=in_channels, out_channels=out_channels, k=k, lambda_l1=lambda_l1,
                          debug=debug, in_file=in_file, results_dir=results_dir, padding_factor=padding_factor, name=name,
                          workers=workers, rec_batch_size=rec_batch_size, gen_refine_iter=gen_refine_iter,
                          gen_subsample_manifold=gen_subsample_manifold, gen_resolution_global=gen_resolution_global,
                          gen_subsample_manifold_iter=gen_subsample_manifold_iter, network_latent_size=network_latent_size,
-                         gen_max_faces=gen_max_faces, gen_color_k=gen_color_k, gen_trim_factor=gen_trim_factor)
+                         gen_max_faces=gen_max_faces, gen_color_k=gen_color_k, gen_trim_factor=gen_trim_factor,
+                         gen_smooth_iters=gen_smooth_iters)
         self.num_pts_local, self.pointnet_latent_size = num_pts_local, pointnet_latent_size
 
     def _make_network(self):

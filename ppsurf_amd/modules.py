@@ -459,12 +459,12 @@ class PocoNetwork(_Base):
         if pts.shape[0] > 1:                               # validation batches: all shapes stacked along the rows, one decoder call
             b, n, q = pts.shape[0], pts.shape[2], ptq.shape[2]
             ids = data['proj_ids'] if has_proj_ids else spatial.knn(pts, ptq, k)
-            flat = (ids + (torch.arange(b, device=dev) * n).view(b, 1, 1)).reshape(b * q, -1).contiguous()
+            flat = (ids + (torch.arange(b, device=dev) * n).view(b, 1, 1)).reshape(b * q, ids.shape[2]).contiguous()
             table = torch.cat([plan.point_table(data['latents'][i]) for i in range(b)])
             lg = plan.decode(table, pts.transpose(1, 2).reshape(b * n, 3).contiguous().float(),
                              ptq.transpose(1, 2).reshape(b * q, 3).contiguous().float(), flat)
             data['proj_ids'] = ids
-            return lg.view(b, q, -1).transpose(1, 2)
+            return lg.view(b, q, plan.nout).transpose(1, 2)          # (widths written out: -1 cannot be inferred for q = 0)
         logits, ids_all = [], []
         for b in range(pts.shape[0]):
             pts_pm, q_pm = pts[b].t().contiguous().float(), ptq[b].t().contiguous().float()

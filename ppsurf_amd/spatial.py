@@ -30,6 +30,8 @@ def knn(points: torch.Tensor, support_points: torch.Tensor, k: int, workers: int
     (poco_utils.py:259-260).  `workers` is accepted and ignored, as the reference ignores it for pykdtree."""
     k = min(int(k), points.shape[2])
     nb = points.shape[0]
+    if support_points.shape[2] == 0:          # no query: nothing to search for (the batched entry refuses an empty task)
+        return torch.empty((nb, 0, k), dtype=torch.int64, device=points.device)
     if k <= 64 and nb > 1 and points.is_cuda:          # a fit batch: all shapes in one launch
         out = ops.knn_batch_point_major([_point_major(points[b]) for b in range(nb)], [_point_major(support_points[b]) for b in range(nb)],
                                         [k] * nb)

@@ -87,3 +87,20 @@ def decode(w, latents_cn, pts, query, idx, patches):
     hh = relu(pooled @ unpack_dense(wa, 256, 256).T + xbar @ unpack_dense(wb, 256, 128).T + bt[0])
     hh = relu(hh @ unpack_dense(l2w, 256, 256).T + bt[1])
     return hh @ unpack_dense(l3w, 2, 256).T + bt[2][:2], trans2
+
+
+def poco_head(plan_w, plan_b, plan_tail, g_w, g_b, c, nout, latents_cn, pts, query, idx):
+    """Packed images of PocoDecoderPlan (w, b, tail, g_w, g_b; pps_decode.hip: weights [xyz 64 CB][fc2 256 CB^2][fc3 256 CB^2][fcq 1024 CB],
+    CB = c / 16; bias [c][c][64]; tail [nout][c] then [nout]); latents_cn [c,N]; pts [N,3]; query [Q,3]; idx [Q,k] -> logits [Q,nout] (float64)."""
+    cb = c // 16
+    xyz, fc2, fc3, fcq = _split(np.asarray(plan_w), [64 * cb, 256 * cb * cb, 256 * cb * cb, 1024 * cb])
+    b2, b3, bq = _split(np.asarray(plan_b, dtype=np.float64), [c, c, 64])
+    tw, tb = _split(np.asarray(plan_tail, dtype=np.float64), [nout * c, nout])
+    G = latents_cn.T.astype(np.float64) @ unpack_dense(g_w, c, c).T + np.asarray(g_b, dtype=np.float64)
+    rel = query[:, None, :].astype(np.float64) - pts[idx]
+    h = relu(G[idx] + rel @ unpack_xyz(xyz, c).T)
+    h = relu(h @ unpack_dense(fc2, c, c).T + b2)
+    h = relu(h @ unpack_dense(fc3, c, c).T + b3)
+    att = softmax(h @ unpack_dense(fcq, 64, c).T + bq, axis=1).mean(axis=2)           # [Q,k]
+    pooled = (att[:, :, None] * h).sum(axis=1)
+    return pooled @ tw.reshape(nout, c).T + tb

@@ -271,12 +271,8 @@ def test_poco_head_both_dtypes_and_range_guard(c):
     (source/poco_model.py:381-419); then latents scaled until the hidden activations leave the f16 range: the split-precision kernel raises the guard
     word, the fp32 kernel queued behind it recomputes the call on the device and the result IS the fp32 kernel's."""
     from ppsurf_amd.decoder import PocoDecoderPlan
-    rng = np.random.default_rng(100 + c)
-    shapes = {'fc1': (c, c + 3), 'fc2': (c, c), 'fc3': (c, c), 'fc_query': (64, c), 'fc_value': (c, c), 'fc8': (2, c)}
-    sd = {}
-    for name, (o, i) in shapes.items():
-        sd['projection.{}.weight'.format(name)] = torch.from_numpy((rng.standard_normal((o, i, 1, 1)) * (1.4 / np.sqrt(i))).astype(np.float32))
-        sd['projection.{}.bias'.format(name)] = torch.from_numpy((rng.standard_normal(o) * 0.1).astype(np.float32))
+    from poco_head_spec import head_state_dict
+    sd = head_state_dict(c, 2, seed=100 + c)              # the draws this test has always used
     cloud = make_cloud(3000, seed=c)
     qry = (cloud[::7][:300] + 0.004).astype(np.float32)
     pts, qd = torch.from_numpy(cloud).to(DEV), torch.from_numpy(qry).to(DEV)

@@ -78,6 +78,41 @@ int ppsx_smooth_half_edges(const int64_t* faces, int64_t nf, int64_t nv, int64_t
 int ppsx_smooth_pass(const double* x, int64_t nv, const int64_t* offsets, const int32_t* nbr, const int32_t* mult, int64_t ne, double s,
                      double* out, void* stream);
 
+/* ---- oriented normals: per vertex on a mesh, per point on a scan (csrc/pps_normals.hip) -----------------------------------------------------
+ * new capability: replaces nothing -- the reference writes positions only.  Driven by ppsurf_amd/normals.py; the rule is written out at the
+ * top of csrc/pps_normals.hip and in DESIGN.md section 17.  A face is valid when its three indices lie in [0, nv) and are pairwise distinct.
+ *   ppsx_normals_corner_keys  keys int64 [3 nf]: per face t = (a, b, c) of faces int64 [nf,3] the keys (a << 32) | t, (b << 32) | t,
+ *                             (c << 32) | t, in that order; INT64_MAX three times for an invalid face, so those sort last.  nv, nf <= 2^31 - 1
+ *                             keeps every other key positive and distinct: sorted, they list every vertex's faces in ascending face index.
+ *                             nf < 0, nv < 0, nf or nv > 2^31 - 1, or a NULL pointer with nf > 0: PPS_ERR_ARG, nothing is launched or
+ *                             written.  nf == 0: 0, nothing is launched.
+ *   ppsx_normals_vertex       out f32 [nv,3]: the normal of every vertex of verts f32 [nv,3].  Row i of the incidence is the entries
+ *                             offsets[i] .. offsets[i + 1] - 1 (offsets int64 [nv + 1]) of inc int32 [ni], the faces that hold vertex i.  Per
+ *                             vertex, in fp64 on the widened coordinates, in row order, every operation rounded on its own: acc = (0, 0, 0);
+ *                             for a face t with i at corner p, n the next corner cyclically and q the one after: e1 = V[n] - V[i],
+ *                             e2 = V[q] - V[i], g = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x); weight 0 (area):
+ *                             acc = acc + g; weight 1 (max): d = ((e1x^2 + e1y^2) + e1z^2) * ((e2x^2 + e2y^2) + e2z^2), acc = acc + g / d
+ *                             when d > 0 and finite, else the face adds nothing.  L = sqrt((accx^2 + accy^2) + accz^2); out[i] =
+ *                             f32(acc / L) when L > 0 and finite, else (0, 0, 0).  A pure function of its inputs: one thread per vertex, no
+ *                             atomics.  A row whose offsets are not 0 <= offsets[i] <= offsets[i + 1] <= ni yields (0, 0, 0); an entry of inc
+ *                             outside [0, nf), an invalid face and a face that does not hold i are skipped; none is read through.
+ *                             nv < 0, nf < 0, ni < 0, nv or nf > 2^31 - 1, weight not 0 or 1, or -- with nv > 0 -- a NULL verts, offsets or
+ *                             out, a NULL faces with nf > 0 or a NULL inc with ni > 0: PPS_ERR_ARG, nothing is launched or written.
+ *                             nv == 0: 0, nothing is launched.  nf == 0 or ni == 0 (nv > 0): out is all zeros.
+ *   ppsx_normals_blend        out f32 [m,3]: the inverse-squared-distance blend of the normals f32 [nv,3] of the k neighbours idx int64 [m,k]
+ *                             with squared distances d2 f32 [m,k] (ops.KnnBlocks.query(..., return_d2=True)).  Per row, in fp64, j = 0..k-1 in
+ *                             column order, every operation rounded on its own: a neighbour counts when 0 <= idx[i,j] < nv;
+ *                             w = 1 / (double(d2[i,j]) + eps); T[c] = T[c] + w * double(normals[idx[i,j], c]).  L = sqrt((Tx^2 + Ty^2) + Tz^2);
+ *                             out[i] = f32(T / L) when L > 0 and finite, else (0, 0, 0).  A pure function of its inputs: one thread per row,
+ *                             no atomics.  Indices outside [0, nv) are skipped, never read through.
+ *                             m < 0, nv < 0, k outside 1..256, eps not > 0, or -- with m > 0 -- a NULL idx, d2 or out, or a NULL normals with
+ *                             nv > 0: PPS_ERR_ARG, nothing is launched or written.  m == 0: 0, nothing is launched. */
+int ppsx_normals_corner_keys(const int64_t* faces, int64_t nf, int64_t nv, int64_t* keys, void* stream);
+int ppsx_normals_vertex(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* offsets, const int32_t* inc, int64_t ni,
+                        int weight, float* out, void* stream);
+int ppsx_normals_blend(const int64_t* idx, const float* d2, int64_t m, int k, const float* normals, int64_t nv, double eps, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -517,6 +517,54 @@ def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8
         f.write(frec.tobytes())
 
 
+def write_ply_mesh_normals(path, verts: np.ndarray, faces: np.ndarray, normals: np.ndarray, colors_u8: np.ndarray = None, double=False):
+    """Binary little-endian PLY mesh with per-vertex normals: `x y z nx ny nz [red green blue alpha]`.  The normals
+    are always `float`; double=True stores `property double x/y/z` as in write_ply_mesh; colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    ftype = '<f8' if double else '<f4'
+    verts = np.asarray(verts, dtype=ftype).reshape(-1, 3)
+    faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
+    fields = [('p', ftype, (3,)), ('n', '<f4', (3,))]
+    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {1} x\nproperty {1} y\nproperty {1} z\n'
+              'property float nx\nproperty float ny\nproperty float nz\n').format(verts.shape[0], 'double' if double else 'float')
+    if colors_u8 is not None:
+        colors = np.asarray(colors_u8, dtype=np.uint8).reshape(verts.shape[0], -1)
+        if colors.shape[1] == 3:
+            colors = np.concatenate([colors, np.full((colors.shape[0], 1), 255, dtype=np.uint8)], axis=1)
+        fields.append(('c', 'u1', (4,)))
+        header += 'property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n'
+    header += 'element face {}\nproperty list uchar int vertex_indices\nend_header\n'.format(faces.shape[0])
+    vrec = np.empty(verts.shape[0], dtype=fields)
+    vrec['p'] = verts
+    vrec['n'] = np.asarray(normals, dtype='<f4').reshape(verts.shape[0], 3)
+    if colors_u8 is not None:
+        vrec['c'] = colors[:, :4]
+    frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    frec['n'] = 3
+    frec['v'] = faces
+    with open(path, 'wb') as f:
+        f.write(header.encode('ascii'))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
+def write_ply_points_normals(path, pts: np.ndarray, normals: np.ndarray, double=False):
+    """Binary little-endian PLY point cloud `x y z nx ny nz` with zero faces: the layout read_ply_vertices returns as [n,6].  The normals are
+    always `float`; double=True stores `property double x/y/z`."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    ftype = '<f8' if double else '<f4'
+    pts = np.asarray(pts, dtype=ftype).reshape(-1, 3)
+    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {1} x\nproperty {1} y\nproperty {1} z\n'
+              'property float nx\nproperty float ny\nproperty float nz\nelement face 0\nproperty list uchar int vertex_indices\n'
+              'end_header\n').format(pts.shape[0], 'double' if double else 'float')
+    rec = np.empty(pts.shape[0], dtype=[('p', ftype, (3,)), ('n', '<f4', (3,))])
+    rec['p'] = pts
+    rec['n'] = np.asarray(normals, dtype='<f4').reshape(pts.shape[0], 3)
+    with open(path, 'wb') as f:
+        f.write(header.encode('ascii'))
+        f.write(rec.tobytes())
+
+
 def read_obj_mesh(path, colors=False):
     """Vertices float32 [nv,3] and triangles int32 [nf,3] of a Wavefront OBJ: `v x y z` and `f` lines only (`a`, `a/b`, `a//c`, `a/b/c`
     corners, 1-based or negative (relative) indices, polygons fan-triangulated).  Raises ValueError on an index outside the vertices.

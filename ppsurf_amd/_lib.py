@@ -102,6 +102,13 @@ def need_device(what, *tensors):
     return dev
 
 
+def need_gpu(what, device=None):
+    """PpsError unless a GPU is there (and `device`, where given, names one): the guard of the command lines and of the functions that upload
+    host arrays."""
+    if (device is not None and torch.device(device).type != 'cuda') or not torch.cuda.is_available():
+        raise PpsError('{} runs on the GPU only{}; there is no CPU fallback'.format(what, '' if device is None else ' (device={!r})'.format(str(device))))
+
+
 _PLAIN = frozenset((int, float, bool, type(None)))
 
 

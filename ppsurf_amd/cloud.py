@@ -121,8 +121,7 @@ def prepare_cloud(pts, max_points=None, voxel_size=None, outlier_k=0, outlier_ra
             xyz = xyz - (xyz.min(dim=0)[0] + xyz.max(dim=0)[0]) * 0.5
         n_in = int(pts.shape[0])
     else:
-        if torch.device(device).type != 'cuda' or not torch.cuda.is_available():
-            raise _lib.PpsError('prepare_cloud runs on the GPU only (device={!r}); there is no CPU fallback'.format(str(device)))
+        _lib.need_gpu('prepare_cloud', device)
         arr = np.asarray(pts)
         if arr.dtype.kind != 'f':
             arr = arr.astype(np.float64)

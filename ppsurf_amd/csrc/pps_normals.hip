@@ -4,7 +4,8 @@
 // ppsurf_amd/normals.py; restated in numpy by tests/normals_spec.py, which the kernels match bit for bit.
 //
 // Rule A, vertex normals: vertices V f32 [nv,3], faces int64 [nf,3], weight 'area' (0) or 'max' (1).
-//   valid face    its three indices lie in [0, nv) and are pairwise distinct.  Invalid faces take no part and are never read through.
+//   valid face    its three indices lie in [0, nv) and are pairwise distinct (face_valid of pps_faces.h).  Invalid faces take no part and are
+//                 never read through.
 //   incidence     a valid face t = (a, b, c) contributes the keys (a << 32) | t, (b << 32) | t, (c << 32) | t, an invalid one INT64_MAX three
 //                 times (nv, nf <= 2^31 - 1).  The keys are distinct, so the sorted keys without the sentinel list every vertex's faces in
 //                 ASCENDING FACE INDEX whatever the sort; a duplicated face sits in the row twice and counts twice.
@@ -32,11 +33,10 @@
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_faces.h"
 #include "../../include/ppsurf_amd_ext.h"
 
 namespace {
-
-constexpr int64_t SENTINEL = INT64_MAX;                     // the keys of an invalid face: they sort last
 
 __device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v < (double)INFINITY; }          // false for a NaN
 
@@ -53,11 +53,11 @@ __global__ __launch_bounds__(256) void corner_keys_kernel(const int64_t* __restr
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= nf) return;
     const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const bool valid = a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv && a != b && b != c && c != a;
+    const bool valid = face_valid(a, b, c, nv);
     int64_t* k = keys + 3 * f;
-    k[0] = valid ? (a << 32) | f : SENTINEL;
-    k[1] = valid ? (b << 32) | f : SENTINEL;
-    k[2] = valid ? (c << 32) | f : SENTINEL;
+    k[0] = valid ? (a << 32) | f : KEY_SENTINEL;
+    k[1] = valid ? (b << 32) | f : KEY_SENTINEL;
+    k[2] = valid ? (c << 32) | f : KEY_SENTINEL;
 }
 
 __global__ __launch_bounds__(256) void vertex_kernel(const float* __restrict__ verts, int64_t nv, const int64_t* __restrict__ faces, int64_t nf,
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void vertex_kernel(const float* __restrict__ v
             const int64_t t = inc[e];
             if (t < 0 || t >= nf) continue;
             const int64_t a = faces[3 * t], b = faces[3 * t + 1], c = faces[3 * t + 2];
-            if (!(a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv && a != b && b != c && c != a)) continue;
+            if (!face_valid(a, b, c, nv)) continue;
             int64_t n, q;
             if (a == i) { n = b; q = c; }
             else if (b == i) { n = c; q = a; }

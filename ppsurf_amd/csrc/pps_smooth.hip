@@ -4,7 +4,8 @@
 // tests/smooth_spec.py, which the kernels match bit for bit.
 //
 // Rule: vertices V f32 [nv,3], faces int64 [nf,3], iters >= 0, lam, mu (fp64).
-//   valid face    its three indices lie in [0, nv) and are pairwise distinct.  Invalid faces take no part and are never read through.
+//   valid face    its three indices lie in [0, nv) and are pairwise distinct (face_valid of pps_faces.h).  Invalid faces take no part and are
+//                 never read through.
 //   half-edges    a valid face (a, b, c) contributes a->b, b->a, b->c, c->b, c->a, a->c.  The multiplicity c(i->j) is the number of times
 //                 i->j occurs = the number of valid faces that hold the edge {i, j} (a duplicated face counts twice).
 //   border        an edge of multiplicity 1 is a border edge; a vertex with at least one border half-edge is a border vertex.
@@ -27,24 +28,23 @@
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_faces.h"
 #include "../../include/ppsurf_amd_ext.h"
 
 namespace {
-
-constexpr int64_t SENTINEL = INT64_MAX;                     // the keys of an invalid face: they sort last
 
 __global__ __launch_bounds__(256) void half_edges_kernel(const int64_t* __restrict__ faces, int64_t nf, int64_t nv, int64_t* __restrict__ keys) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (f >= nf) return;
     const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const bool valid = a >= 0 && a < nv && b >= 0 && b < nv && c >= 0 && c < nv && a != b && b != c && c != a;
+    const bool valid = face_valid(a, b, c, nv);
     int64_t* k = keys + 6 * f;
-    k[0] = valid ? (a << 32) | b : SENTINEL;
-    k[1] = valid ? (b << 32) | a : SENTINEL;
-    k[2] = valid ? (b << 32) | c : SENTINEL;
-    k[3] = valid ? (c << 32) | b : SENTINEL;
-    k[4] = valid ? (c << 32) | a : SENTINEL;
-    k[5] = valid ? (a << 32) | c : SENTINEL;
+    k[0] = valid ? (a << 32) | b : KEY_SENTINEL;
+    k[1] = valid ? (b << 32) | a : KEY_SENTINEL;
+    k[2] = valid ? (b << 32) | c : KEY_SENTINEL;
+    k[3] = valid ? (c << 32) | b : KEY_SENTINEL;
+    k[4] = valid ? (c << 32) | a : KEY_SENTINEL;
+    k[5] = valid ? (a << 32) | c : KEY_SENTINEL;
 }
 
 __global__ __launch_bounds__(256) void pass_kernel(const double* __restrict__ x, int64_t nv, const int64_t* __restrict__ offsets,

@@ -3,7 +3,8 @@
 // new capability: replaces nothing -- the reference closes every surface and has no trim.  Driven by ppsurf_amd/trim.py; restated in numpy by
 // tests/trim_spec.py (brute force over all pairs), which the kernel matches bit for bit.
 //
-// Rule: face f = (i0, i1, i2) is supported iff 0 <= i0, i1, i2 < nv, its nine corner coordinates are finite and some cloud point p has
+// Rule: face f = (i0, i1, i2) is supported iff 0 <= i0, i1, i2 < nv (face_in_range of pps_faces.h), its nine corner coordinates are finite
+//   and some cloud point p has
 //   d2(p, triangle) <= r * r,  d2 from closest_on_triangle<double> of pps_tri.h on the f32 inputs widened to fp64, r * r one fp64 multiply.
 // Existence does not depend on the order in which the points are visited, so support is a pure function of (points, verts, faces, r).
 //
@@ -24,6 +25,7 @@
 #include <math.h>
 
 #include "pps_cells.h"
+#include "pps_faces.h"
 #include "pps_tri.h"
 #include "../../include/ppsurf_amd_ext.h"
 
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(64 * FACES_PER_BLOCK) void face_support_kernel(cons
     if (f >= nf) return;
     const int lane = threadIdx.x & 63;
     const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    bool live = i0 >= 0 && i0 < nv && i1 >= 0 && i1 < nv && i2 >= 0 && i2 < nv;            // a bad index is never read through
+    bool live = face_in_range(i0, i1, i2, nv);                                             // a bad index is never read through
     V3<double> a = {0.0, 0.0, 0.0}, b = a, c = a;
     int c0[3] = {0, 0, 0}, cn[3] = {0, 0, 0};
     if (live) {

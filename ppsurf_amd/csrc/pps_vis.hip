@@ -29,6 +29,7 @@
 #include <math.h>
 
 #include "pps_common.h"
+#include "pps_faces.h"
 #include "pps_sweep.h"
 #include "pps_tri.h"
 #include "../../include/ppsurf_amd.h"
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256) void face_setup_kernel(const int32_t* __restri
     int32_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
     int64_t count = 0;
     float4 r0 = {0, 0, 0, 0}, r1 = {0, 0, 0, 0}, r2 = {0, 0, 0, 0};
-    if (i0 >= 0 && i0 < nv && i1 >= 0 && i1 < nv && i2 >= 0 && i2 < nv) {
+    if (face_in_range(i0, i1, i2, nv)) {
         float x0 = proj[3 * (int64_t)i0], y0 = proj[3 * (int64_t)i0 + 1], z0 = proj[3 * (int64_t)i0 + 2];
         float x1 = proj[3 * (int64_t)i1], y1 = proj[3 * (int64_t)i1 + 1], z1 = proj[3 * (int64_t)i1 + 2];
         float x2 = proj[3 * (int64_t)i2], y2 = proj[3 * (int64_t)i2 + 1], z2 = proj[3 * (int64_t)i2 + 2];

@@ -496,14 +496,7 @@ class PocoModel(_Base):
                 # geo-referenced coordinates: doubles when float32 would move a vertex by more than 1e-3 of the grid step (file units)
                 moved = np.abs(np.asarray(verts, dtype=np.float64) - np.asarray(verts, dtype=np.float32).astype(np.float64))
                 double = bool(moved.size) and float(moved.max()) > 1e-3 * float(scale) / self.gen_resolution_global
-            if normals is not None:
-                meshio.write_ply_mesh_normals(out_file_rec, verts, faces, normals, colors_u8=colors, double=double)
-            elif colors is not None:
-                meshio.write_ply_mesh_colored(out_file_rec, verts, faces, colors, double=double)
-            elif double:
-                meshio.write_ply_mesh(out_file_rec, verts, faces, double=True)
-            else:
-                meshio.write_ply_mesh(out_file_rec, verts, faces)
+            meshio.write_ply_mesh(out_file_rec, verts, faces, double=double, normals=normals, colors_u8=colors)
         else:
             print('No reconstruction for {}'.format(pc_file_in))
         return 0

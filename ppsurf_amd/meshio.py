@@ -464,105 +464,66 @@ def load_pts_colors(pts_file: str):
     return None
 
 
-def write_ply_mesh(path, verts: np.ndarray, faces: np.ndarray, double=False):
-    """Binary little-endian PLY mesh; double=True stores `property double x/y/z` (geo-referenced coordinates lose centimetres in float32)."""
+def _write_ply(path, pos, double, normals, colors_u8, faces):
+    """The one layout of every writer below, binary little-endian: `x y z` float or double, then `nx ny nz` float when given, then `red green
+    blue alpha` uchar when given (three columns get alpha 255), then the faces; faces=None is `element face 0`."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    verts = np.asarray(verts, dtype='<f8' if double else '<f4')
-    faces = np.asarray(faces, dtype='<i4')
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {2} x\nproperty {2} y\n'
-              'property {2} z\nelement face {1}\nproperty list uchar int vertex_indices\nend_header\n').format(
-                  verts.shape[0], faces.shape[0], 'double' if double else 'float')
-    rec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
-    rec['n'] = 3
-    rec['v'] = faces
+    ftype, name = ('<f8', 'double') if double else ('<f4', 'float')
+    pos = np.asarray(pos, dtype=ftype).reshape(-1, 3)
+    n = pos.shape[0]
+    fields, cols = [('p', ftype, (3,))], {'p': pos}
+    header = 'ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {1} x\nproperty {1} y\nproperty {1} z\n'.format(n, name)
+    if normals is not None:
+        fields.append(('n', '<f4', (3,)))
+        cols['n'] = np.asarray(normals, dtype='<f4').reshape(n, 3)
+        header += 'property float nx\nproperty float ny\nproperty float nz\n'
+    if colors_u8 is not None:
+        colors = np.asarray(colors_u8, dtype=np.uint8).reshape(n, -1)
+        if colors.shape[1] == 3:
+            colors = np.concatenate([colors, np.full((n, 1), 255, dtype=np.uint8)], axis=1)
+        fields.append(('c', 'u1', (4,)))
+        cols['c'] = colors[:, :4]
+        header += 'property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n'
+    faces = np.zeros((0, 3), dtype='<i4') if faces is None else np.asarray(faces, dtype='<i4').reshape(-1, 3)
+    header += 'element face {}\nproperty list uchar int vertex_indices\nend_header\n'.format(faces.shape[0])
+    vrec = np.empty(n, dtype=fields)
+    for k, col in cols.items():
+        vrec[k] = col
+    frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    frec['n'] = 3
+    frec['v'] = faces
     with open(path, 'wb') as f:
         f.write(header.encode('ascii'))
-        f.write(verts.tobytes())
-        f.write(rec.tobytes())
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
+def write_ply_mesh(path, verts: np.ndarray, faces: np.ndarray, double=False, normals: np.ndarray = None, colors_u8: np.ndarray = None):
+    """Binary little-endian PLY mesh `x y z [nx ny nz] [red green blue alpha]`; double=True stores `property double x/y/z` (geo-referenced
+    coordinates lose centimetres in float32).  The normals are always `float`; colors_u8 uint8 [nv,3] (alpha 255) or
+    [nv,4], the layout trimesh exports for vertex colours."""
+    _write_ply(path, verts, double, normals, colors_u8, faces)
 
 
 def write_ply_points(path, pts: np.ndarray):
     """Binary little-endian PLY with float x/y/z vertices and zero faces (layout of datasets/*/04_pts_vis/*.xyz.ply)."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    pts = np.asarray(pts, dtype='<f4')
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {}\nproperty float x\nproperty float y\n'
-              'property float z\nelement face 0\nproperty list uchar int vertex_indices\nend_header\n').format(pts.shape[0])
-    with open(path, 'wb') as f:
-        f.write(header.encode('ascii'))
-        f.write(pts.tobytes())
+    _write_ply(path, pts, False, None, None, None)
 
 
 def write_ply_mesh_colored(path, verts: np.ndarray, faces: np.ndarray, colors_u8: np.ndarray, double=False):
-    """Binary little-endian PLY mesh with per-vertex `uchar red/green/blue/alpha` (the layout trimesh exports for vertex colours).
-    colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]; double=True stores `property double x/y/z` as in write_ply_mesh."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    ftype = '<f8' if double else '<f4'
-    verts = np.asarray(verts, dtype=ftype).reshape(-1, 3)
-    faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
-    colors = np.asarray(colors_u8, dtype=np.uint8).reshape(verts.shape[0], -1)
-    if colors.shape[1] == 3:
-        colors = np.concatenate([colors, np.full((colors.shape[0], 1), 255, dtype=np.uint8)], axis=1)
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {2} x\nproperty {2} y\n'
-              'property {2} z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face {1}\n'
-              'property list uchar int vertex_indices\nend_header\n').format(verts.shape[0], faces.shape[0], 'double' if double else 'float')
-    vrec = np.empty(verts.shape[0], dtype=[('p', ftype, (3,)), ('c', 'u1', (4,))])
-    vrec['p'] = verts
-    vrec['c'] = colors[:, :4]
-    frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
-    frec['n'] = 3
-    frec['v'] = faces
-    with open(path, 'wb') as f:
-        f.write(header.encode('ascii'))
-        f.write(vrec.tobytes())
-        f.write(frec.tobytes())
+    """write_ply_mesh with per-vertex colours."""
+    _write_ply(path, verts, double, None, colors_u8, faces)
 
 
 def write_ply_mesh_normals(path, verts: np.ndarray, faces: np.ndarray, normals: np.ndarray, colors_u8: np.ndarray = None, double=False):
-    """Binary little-endian PLY mesh with per-vertex normals: `x y z nx ny nz [red green blue alpha]`.  The normals
-    are always `float`; double=True stores `property double x/y/z` as in write_ply_mesh; colors_u8 uint8 [nv,3] (alpha 255) or [nv,4]."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    ftype = '<f8' if double else '<f4'
-    verts = np.asarray(verts, dtype=ftype).reshape(-1, 3)
-    faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
-    fields = [('p', ftype, (3,)), ('n', '<f4', (3,))]
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {1} x\nproperty {1} y\nproperty {1} z\n'
-              'property float nx\nproperty float ny\nproperty float nz\n').format(verts.shape[0], 'double' if double else 'float')
-    if colors_u8 is not None:
-        colors = np.asarray(colors_u8, dtype=np.uint8).reshape(verts.shape[0], -1)
-        if colors.shape[1] == 3:
-            colors = np.concatenate([colors, np.full((colors.shape[0], 1), 255, dtype=np.uint8)], axis=1)
-        fields.append(('c', 'u1', (4,)))
-        header += 'property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n'
-    header += 'element face {}\nproperty list uchar int vertex_indices\nend_header\n'.format(faces.shape[0])
-    vrec = np.empty(verts.shape[0], dtype=fields)
-    vrec['p'] = verts
-    vrec['n'] = np.asarray(normals, dtype='<f4').reshape(verts.shape[0], 3)
-    if colors_u8 is not None:
-        vrec['c'] = colors[:, :4]
-    frec = np.empty(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
-    frec['n'] = 3
-    frec['v'] = faces
-    with open(path, 'wb') as f:
-        f.write(header.encode('ascii'))
-        f.write(vrec.tobytes())
-        f.write(frec.tobytes())
+    """write_ply_mesh with per-vertex normals, and colours when given."""
+    _write_ply(path, verts, double, normals, colors_u8, faces)
 
 
 def write_ply_points_normals(path, pts: np.ndarray, normals: np.ndarray, double=False):
     """Binary little-endian PLY point cloud `x y z nx ny nz` with zero faces: the layout read_ply_vertices returns as [n,6].  The normals are
     always `float`; double=True stores `property double x/y/z`."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    ftype = '<f8' if double else '<f4'
-    pts = np.asarray(pts, dtype=ftype).reshape(-1, 3)
-    header = ('ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex {0}\nproperty {1} x\nproperty {1} y\nproperty {1} z\n'
-              'property float nx\nproperty float ny\nproperty float nz\nelement face 0\nproperty list uchar int vertex_indices\n'
-              'end_header\n').format(pts.shape[0], 'double' if double else 'float')
-    rec = np.empty(pts.shape[0], dtype=[('p', ftype, (3,)), ('n', '<f4', (3,))])
-    rec['p'] = pts
-    rec['n'] = np.asarray(normals, dtype='<f4').reshape(pts.shape[0], 3)
-    with open(path, 'wb') as f:
-        f.write(header.encode('ascii'))
-        f.write(rec.tobytes())
+    _write_ply(path, pts, double, normals, None, None)
 
 
 def read_obj_mesh(path, colors=False):
@@ -610,6 +571,41 @@ def load_mesh_any(path: str):
         v, f = read_ply_mesh(path)
         return v, f, read_ply_vertex_colors(path)
     raise ValueError('unsupported mesh file: {}'.format(path))
+
+
+def ply_stores_doubles(path) -> bool:
+    """True when the PLY file's header declares `property double x`: a file that write_ply_mesh(..., double=True) or a geo-referenced export wrote."""
+    with open(path, 'rb') as f:
+        head = f.read(4096)
+    return b'property double x' in head.split(b'end_header')[0]
+
+
+def read_mesh_file(path: str):
+    """(verts float64 [nv,3], faces int32 [nf,3], colours uint8 [nv,3] or None, double) of the mesh file of a command line: a PLY is read as
+    float64 with its colours and whether it stores doubles (a writer's `double=`); OBJ and .npy go through load_mesh_any."""
+    if os.path.splitext(path)[1].lower() == '.ply':
+        verts, faces = read_ply_mesh(path, dtype=np.float64)
+        return verts, faces, read_ply_vertex_colors(path), ply_stores_doubles(path)
+    verts, faces, colors = load_mesh_any(path)
+    return np.asarray(verts, dtype=np.float64).reshape(-1, 3), faces, colors, False
+
+
+def box_centre(pts):
+    """The float64 centre of the box of pts [n,3] (zeros for no points)."""
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    return (pts.min(axis=0) + pts.max(axis=0)) * 0.5 if pts.shape[0] else np.zeros(3)
+
+
+def centred_f32(pts, centre):
+    """float32 [n,3]: pts - centre in float64 on the host and only then the cast to float32 (geo-referenced coordinates)."""
+    return (np.asarray(pts, dtype=np.float64).reshape(-1, 3) - np.asarray(centre, dtype=np.float64)[None]).astype(np.float32)
+
+
+def need_ply_output(ap, *names, plural=False):
+    """ap.error (exit code 2) unless every given output name of an argparse front end ends in .ply; None is skipped."""
+    for name in names:
+        if name is not None and os.path.splitext(name)[1].lower() != '.ply':
+            ap.error('the outputs are .ply files' if plural else 'the output is a .ply file')
 
 
 def call_necessary(file_in, file_out) -> bool:

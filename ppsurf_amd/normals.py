@@ -15,17 +15,11 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, ops
+from . import _lib, meshio, ops, topology
+from .topology import CpuTensorError, vertex_incidence  # noqa: F401  (their home is topology.py; the names stay importable from here)
 
 MAX_K = 256
-MAX_COUNT = 2 ** 31 - 1
 WEIGHTS = {'area': 0, 'max': 1}
-_SENTINEL = 2 ** 63 - 1
-
-
-class CpuTensorError(_lib.PpsError, ValueError):
-    """CPU tensors given to vertex_normals / point_normals: the PpsError of every module's device guard, and a ValueError like their other
-    argument errors."""
 
 
 def _checked_weight(weight):
@@ -40,57 +34,13 @@ def _checked_k(k):
     return int(k)
 
 
-def _need_device(what, *tensors):
-    try:
-        return _lib.need_device(what, *tensors)
-    except _lib.PpsError as e:
-        raise CpuTensorError(str(e)) from None
-
-
-def _checked_mesh(what, verts, faces):
-    assert verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
-    v, f = verts.contiguous().float(), faces.contiguous()
-    if v.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT:
-        raise ValueError('{}: at most 2^31 - 1 vertices and faces, got {} and {}'.format(what, v.shape[0], f.shape[0]))
-    if not bool(torch.isfinite(v).all()):
-        raise ValueError('{}: the mesh has non-finite vertices'.format(what))
-    return v, f
-
-
-def _corner_keys(faces, nv):
-    """Sorted keys int64 [3 nf] of ppsx_normals_corner_keys: (vertex << 32) | face, the three keys of an invalid face last."""
-    nf = int(faces.shape[0])
-    keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
-    _lib.call('ppsx_normals_corner_keys', faces, nf, nv, keys)
-    return torch.sort(keys)[0]
-
-
-def _incidence(keys, nv):
-    keys = keys[keys != _SENTINEL]
-    offsets = torch.zeros(nv + 1, dtype=torch.int64, device=keys.device)
-    offsets[1:] = torch.cumsum(torch.bincount(keys >> 32, minlength=nv), 0)
-    return offsets, (keys & 0xFFFFFFFF).to(torch.int32)
-
-
-def vertex_incidence(faces: torch.Tensor, nv: int):
-    """(offsets int64 [nv + 1], inc int32 [ni]) on the device: row i lists the valid faces that hold vertex i in ascending face index (a
-    duplicated face is two faces).  A face is valid when its indices lie in [0, nv) and are pairwise distinct.  One key per corner from the
-    kernel and one sort; the keys are distinct, so the rows do not depend on the sort implementation."""
-    _need_device('vertex_incidence', faces)
-    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
-    if not 0 <= int(nv) <= MAX_COUNT or faces.shape[0] > MAX_COUNT:
-        raise ValueError('nv and the number of faces must be in 0..2^31 - 1, got {} and {}'.format(nv, faces.shape[0]))
-    return _incidence(_corner_keys(faces.contiguous(), int(nv)), int(nv))
-
-
 def _vertex_normals(v, f, weight):
     """(normals f32 [nv,3], valid faces) of a checked device mesh."""
     nv, nf = int(v.shape[0]), int(f.shape[0])
-    keys = _corner_keys(f, nv)
-    offsets, inc = _incidence(keys, nv)
+    offsets, inc, valid = topology.incidence_rows(f, nv)
     out = torch.empty(nv, 3, dtype=torch.float32, device=v.device)          # the kernel writes every row
     _lib.call('ppsx_normals_vertex', v, nv, f, nf, offsets, inc, int(inc.shape[0]), WEIGHTS[weight], out)
-    return out, int(inc.shape[0]) // 3
+    return out, valid
 
 
 def _zero_rows(n):
@@ -104,8 +54,8 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, weight: str = 'area
     (0, 0, 0).  info: vertices, faces_valid, zero_normals, weight.  ValueError: an unknown weight, non-finite vertices, CPU tensors
     (CpuTensorError)."""
     weight = _checked_weight(weight)
-    _need_device('vertex_normals', verts, faces)
-    v, f = _checked_mesh('vertex_normals', verts, faces)
+    topology.need_device('vertex_normals', verts, faces)
+    v, f = topology.checked_mesh('vertex_normals', verts, faces, limit=True)
     out, valid = _vertex_normals(v, f, weight)
     return out, {'vertices': int(v.shape[0]), 'faces_valid': valid, 'zero_normals': _zero_rows(out), 'weight': weight}
 
@@ -113,7 +63,7 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, weight: str = 'area
 def blend_normals(idx: torch.Tensor, d2: torch.Tensor, normals: torch.Tensor, eps: float = 1e-30) -> torch.Tensor:
     """f32 [m,3]: per row the sum of normals f32 [nv,3] at idx int64 [m,k] with the weights 1 / (double(d2) + eps), d2 f32 [m,k], in column
     order in fp64, normalised; entries of idx outside [0, nv) are skipped and a row whose sum has no finite positive length is (0, 0, 0)."""
-    _need_device('blend_normals', idx, d2, normals)
+    topology.need_device('blend_normals', idx, d2, normals)
     assert idx.dtype == torch.int64 and d2.dtype == torch.float32 and normals.dtype == torch.float32
     assert idx.dim() == 2 and idx.shape == d2.shape and normals.dim() == 2 and normals.shape[1] == 3
     idx, d2, normals = idx.contiguous(), d2.contiguous(), normals.contiguous()
@@ -128,9 +78,9 @@ def point_normals(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor
     used), zero_normals, weight.  ValueError: an unknown weight, k outside 1..256, no vertices, non-finite vertices or points, CPU tensors
     (CpuTensorError)."""
     weight, k = _checked_weight(weight), _checked_k(k)
-    dev = _need_device('point_normals', points, verts, faces)
+    dev = topology.need_device('point_normals', points, verts, faces)
     assert points.dim() == 2 and points.shape[1] == 3
-    v, f = _checked_mesh('point_normals', verts, faces)
+    v, f = topology.checked_mesh('point_normals', verts, faces, limit=True)
     p = points.contiguous().float()
     if not bool(torch.isfinite(p).all()):
         raise ValueError('point_normals: non-finite points')
@@ -148,7 +98,6 @@ def point_normals(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor
 
 def main(argv=None):
     import argparse
-    from .transfer import _ply_stores_doubles
     ap = argparse.ArgumentParser(prog='python -m ppsurf_amd.normals', description='Write a mesh with oriented vertex normals, and optionally a '
                                  'scan with the normals of that surface (GPU).')
     ap.add_argument('mesh', help='PLY or OBJ mesh')
@@ -164,28 +113,17 @@ def main(argv=None):
         ap.error(str(e))
     if (args.points is None) != (args.points_out is None):
         ap.error('--points and --points_out go together')
-    for name in (args.out_file, args.points_out):
-        if name is not None and os.path.splitext(name)[1].lower() != '.ply':
-            ap.error('the outputs are .ply files')
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('python -m ppsurf_amd.normals runs on the GPU only; there is no CPU fallback')
-    double = False
-    if os.path.splitext(args.mesh)[1].lower() == '.ply':
-        verts, faces = meshio.read_ply_mesh(args.mesh, dtype=np.float64)
-        double = _ply_stores_doubles(args.mesh)
-        colors = meshio.read_ply_vertex_colors(args.mesh)
-    else:
-        verts, faces, colors = meshio.load_mesh_any(args.mesh)
-    verts = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    meshio.need_ply_output(ap, args.out_file, args.points_out, plural=True)
+    _lib.need_gpu('python -m ppsurf_amd.normals')
+    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
     if not np.isfinite(verts).all():
         raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    # centred on the mesh's box centre in float64 on the host and only then cast to float32 (geo-referenced coordinates)
-    centre = (verts.min(axis=0) + verts.max(axis=0)) * 0.5 if verts.shape[0] else np.zeros(3)
+    centre = meshio.box_centre(verts)                              # the mesh's own box
     dev = torch.device('cuda')
-    local = torch.from_numpy((verts - centre[None]).astype(np.float32)).to(dev)
+    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
     dev_faces = torch.from_numpy(np.asarray(faces, dtype=np.int64).reshape(-1, 3)).to(dev)
     nrm, info = vertex_normals(local, dev_faces, weight)
-    meshio.write_ply_mesh_normals(args.out_file, verts, faces, nrm.cpu().numpy(), colors_u8=colors, double=double)
+    meshio.write_ply_mesh(args.out_file, verts, faces, double=double, normals=nrm.cpu().numpy(), colors_u8=colors)
     if args.points is not None:
         pts = np.asarray(meshio.load_pts(args.points))[:, :3].astype(np.float64)
         if not np.isfinite(pts).all():
@@ -193,8 +131,8 @@ def main(argv=None):
         if verts.shape[0] == 0:
             raise SystemExit('{} has no vertices to take normals from'.format(args.mesh))
         pts_double = os.path.splitext(args.points)[1].lower() == '.las' or (
-            os.path.splitext(args.points)[1].lower() == '.ply' and _ply_stores_doubles(args.points))
-        scan = torch.from_numpy((pts - centre[None]).astype(np.float32)).to(dev)          # the scan on the mesh's centre: one frame
+            os.path.splitext(args.points)[1].lower() == '.ply' and meshio.ply_stores_doubles(args.points))
+        scan = torch.from_numpy(meshio.centred_f32(pts, centre)).to(dev)                   # the scan on the mesh's centre: one frame
         pn, pinfo = point_normals(scan, local, dev_faces, k=k, weight=weight)
         meshio.write_ply_points_normals(args.points_out, pts, pn.cpu().numpy(), double=pts_double)
         info = dict(info, points=pinfo['points'], k=pinfo['k'], zero_point_normals=pinfo['zero_normals'])

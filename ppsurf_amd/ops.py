@@ -280,6 +280,15 @@ def csr_build(idx_flat: torch.Tensor, n: int):
     return csr_build_table(idx_flat.reshape(-1), 0, 0, n, False, want_flat=False)[1:]
 
 
+def row_offsets(ids: torch.Tensor, n: int) -> torch.Tensor:
+    """int64 [n + 1] on the device of ids: 0, then the running count of the ids int64 in [0, n) per row -- the offsets of rows whose entries
+    a sort has already put in order (adjacency, incidence, cell lists).  A bincount and a cumsum, not pps_csr: its rank step is quadratic in
+    a crowded row, and the fan vertex of a simplified mesh or a cell of a dense scan is such a row."""
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=ids.device)
+    offsets[1:] = torch.cumsum(torch.bincount(ids, minlength=n), 0)
+    return offsets
+
+
 def csr_build_table(ids: torch.Tensor, per_item: int, rows_per_item: int, rows: int, clamp_negative: bool, want_flat: bool = True):
     """(flat, order, offsets) of an id table [B, M, K] of a fit batch in one call: flat row numbers ids + item * rows_per_item (per_item = M * K
     entries per batch item; -1 -> row 0 with clamp_negative), and their CSR.  per_item = 0: `ids` are flat rows already."""

@@ -157,8 +157,7 @@ def simplify_mesh(verts, faces, max_faces=None, voxel_size=None, placement='quad
     if host:
         if torch.is_tensor(faces):
             raise _lib.PpsError('simplify_mesh takes vertices and faces of one kind: device tensors or host arrays')
-        if torch.device(device).type != 'cuda' or not torch.cuda.is_available():
-            raise _lib.PpsError('simplify_mesh runs on the GPU only (device={!r}); there is no CPU fallback'.format(str(device)))
+        _lib.need_gpu('simplify_mesh', device)
         v_in, f_in = np.asarray(verts), np.asarray(faces)
         if v_in.dtype.kind != 'f':
             v_in = v_in.astype(np.float64)
@@ -204,14 +203,7 @@ def main(argv=None):
     ext = os.path.splitext(args.in_file)[1].lower()
     if ext not in ('.ply', '.obj') or os.path.splitext(args.out_file)[1].lower() != '.ply':
         ap.error('reads .ply or .obj and writes .ply')
-    double = False
-    if ext == '.ply':
-        with open(args.in_file, 'rb') as f:
-            double = b'property double x' in f.read(4096).split(b'end_header')[0]
-    if double:
-        verts, faces = meshio.read_ply_mesh(args.in_file, dtype=np.float64)
-    else:
-        verts, faces, _ = meshio.load_mesh_any(args.in_file)
+    verts, faces, _, double = meshio.read_mesh_file(args.in_file)
     out_v, out_f, report = simplify_mesh(verts, faces, max_faces=args.max_faces, voxel_size=args.voxel_size, placement=args.placement)
     meshio.write_ply_mesh(args.out_file, out_v, out_f, double=double)
     print(json.dumps(report))

@@ -1,0 +1,83 @@
+"""The topology layer of the mesh stages: faces -> sorted keys -> row tables, and the checks on a mesh argument.
+
+smooth.py takes its adjacency from here and normals.py its incidence; the valid-face rule on the device is csrc/pps_faces.h, the numpy
+restatement tests/topology_spec.py.  One key kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end,
+ops.row_offsets for the rows.
+"""
+import torch
+
+from . import _lib, ops
+
+SENTINEL = 2 ** 63 - 1                     # KEY_SENTINEL of csrc/pps_faces.h: the keys of an invalid face, they sort last
+MAX_COUNT = 2 ** 31 - 1                    # vertices and faces: a key is (row << 32) | entry
+
+
+class CpuTensorError(_lib.PpsError, ValueError):
+    """CPU tensors given to a mesh stage (smooth_mesh, vertex_normals, point_normals, ...): the PpsError of every module's device guard, and
+    a ValueError like their other argument errors."""
+
+
+def need_device(what, *tensors):
+    try:
+        return _lib.need_device(what, *tensors)
+    except _lib.PpsError as e:
+        raise CpuTensorError(str(e)) from None
+
+
+def checked_mesh(what, verts, faces, limit=False):
+    """(verts f32 contiguous, faces contiguous) of a device mesh, or a ValueError: non-finite vertices, with `limit` more than 2^31 - 1
+    vertices or faces."""
+    assert verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
+    v, f = verts.contiguous().float(), faces.contiguous()
+    if limit and (v.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT):
+        raise ValueError('{}: at most 2^31 - 1 vertices and faces, got {} and {}'.format(what, v.shape[0], f.shape[0]))
+    if not bool(torch.isfinite(v).all()):
+        raise ValueError('{}: the mesh has non-finite vertices'.format(what))
+    return v, f
+
+
+def sorted_keys(entry, per_face, faces, nv):
+    """(live keys int64 ascending, valid faces) of a key entry on contiguous device faces: ppsx_smooth_half_edges writes 6 keys per face,
+    (src << 32) | dst, and ppsx_normals_corner_keys 3, (vertex << 32) | face; an invalid face gets SENTINEL for all of them, and those leave."""
+    nf = int(faces.shape[0])
+    keys = torch.empty(per_face * nf, dtype=torch.int64, device=faces.device)
+    _lib.call(entry, faces, nf, nv, keys)
+    keys = torch.sort(keys)[0]
+    keys = keys[keys != SENTINEL]
+    return keys, int(keys.shape[0]) // per_face
+
+
+def adjacency_rows(faces, nv):
+    """(offsets, nbr, mult, valid faces) of contiguous device faces."""
+    keys, valid = sorted_keys('ppsx_smooth_half_edges', 6, faces, nv)
+    uniq, counts = torch.unique_consecutive(keys, return_counts=True)
+    return ops.row_offsets(uniq >> 32, nv), (uniq & 0xFFFFFFFF).to(torch.int32), counts.to(torch.int32), valid
+
+
+def incidence_rows(faces, nv):
+    """(offsets, inc, valid faces) of contiguous device faces."""
+    keys, valid = sorted_keys('ppsx_normals_corner_keys', 3, faces, nv)
+    return ops.row_offsets(keys >> 32, nv), (keys & 0xFFFFFFFF).to(torch.int32), valid
+
+
+def mesh_adjacency(faces: torch.Tensor, nv: int):
+    """(offsets int64 [nv + 1], nbr int32 [ne], mult int32 [ne]) on the device: row i lists the distinct vertices that share a valid face
+    with vertex i, ascending, and the number of valid faces on each of those edges.  A face is valid when its indices lie in [0, nv) and
+    are pairwise distinct.  One key per half-edge from the kernel, one sort, the distinct keys with their counts (ops.row_offsets says why
+    not pps_csr; a fan vertex of a simplified mesh is a crowded row).  Does not depend on the order of the faces."""
+    need_device('mesh_adjacency', faces)
+    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
+    if not 0 <= int(nv) <= MAX_COUNT:
+        raise ValueError('nv must be in 0..2^31 - 1, got {}'.format(nv))
+    return adjacency_rows(faces.contiguous(), int(nv))[:3]
+
+
+def vertex_incidence(faces: torch.Tensor, nv: int):
+    """(offsets int64 [nv + 1], inc int32 [ni]) on the device: row i lists the valid faces that hold vertex i in ascending face index (a
+    duplicated face is two faces).  A face is valid when its indices lie in [0, nv) and are pairwise distinct.  One key per corner from the
+    kernel and one sort; the keys are distinct, so the rows do not depend on the sort implementation."""
+    need_device('vertex_incidence', faces)
+    assert faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
+    if not 0 <= int(nv) <= MAX_COUNT or faces.shape[0] > MAX_COUNT:
+        raise ValueError('nv and the number of faces must be in 0..2^31 - 1, got {} and {}'.format(nv, faces.shape[0]))
+    return incidence_rows(faces.contiguous(), int(nv))[:2]

@@ -8,7 +8,6 @@ The reference writes uncoloured meshes (source/poco_model.py:269 `mesh.export`);
 colours are a pure function of the cloud, its colours and the vertices: no float atomics, no dependence on the launch shape.
 """
 import json
-import os
 import sys
 
 import numpy as np
@@ -55,12 +54,6 @@ def transfer_colors(cloud_pts: torch.Tensor, cloud_rgb, verts: torch.Tensor, k: 
     return blend_rgba(idx, d2, cloud_rgb), d2[:, 0].contiguous()
 
 
-def _ply_stores_doubles(path):
-    with open(path, 'rb') as f:
-        head = f.read(4096)
-    return b'property double x' in head.split(b'end_header')[0]
-
-
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog='python -m ppsurf_amd.transfer', description='Colour a mesh from the point colours of a scan (GPU).')
@@ -71,8 +64,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 1 <= args.k <= MAX_K:
         raise SystemExit('--k must be in 1..{}'.format(MAX_K))
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('python -m ppsurf_amd.transfer runs on the GPU only; there is no CPU fallback')
+    _lib.need_gpu('python -m ppsurf_amd.transfer')
     rgb = meshio.load_pts_colors(args.scan)
     if rgb is None:
         raise SystemExit('{} carries no colours'.format(args.scan))
@@ -81,19 +73,13 @@ def main(argv=None):
     pts, rgb = pts[finite], rgb[finite]                           # non-finite rows leave together with their colours
     if pts.shape[0] == 0:
         raise SystemExit('{} has no finite point'.format(args.scan))
-    double = False
-    if os.path.splitext(args.mesh)[1].lower() == '.ply':
-        verts, faces = meshio.read_ply_mesh(args.mesh, dtype=np.float64)
-        double = _ply_stores_doubles(args.mesh)
-    else:
-        verts, faces, _ = meshio.load_mesh_any(args.mesh)
-    # both are centred on the scan's box centre in float64 on the host and only then cast to float32 (geo-referenced coordinates)
-    centre = (pts.min(axis=0) + pts.max(axis=0)) * 0.5
+    verts, faces, _, double = meshio.read_mesh_file(args.mesh)      # the mesh's own colours are not looked at
+    centre = meshio.box_centre(pts)                                # both on the scan's box
     dev = torch.device('cuda')
-    cloud = torch.from_numpy((pts - centre[None]).astype(np.float32)).to(dev)
-    local = torch.from_numpy((np.asarray(verts, dtype=np.float64) - centre[None]).astype(np.float32)).to(dev)
+    cloud = torch.from_numpy(meshio.centred_f32(pts, centre)).to(dev)
+    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
     rgba, d2 = transfer_colors(cloud, rgb, local, k=args.k)
-    meshio.write_ply_mesh_colored(args.out_file, verts, faces, rgba.cpu().numpy(), double=double)
+    meshio.write_ply_mesh(args.out_file, verts, faces, double=double, colors_u8=rgba.cpu().numpy())
     dist = np.sqrt(d2.cpu().numpy().astype(np.float64))
     report = {'vertices': int(verts.shape[0]), 'points': int(pts.shape[0]), 'k': min(args.k, int(pts.shape[0])),
               'mean_nearest': float(dist.mean()) if dist.size else None, 'max_nearest': float(dist.max()) if dist.size else None}

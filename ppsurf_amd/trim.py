@@ -10,7 +10,6 @@ cloud, the mesh and r: no dependence on the cell grid, the table capacity, the l
 With `--factor` the radius is F times the cloud's spacing (`cloud_spacing`); `--dist` gives it in file units.
 """
 import json
-import os
 import sys
 
 import numpy as np
@@ -45,8 +44,7 @@ class SupportGrid(CellGrid):
         return _f32_not_below(max(float(radius), float(np.float64(self.ext) / np.float64(MAX_AXIS - 1))))
 
     def build(self, h):
-        """Cell lists for the cell edge h: one insertion kernel writes every point's slot, a stable sort and a count per slot make the lists
-        (not pps_csr: its rank step is quadratic in a crowded row, and a cell of a dense scan is such a row)."""
+        """Cell lists for the cell edge h: one insertion kernel writes every point's slot, a stable sort and ops.row_offsets make the lists."""
         self._scratch()
         self.h = np.float32(h)
         self.inv_h = np.float32(1.0) / self.h
@@ -54,8 +52,7 @@ class SupportGrid(CellGrid):
         _lib.call('ppsx_trim_cell_slots', self.pts, self.n, self._vec3(self.lo), self._vec3(self.hi), float(self.h), float(self.inv_h), self._table,
                   self.capacity, slot)
         self.order = torch.sort(slot, stable=True)[1].contiguous()
-        self.offsets = torch.zeros(self.capacity + 1, dtype=torch.int64, device=self.device)
-        self.offsets[1:] = torch.cumsum(torch.bincount(slot, minlength=self.capacity), 0)
+        self.offsets = ops.row_offsets(slot, self.capacity)
         return self
 
     def support(self, verts: torch.Tensor, faces: torch.Tensor, radius: float) -> torch.Tensor:
@@ -139,7 +136,6 @@ def trim_mesh(cloud: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, rad
 
 def main(argv=None):
     import argparse
-    from .transfer import _ply_stores_doubles
     ap = argparse.ArgumentParser(prog='python -m ppsurf_amd.trim', description='Drop the faces of a mesh that no point of a scan supports (GPU).')
     ap.add_argument('mesh', help='PLY or OBJ mesh in the scan\'s frame')
     ap.add_argument('scan', help='the scan: .ply, .las, .pcd, .off, .obj, .stl, .xyz, .npy')
@@ -154,26 +150,17 @@ def main(argv=None):
         ap.error('--factor / --dist must be a finite number > 0')
     if not 1 <= args.spacing_k <= MAX_SPACING_K:
         ap.error('--spacing_k must be in 1..{}'.format(MAX_SPACING_K))
-    if os.path.splitext(args.out_file)[1].lower() != '.ply':
-        ap.error('the output is a .ply file')
-    if not torch.cuda.is_available():
-        raise _lib.PpsError('python -m ppsurf_amd.trim runs on the GPU only; there is no CPU fallback')
+    meshio.need_ply_output(ap, args.out_file)
+    _lib.need_gpu('python -m ppsurf_amd.trim')
     pts = np.asarray(meshio.load_pts(args.scan))[:, :3].astype(np.float64)
     pts = pts[np.isfinite(pts).all(axis=1)]
     if pts.shape[0] == 0:
         raise SystemExit('{} has no finite point'.format(args.scan))
-    double = False
-    if os.path.splitext(args.mesh)[1].lower() == '.ply':
-        verts, faces = meshio.read_ply_mesh(args.mesh, dtype=np.float64)
-        double = _ply_stores_doubles(args.mesh)
-        colors = meshio.read_ply_vertex_colors(args.mesh)
-    else:
-        verts, faces, colors = meshio.load_mesh_any(args.mesh)
-    # both are centred on the scan's box centre in float64 on the host and only then cast to float32 (geo-referenced coordinates)
-    centre = (pts.min(axis=0) + pts.max(axis=0)) * 0.5
+    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
+    centre = meshio.box_centre(pts)                                # both on the scan's box
     dev = torch.device('cuda')
-    cloud = torch.from_numpy((pts - centre[None]).astype(np.float32)).to(dev)
-    local = torch.from_numpy((np.asarray(verts, dtype=np.float64) - centre[None]).astype(np.float32)).to(dev)
+    cloud = torch.from_numpy(meshio.centred_f32(pts, centre)).to(dev)
+    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
     spacing = None
     if args.factor is not None:
         if pts.shape[0] <= args.spacing_k:
@@ -183,13 +170,9 @@ def main(argv=None):
     else:
         radius = float(args.dist)
     # the vertices (and colours) are written as read: the trim works on row numbers, not on the float32 copies
-    verts = np.asarray(verts)
     rows, out_f, supported = _trim_rows(cloud, local, torch.from_numpy(np.asarray(faces, dtype=np.int64)).to(dev), radius, 6)
     rows, out_f = rows.cpu().numpy(), out_f.cpu().numpy()
-    if colors is not None:
-        meshio.write_ply_mesh_colored(args.out_file, verts[rows], out_f, np.asarray(colors)[rows], double=double)
-    else:
-        meshio.write_ply_mesh(args.out_file, verts[rows], out_f, double=double)
+    meshio.write_ply_mesh(args.out_file, verts[rows], out_f, double=double, colors_u8=None if colors is None else np.asarray(colors)[rows])
     report = {'faces_in': int(np.asarray(faces).shape[0]), 'faces_supported': supported, 'faces_out': int(out_f.shape[0]),
               'vertices_in': int(verts.shape[0]), 'vertices_out': int(rows.shape[0]), 'points': int(pts.shape[0]), 'radius': radius,
               'spacing': spacing}

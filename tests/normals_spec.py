@@ -11,33 +11,14 @@ normalised as in rule A.
 """
 import numpy as np
 
-from smooth_spec import fan, noisy_sphere, valid_faces  # noqa: F401  (the meshes of section 16 serve section 17 too)
+from smooth_spec import fan, noisy_sphere  # noqa: F401  (the meshes of section 16 serve section 17 too)
+from topology_spec import SENTINEL, corner_keys, incidence, valid_faces  # noqa: F401  (the rows of section 17 are restated in topology_spec)
 import transfer_spec
 
 D = np.float64
 F = np.float32
-SENTINEL = np.iinfo(np.int64).max
 EPS = 1e-30
 WEIGHTS = ('area', 'max')
-
-
-def corner_keys(faces, nv):
-    """int64 [3 nf]: (a << 32) | t, (b << 32) | t, (c << 32) | t per face t = (a, b, c), in that order; INT64_MAX three times for an invalid face."""
-    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    t = np.arange(f.shape[0], dtype=np.int64)
-    keys = (f << 32) | t[:, None]
-    keys[~valid_faces(f, nv)] = SENTINEL
-    return keys.reshape(-1)
-
-
-def incidence(faces, nv):
-    """(offsets int64 [nv + 1], inc int64 [ni]): per vertex the valid faces that hold it, in ascending face index (a duplicated face is two
-    faces and sits in the row twice)."""
-    keys = corner_keys(faces, nv)
-    keys = np.sort(keys[keys != SENTINEL])
-    offsets = np.zeros(nv + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(np.bincount(keys >> 32, minlength=nv))
-    return offsets, keys & 0xFFFFFFFF
 
 
 def _unit(acc):

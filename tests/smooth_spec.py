@@ -10,34 +10,9 @@ an iteration is pass(lam) then pass(mu); the state is float64 and is rounded to 
 """
 import numpy as np
 
+from topology_spec import SENTINEL, adjacency, half_edge_keys, valid_faces  # noqa: F401  (the rows of section 16 are restated in topology_spec)
+
 D = np.float64
-SENTINEL = np.iinfo(np.int64).max
-
-
-def valid_faces(faces, nv):
-    """bool [nf]: the three indices lie in [0, nv) and are pairwise distinct."""
-    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    a, b, c = f[:, 0], f[:, 1], f[:, 2]
-    return ((f >= 0) & (f < nv)).all(axis=1) & (a != b) & (b != c) & (c != a)
-
-
-def half_edge_keys(faces, nv):
-    """int64 [6 nf]: (src << 32) | dst of a->b, b->a, b->c, c->b, c->a, a->c per face, in that order; INT64_MAX six times for an invalid face."""
-    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    a, b, c = f[:, 0], f[:, 1], f[:, 2]
-    keys = np.stack([(a << 32) | b, (b << 32) | a, (b << 32) | c, (c << 32) | b, (c << 32) | a, (a << 32) | c], axis=1)
-    keys[~valid_faces(f, nv)] = SENTINEL
-    return keys.reshape(-1)
-
-
-def adjacency(faces, nv):
-    """(offsets int64 [nv + 1], nbr int64 [ne], mult int64 [ne]): per vertex the distinct targets of its half-edges in ascending order and how
-    often each occurs."""
-    keys = half_edge_keys(faces, nv)
-    uniq, counts = np.unique(keys[keys != SENTINEL], return_counts=True)
-    offsets = np.zeros(nv + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(np.bincount(uniq >> 32, minlength=nv))
-    return offsets, uniq & 0xFFFFFFFF, counts.astype(np.int64)
 
 
 def neighbours(faces, nv):

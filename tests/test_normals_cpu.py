@@ -1,17 +1,15 @@
 """CPU tier of the oriented normals: hand-checked cases and properties of the numpy specification
 tests/normals_spec.py, the argument rules of `vertex_normals` / `point_normals`, the models' `gen_normals`, the command's argument errors, the
 two PLY writers and the extension entries of the C ABI."""
-import ast
 import ctypes
 import inspect
-import os
 
 import numpy as np
 import pytest
 
 import eval_spec
 import normals_spec as N
-from golden_util import REPO
+import call_sites
 
 TRI = np.array([[0, 0, 0], [4, 0, 0], [0, 4, 0]], dtype=np.float32)
 FACE = np.array([[0, 1, 2]], dtype=np.int64)
@@ -240,15 +238,11 @@ def test_the_normals_entries_are_declared_and_every_call_site_has_their_argument
     assert _lib.EXT_PARAMS['ppsx_normals_vertex'] == ['verts', 'nv', 'faces', 'nf', 'offsets', 'inc', 'ni', 'weight', 'out', 'stream']
     assert _lib.EXT_PARAMS['ppsx_normals_blend'] == ['idx', 'd2', 'm', 'k', 'normals', 'nv', 'eps', 'out', 'stream']
     assert not any(n.startswith('pps_normals') or n.startswith('ppsx_') for n in _lib.SIGNATURES)          # the main header stays frozen
-    text = open(os.path.join(REPO, 'ppsurf_amd', 'normals.py')).read()
-    seen = {}
-    for node in ast.walk(ast.parse(text)):
-        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'call' and node.args
-                and isinstance(node.args[0], ast.Constant) and str(node.args[0].value).startswith('ppsx_normals')):
-            name = node.args[0].value
-            assert not any(isinstance(a, ast.Starred) for a in node.args)
-            assert len(node.args) - 1 == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}'.format(name, node.lineno)
-            seen[name] = seen.get(name, 0) + 1
+    sites = call_sites.ext_call_sites('ppsx_normals')                    # every ppsurf_amd/*.py: the key entries are called from topology.py
+    for name, where in sites.items():
+        for path, line, nargs in where:
+            assert nargs == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}:{}'.format(path, line, name)
+    seen = {name: len(where) for name, where in sites.items()}
     assert seen == {'ppsx_normals_corner_keys': 1, 'ppsx_normals_vertex': 1, 'ppsx_normals_blend': 1}
     assert 'pps_normals.hip' in build.SOURCES
     lib = _lib.lib()
@@ -289,11 +283,15 @@ def test_the_writers_round_trip(tmp_path, double):
 
 
 def test_the_existing_writers_still_produce_the_same_bytes(tmp_path):
-    """write_ply_mesh / write_ply_mesh_colored / write_ply_points against bytes laid out by hand from the published format."""
+    """Every public writer against bytes laid out by hand from the published format: write_ply_mesh / write_ply_mesh_colored /
+    write_ply_points, and the two normals writers, float and double, write_ply_mesh_normals with and without colours."""
     from ppsurf_amd import meshio
     verts = np.array([[0, 0, 0], [4, 0, 0], [0, 4, 0.5]], dtype=np.float64)
     faces = np.array([[0, 1, 2]], dtype=np.int64)
     rgb = np.array([[1, 2, 3], [4, 5, 6], [7, 8, 9]], dtype=np.uint8)
+    nrm = np.array([[0, 0, 1], [0.6, 0, -0.8], [0.1, -0.25, 0.5]], dtype=np.float64)
+    normal_props = 'property float nx\nproperty float ny\nproperty float nz\n'
+    no_faces = 'element face 0\nproperty list uchar int vertex_indices\nend_header\n'
     face_bytes = b'\x03' + np.array([0, 1, 2], dtype='<i4').tobytes()
     for double in (False, True):
         ftype, name = ('<f8', 'double') if double else ('<f4', 'float')
@@ -306,6 +304,18 @@ def test_the_existing_writers_still_produce_the_same_bytes(tmp_path):
         rows = b''.join(verts[i].astype(ftype).tobytes() + rgb[i].tobytes() + b'\xff' for i in range(3))
         colour_props = 'property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n'
         assert open(path, 'rb').read() == (head + colour_props + tail).encode('ascii') + rows + face_bytes
+        meshio.write_ply_mesh_normals(path, verts, faces, nrm, double=double)
+        rows = b''.join(verts[i].astype(ftype).tobytes() + nrm[i].astype('<f4').tobytes() for i in range(3))
+        assert open(path, 'rb').read() == (head + normal_props + tail).encode('ascii') + rows + face_bytes
+        meshio.write_ply_mesh_normals(path, verts, faces, nrm, colors_u8=rgb, double=double)
+        rows = b''.join(verts[i].astype(ftype).tobytes() + nrm[i].astype('<f4').tobytes() + rgb[i].tobytes() + b'\xff' for i in range(3))
+        assert open(path, 'rb').read() == (head + normal_props + colour_props + tail).encode('ascii') + rows + face_bytes
+        general = str(tmp_path / 'g.ply')                                # the general form writes the same file
+        meshio.write_ply_mesh(general, verts, faces, double=double, normals=nrm, colors_u8=rgb)
+        assert open(general, 'rb').read() == open(path, 'rb').read()
+        meshio.write_ply_points_normals(path, verts, nrm, double=double)
+        rows = b''.join(verts[i].astype(ftype).tobytes() + nrm[i].astype('<f4').tobytes() for i in range(3))
+        assert open(path, 'rb').read() == (head + normal_props + no_faces).encode('ascii') + rows
     meshio.write_ply_points(path, verts)
     head = 'ply\nformat binary_little_endian 1.0\ncomment ppsurf_amd\nelement vertex 3\nproperty float x\nproperty float y\nproperty float z\n'
     assert open(path, 'rb').read() == (head + 'element face 0\nproperty list uchar int vertex_indices\nend_header\n').encode('ascii') + verts.astype('<f4').tobytes()

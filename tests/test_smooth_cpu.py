@@ -1,16 +1,14 @@
 """CPU tier of the Taubin smoothing: hand-checked cases and properties of the numpy specification
 tests/smooth_spec.py, the argument rules of `smooth_mesh`, the models' `gen_smooth_iters`, the command's argument errors and the extension
 entries of the C ABI."""
-import ast
 import ctypes
 import inspect
-import os
 
 import numpy as np
 import pytest
 
 import smooth_spec as S
-from golden_util import REPO
+import call_sites
 
 TRI = np.array([[0, 0, 0], [4, 0, 0], [0, 4, 0]], dtype=np.float32)
 FACE = np.array([[0, 1, 2]], dtype=np.int64)
@@ -180,15 +178,11 @@ def test_the_smooth_entries_are_declared_and_every_call_site_has_their_argument_
     assert _lib.EXT_PARAMS['ppsx_smooth_half_edges'] == ['faces', 'nf', 'nv', 'keys', 'stream']
     assert _lib.EXT_PARAMS['ppsx_smooth_pass'] == ['x', 'nv', 'offsets', 'nbr', 'mult', 'ne', 's', 'out', 'stream']
     assert not any(n.startswith('pps_smooth') or n.startswith('ppsx_') for n in _lib.SIGNATURES)          # the main header stays frozen
-    text = open(os.path.join(REPO, 'ppsurf_amd', 'smooth.py')).read()
-    seen = {}
-    for node in ast.walk(ast.parse(text)):
-        if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'call' and node.args
-                and isinstance(node.args[0], ast.Constant) and str(node.args[0].value).startswith('ppsx_smooth')):
-            name = node.args[0].value
-            assert not any(isinstance(a, ast.Starred) for a in node.args)
-            assert len(node.args) - 1 == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}'.format(name, node.lineno)
-            seen[name] = seen.get(name, 0) + 1
+    sites = call_sites.ext_call_sites('ppsx_smooth')                    # every ppsurf_amd/*.py: the key entries are called from topology.py
+    for name, where in sites.items():
+        for path, line, nargs in where:
+            assert nargs == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}:{}'.format(path, line, name)
+    seen = {name: len(where) for name, where in sites.items()}
     assert seen == {'ppsx_smooth_half_edges': 1, 'ppsx_smooth_pass': 1}
     assert 'pps_smooth.hip' in build.SOURCES
     lib = _lib.lib()

@@ -1,0 +1,89 @@
+"""CPU tier of the shared layer of the mesh stages: one CpuTensorError and one home for the row tables
+(ppsurf_amd/topology.py), the mesh-file front end of the five command lines (meshio.read_mesh_file, ply_stores_doubles)."""
+import numpy as np
+import pytest
+
+
+def test_one_error_class_and_one_home_for_the_row_tables():
+    from ppsurf_amd import _lib, normals, smooth, topology
+    assert smooth.CpuTensorError is topology.CpuTensorError and normals.CpuTensorError is topology.CpuTensorError
+    assert issubclass(topology.CpuTensorError, _lib.PpsError) and issubclass(topology.CpuTensorError, ValueError)
+    assert smooth.mesh_adjacency is topology.mesh_adjacency and normals.vertex_incidence is topology.vertex_incidence
+    assert topology.SENTINEL == np.iinfo(np.int64).max and topology.MAX_COUNT == 2 ** 31 - 1
+
+
+def test_cpu_tensors_raise_the_one_error_with_the_guards_message():
+    import torch
+    from ppsurf_amd import normals, smooth, topology
+    v, f = torch.zeros(3, 3), torch.zeros(1, 3, dtype=torch.int64)
+    for what, fn in (('smooth_mesh', lambda: smooth.smooth_mesh(v, f, 1)), ('vertex_normals', lambda: normals.vertex_normals(v, f)),
+                     ('point_normals', lambda: normals.point_normals(v, v, f)), ('mesh_adjacency', lambda: topology.mesh_adjacency(f, 3)),
+                     ('vertex_incidence', lambda: topology.vertex_incidence(f, 3))):
+        with pytest.raises(topology.CpuTensorError) as e:
+            fn()
+        assert str(e.value) == '{}: tensor on cpu; inputs must be device tensors, there is no CPU path'.format(what)
+    with pytest.raises(topology.CpuTensorError, match='got ndarray; inputs must be device tensors, there is no CPU path'):
+        smooth.smooth_mesh(np.zeros((3, 3), dtype=np.float32), f, 1)
+
+
+def test_read_mesh_file(tmp_path):
+    from ppsurf_amd import meshio
+    verts = np.array([[0, 0, 0], [4, 0, 0], [0, 4, 0.5], [500000.125, -250000.0625, 120.1]], dtype=np.float64)
+    faces = np.array([[0, 1, 2], [1, 3, 2]], dtype=np.int32)
+    rgb = np.array([[1, 2, 3], [4, 5, 6], [7, 8, 9], [255, 0, 128]], dtype=np.uint8)
+    plain, geo, obj = str(tmp_path / 'f.ply'), str(tmp_path / 'd.ply'), str(tmp_path / 'c.obj')
+    meshio.write_ply_mesh(plain, verts, faces)
+    meshio.write_ply_mesh(geo, verts, faces, double=True, colors_u8=rgb)
+    with open(obj, 'w') as fh:
+        for p, c in zip(verts[:3], rgb[:3]):
+            fh.write('v {} {} {} {} {} {}\n'.format(*p, *(c / 255.0)))
+        fh.write('f 1 2 3\n')
+    v, f, c, double = meshio.read_mesh_file(plain)
+    assert v.dtype == np.float64 and np.array_equal(v, verts.astype(np.float32).astype(np.float64)) and c is None and double is False
+    assert f.dtype == np.int32 and np.array_equal(f, faces)
+    v, f, c, double = meshio.read_mesh_file(geo)
+    assert v.dtype == np.float64 and np.array_equal(v, verts) and double is True                # the doubles come back as written
+    assert np.array_equal(f, faces) and c.dtype == np.uint8 and np.array_equal(c, rgb)
+    v, f, c, double = meshio.read_mesh_file(obj)
+    assert v.dtype == np.float64 and v.shape == (3, 3) and np.array_equal(v, verts[:3].astype(np.float32).astype(np.float64)) and double is False
+    assert np.array_equal(f, faces[:1]) and c.dtype == np.uint8 and np.array_equal(c, rgb[:3])
+    with pytest.raises(ValueError, match='unsupported mesh file'):
+        meshio.read_mesh_file(str(tmp_path / 'm.stl'))
+
+
+def test_box_centre_and_the_centred_copy():
+    from ppsurf_amd import meshio
+    pts = np.array([[500000.0, -250000.0, 100.0], [500004.0, -249990.0, 120.5]], dtype=np.float64)
+    centre = meshio.box_centre(pts)
+    assert centre.dtype == np.float64 and centre.tolist() == [500002.0, -249995.0, 110.25]
+    local = meshio.centred_f32(pts, centre)
+    assert local.dtype == np.float32 and local.tolist() == [[-2.0, -5.0, -10.25], [2.0, 5.0, 10.25]]
+    assert meshio.box_centre(np.zeros((0, 3))).tolist() == [0.0, 0.0, 0.0] and meshio.centred_f32(np.zeros((0, 3)), np.zeros(3)).shape == (0, 3)
+
+
+def test_ply_stores_doubles_reads_the_whole_header(tmp_path):
+    from ppsurf_amd import meshio
+    comments = ''.join('comment line {} of a long header\n'.format(i) for i in range(40))
+    for name, kind, want in (('d.ply', 'double', True), ('f.ply', 'float', False)):
+        path = str(tmp_path / name)
+        with open(path, 'w') as fh:                                  # the vertex properties come after 40 comment lines
+            fh.write('ply\nformat ascii 1.0\n' + comments + 'element vertex 1\nproperty {0} x\nproperty {0} y\nproperty {0} z\n'.format(kind)
+                     + 'element face 0\nproperty list uchar int vertex_indices\nend_header\n0 0 0\n')
+        assert meshio.ply_stores_doubles(path) is want
+    path = str(tmp_path / 'body.ply')                                # the words in the body of a float file do not count
+    with open(path, 'wb') as fh:
+        fh.write(b'ply\nformat binary_little_endian 1.0\nelement vertex 0\nproperty float x\nproperty float y\nproperty float z\nend_header\n'
+                 b'property double x')
+    assert meshio.ply_stores_doubles(path) is False
+
+
+def test_need_gpu_names_the_program_and_the_device():
+    import torch
+    from ppsurf_amd import _lib
+    with pytest.raises(_lib.PpsError) as e:
+        _lib.need_gpu('simplify_mesh', 'cpu')
+    assert str(e.value) == "simplify_mesh runs on the GPU only (device='cpu'); there is no CPU fallback"
+    if not torch.cuda.is_available():
+        with pytest.raises(_lib.PpsError) as e:
+            _lib.need_gpu('python -m ppsurf_amd.smooth')
+        assert str(e.value) == 'python -m ppsurf_amd.smooth runs on the GPU only; there is no CPU fallback'

@@ -16,7 +16,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from ppsurf_amd import _lib, mcubes, normals, ops  # noqa: E402
+from ppsurf_amd import _lib, mcubes, normals, ops, topology  # noqa: E402
 import normals_spec as N  # noqa: E402
 
 
@@ -65,7 +65,7 @@ def main():
     verts = (verts * (1.0 / (R - 1)) - 0.5).float().contiguous()
     faces = faces.contiguous()
     nv, nf = int(verts.shape[0]), int(faces.shape[0])
-    offsets, inc = normals.vertex_incidence(faces, nv)
+    offsets, inc = topology.vertex_incidence(faces, nv)
     ni = int(inc.shape[0])
     deg = offsets[1:] - offsets[:-1]
     print('sphere R={}: {} faces, {} vertices, {} incidence entries, faces per vertex max {} mean {:.2f}'.format(
@@ -85,7 +85,7 @@ def main():
     blocks = ops.KnnBlocks(verts)
     idx, d2 = blocks.query(cloud, args.k, return_d2=True)
     nrm = normals.vertex_normals(verts, faces, 'area')[0]
-    rows = [('incidence (ppsx_normals_corner_keys + sort + bincount + cumsum), wall', wall_ms(lambda: normals.vertex_incidence(faces, nv), args.reps))]
+    rows = [('incidence (ppsx_normals_corner_keys + sort + bincount + cumsum), wall', wall_ms(lambda: topology.vertex_incidence(faces, nv), args.reps))]
     for name, code in normals.WEIGHTS.items():
         rows.append(('{} launches of ppsx_normals_vertex, weight {}, device events'.format(BATCH, name), device_ms(kernel(code), args.reps)))
     for name in normals.WEIGHTS:

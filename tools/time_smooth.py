@@ -15,7 +15,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
-from ppsurf_amd import _lib, mcubes, smooth  # noqa: E402
+from ppsurf_amd import _lib, mcubes, smooth, topology  # noqa: E402
 import smooth_spec as S  # noqa: E402
 
 
@@ -63,7 +63,7 @@ def main():
     verts = (verts * (1.0 / (R - 1)) - 0.5).float().contiguous()
     faces = faces.contiguous()
     nv, nf = int(verts.shape[0]), int(faces.shape[0])
-    offsets, nbr, mult = smooth.mesh_adjacency(faces, nv)
+    offsets, nbr, mult = topology.mesh_adjacency(faces, nv)
     ne = int(nbr.shape[0])
     deg = offsets[1:] - offsets[:-1]
     print('sphere R={}: {} faces, {} vertices, {} half-edges after merging, valence max {} mean {:.2f}'.format(
@@ -75,7 +75,7 @@ def main():
             _lib.call('ppsx_smooth_pass', x, nv, offsets, nbr, mult, ne, 0.5, y)
             _lib.call('ppsx_smooth_pass', y, nv, offsets, nbr, mult, ne, -0.53, x)
 
-    rows = [('adjacency (ppsx_smooth_half_edges + sort + unique_consecutive + bincount + cumsum), wall', wall_ms(lambda: smooth.mesh_adjacency(faces, nv), args.reps)),
+    rows = [('adjacency (ppsx_smooth_half_edges + sort + unique_consecutive + bincount + cumsum), wall', wall_ms(lambda: topology.mesh_adjacency(faces, nv), args.reps)),
             ('{} passes back to back (ppsx_smooth_pass), device events'.format(BATCH), device_ms(passes, args.reps)),
             ('smooth_mesh(iters={}) end to end, wall'.format(args.iters), wall_ms(lambda: smooth.smooth_mesh(verts, faces, args.iters), args.reps))]
     print('GPU ({} reps after warm-up):'.format(args.reps))

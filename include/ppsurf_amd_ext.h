@@ -113,6 +113,49 @@ int ppsx_normals_vertex(const float* verts, int64_t nv, const int64_t* faces, in
 int ppsx_normals_blend(const int64_t* idx, const float* d2, int64_t m, int k, const float* normals, int64_t nv, double eps, float* out,
                        void* stream);
 
+/* ---- hole filling: short border loops of a mesh are closed (csrc/pps_fill.hip) --------------------------------------------------------------
+ * new capability: replaces nothing -- the reference has no mesh repair.  Driven by ppsurf_amd/fill.py and topology.rim_rows; the rule is
+ * written out at the top of csrc/pps_fill.hip and in DESIGN.md section 19.  In short: a face is valid when its three indices lie in [0, nv)
+ * and are pairwise distinct; the multiplicity of an edge is the number of valid faces that hold it; a loose triangle is a valid face whose
+ * three edges all have multiplicity 1; a rim half-edge is a directed half-edge u->v (a->b, b->c, c->a) of a valid, non-loose face whose
+ * edge has multiplicity 1; a vertex is simple when exactly one rim half-edge leaves it and exactly one enters it, and succ(u) is where the
+ * one that leaves goes; a loop is a cycle s_0 .. s_{L-1} of succ over simple vertices with s_0 its smallest index (the leader), filled when
+ * L <= max_edges: L == 3 by the face (s_0, s_2, s_1), L > 3 by the faces (s_{j+1}, s_j, c), j = 0..L-1, s_L = s_0, around a new vertex c =
+ * f32(acc / double(L)), acc = 0.0; acc = acc + double(V[s_j]) in loop order, per component in fp64, every operation rounded on its own.
+ * Loops come in ascending leader; the new vertices and faces are appended.  No entry uses atomics.
+ *   ppsx_fill_rim_keys  keys int64 [3 nf]: per face (a, b, c) of faces int64 [nf,3] the keys of a->b, b->c, c->a in that order, (u << 32) | v
+ *                       for a rim half-edge and INT64_MAX otherwise (an invalid face, an edge of another multiplicity, all three keys of a
+ *                       loose triangle).  The multiplicity is looked up by binary search for v in row u of the adjacency: the entries
+ *                       offsets[u] .. offsets[u + 1] - 1 (offsets int64 [nv + 1]) of nbr int32 [ne] (ascending) and mult int32 [ne], as
+ *                       topology.adjacency_rows builds them.  A row whose offsets are not 0 <= offsets[u] <= offsets[u + 1] <= ne and a
+ *                       row without v give multiplicity 0; neither is read through.
+ *                       nf < 0, nv < 0, ne < 0, nf or nv > 2^31 - 1, or -- with nf > 0 -- a NULL faces or keys, a NULL offsets with
+ *                       nv > 0, a NULL nbr or mult with ne > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is
+ *                       launched.
+ *   ppsx_fill_loops     len int32 [nc]: for every candidate v = cand[i] (int64 [nc]) the length L of the loop that v leads, else 0.  The
+ *                       walk follows succ int32 [nv] from v and ends with 0 at an entry that is negative or >= nv, at the first vertex
+ *                       < v (v is no leader), after max_edges steps without a return to v, and for a return after fewer than 3 steps; a
+ *                       candidate outside [0, nv) gives 0.  At most nc x max_edges steps in all (a long rim whose indices ascend along
+ *                       it); near the size of the rims for a typical labelling.
+ *                       nc < 0, nv < 0, nc or nv > 2^31 - 1, max_edges outside 3..4096, or -- with nc > 0 -- a NULL cand or len or a NULL
+ *                       succ with nv > 0: PPS_ERR_ARG, nothing is launched or written.  nc == 0: 0, nothing is launched.
+ *   ppsx_fill_emit      the new vertex and the new faces of every loop i of nl: leader int64 [nl], len int32 [nl] (3..4096), vslot int64
+ *                       [nl] (the row of new_verts f32 [nnew,3] of a loop with len > 3; not read for len == 3) and foff int64 [nl] (the
+ *                       first of its len -- for len == 3 one -- rows of new_faces int64 [nfnew,3]).  The new vertex gets the index
+ *                       nv + vslot[i].  One lane per loop walks succ int32 [nv] from the leader over verts f32 [nv,3], re-checking every
+ *                       entry.  A loop that does not return to its leader after exactly len steps (an entry outside [0, nv), an earlier
+ *                       return, none), a leader outside [0, nv), a len outside 3..4096, a vslot outside [0, nnew) or rows outside
+ *                       [0, nfnew) writes NOTHING: its rows keep what the caller put there (fill.py: the invalid face (-1, -1, -1) and a
+ *                       zero vertex).  Rows of two loops that overlap are the caller's error; they stay inside the buffers.
+ *                       nv, nl, nnew or nfnew < 0 or > 2^31 - 1, or -- with nl > 0 -- a NULL leader, len, vslot or foff, a NULL verts or
+ *                       succ with nv > 0, a NULL new_verts with nnew > 0 or a NULL new_faces with nfnew > 0: PPS_ERR_ARG, nothing is
+ *                       launched or written.  nl == 0: 0, nothing is launched. */
+int ppsx_fill_rim_keys(const int64_t* faces, int64_t nf, int64_t nv, const int64_t* offsets, const int32_t* nbr, const int32_t* mult, int64_t ne,
+                       int64_t* keys, void* stream);
+int ppsx_fill_loops(const int64_t* cand, int64_t nc, const int32_t* succ, int64_t nv, int max_edges, int32_t* len, void* stream);
+int ppsx_fill_emit(const float* verts, int64_t nv, const int32_t* succ, const int64_t* leader, const int32_t* len, const int64_t* vslot,
+                   const int64_t* foff, int64_t nl, float* new_verts, int64_t nnew, int64_t* new_faces, int64_t nfnew, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

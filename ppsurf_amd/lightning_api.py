@@ -88,8 +88,14 @@ class PocoModel(_Base):
 
     def __init__(self, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir, padding_factor, name,
                  network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global, rec_batch_size,
-                 gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_normals=None, gen_trim_factor=None, gen_smooth_iters=None):
+                 gen_refine_iter, workers, gen_fill_holes=None, gen_max_faces=None, gen_color_k=None, gen_normals=None, gen_trim_factor=None,
+                 gen_smooth_iters=None):
         super().__init__()
+        if gen_fill_holes is not None:
+            n = float(gen_fill_holes)
+            if not (math.isfinite(n) and n == int(n) and 3 <= n <= 4096):
+                raise ValueError('gen_fill_holes must be an integer in 3..4096 (edges of the longest border loop that is closed), got {}'.format(gen_fill_holes))
+        self.gen_fill_holes = None if gen_fill_holes is None else int(float(gen_fill_holes))         # hole filling (ppsurf_amd/fill.py)
         if gen_normals is not None and gen_normals not in ('area', 'max'):
             raise ValueError('gen_normals must be \'area\' or \'max\' (the weights of the vertex normals), got {!r}'.format(gen_normals))
         self.gen_normals = gen_normals              # vertex normals of the written mesh (ppsurf_amd/normals.py)
@@ -472,6 +478,7 @@ class PocoModel(_Base):
             network=self.network, latent=shape, pts_raw_ms=batch['pts_raw_ms'] if 'pts_raw_ms' in batch else None,
             resolution=self.gen_resolution_global, padding=1, mc_value=0, num_pts=self.rec_batch_size, num_pts_local=self.num_pts_local,
             input_points=pts_cf.t().cpu().numpy(), refine_iter=self.gen_refine_iter, out_value=1, prog_bar=bar, pc_file_in=pc_file_in,
+            **({} if self.gen_fill_holes is None else {'fill_holes': self.gen_fill_holes}),
             **({} if self.gen_max_faces is None else {'max_faces': self.gen_max_faces}),
             **({} if self.gen_trim_factor is None else {'trim_factor': self.gen_trim_factor}),
             **({} if self.gen_smooth_iters is None else {'smooth_iters': self.gen_smooth_iters}))
@@ -533,16 +540,16 @@ class PPSurfModel(PocoModel):
 
     def __init__(self, pointnet_latent_size, output_names, in_channels, out_channels, k, lambda_l1, debug, in_file, results_dir,
                  padding_factor, name, network_latent_size, gen_subsample_manifold_iter, gen_subsample_manifold, gen_resolution_global,
-                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_max_faces=None, gen_color_k=None, gen_normals=None, gen_trim_factor=None,
-                 gen_smooth_iters=None):
+                 num_pts_local, rec_batch_size, gen_refine_iter, workers, gen_fill_holes=None, gen_max_faces=None, gen_color_k=None, gen_normals=None,
+                 gen_trim_factor=None, gen_smooth_iters=None):
         self._pps = (num_pts_local, pointnet_latent_size)
         super().__init__(output_names=output_names, in_channels=in_channels, out_channels=out_channels, k=k, lambda_l1=lambda_l1,
                          debug=debug, in_file=in_file, results_dir=results_dir, padding_factor=padding_factor, name=name,
                          workers=workers, rec_batch_size=rec_batch_size, gen_refine_iter=gen_refine_iter,
                          gen_subsample_manifold=gen_subsample_manifold, gen_resolution_global=gen_resolution_global,
                          gen_subsample_manifold_iter=gen_subsample_manifold_iter, network_latent_size=network_latent_size,
-                         gen_max_faces=gen_max_faces, gen_color_k=gen_color_k, gen_normals=gen_normals, gen_trim_factor=gen_trim_factor,
-                         gen_smooth_iters=gen_smooth_iters)
+                         gen_fill_holes=gen_fill_holes, gen_max_faces=gen_max_faces, gen_color_k=gen_color_k, gen_normals=gen_normals,
+                         gen_trim_factor=gen_trim_factor, gen_smooth_iters=gen_smooth_iters)
         self.num_pts_local, self.pointnet_latent_size = num_pts_local, pointnet_latent_size
 
     def _make_network(self):

@@ -189,7 +189,7 @@ def small_components_removed(verts: torch.Tensor, faces: torch.Tensor, min_compo
 def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts_raw_ms, resolution: int, padding=0, mc_value=0,
                                                       num_pts=50000, num_pts_local=None, refine_iter=10, input_points=None,
                                                       out_value=np.nan, dilation_size=2, prog_bar=None, pc_file_in: str = 'unknown',
-                                                      trim_factor=None, smooth_iters=None, max_faces=None):
+                                                      fill_holes=None, trim_factor=None, smooth_iters=None, max_faces=None):
     """poco_utils.py:26-175.  Returns (vertices float32 [V,3], faces int64 [F,3]) in model space, or None when the occupancy
     never crosses `mc_value`.  (The reference wraps the same arrays into a trimesh.Trimesh; ppsurf_amd.meshio writes PLY.)
     `max_faces` (not in the reference): a face budget; the cleaned mesh is simplified to it on the device (ppsurf_amd/simplify.py) and passes
@@ -197,7 +197,9 @@ def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts
     `trim_factor` (not in the reference): faces without a point of latent['pts'] within trim_factor x the cloud's spacing are dropped before
     that (ppsurf_amd/trim.py); None when no face survives.
     `smooth_iters` (not in the reference): that many Taubin lambda|mu iterations with the default factors on the float32 vertices, after
-    the trim and before the face budget (ppsurf_amd/smooth.py)."""
+    the trim and before the face budget (ppsurf_amd/smooth.py).
+    `fill_holes` (not in the reference): border loops of at most that many edges are closed, after the trim (whose pinholes they are; a
+    watertight mesh has no rims) and before the smoothing, which then relaxes the new fans (ppsurf_amd/fill.py)."""
     if latent['pts'].shape[0] != 1:
         raise ValueError('Reconstruction must be done with batch size = 0!')     # message kept from poco_utils.py:50
     progress = None
@@ -225,6 +227,9 @@ def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts
         verts, faces = trim_supported(field.pts, verts.to(torch.float32), faces, float(trim_factor))
         if faces.shape[0] == 0:
             return None
+    if fill_holes is not None:
+        from . import fill
+        verts, faces = fill.fill_holes(verts.to(torch.float32), faces, int(fill_holes))[:2]
     if smooth_iters is not None:
         # after the trim (which measures the surface the network produced) and before the budget (whose quadrics get the denoised one)
         from . import smooth

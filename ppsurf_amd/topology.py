@@ -1,6 +1,6 @@
 """The topology layer of the mesh stages: faces -> sorted keys -> row tables, and the checks on a mesh argument.
 
-smooth.py takes its adjacency from here and normals.py its incidence; the valid-face rule on the device is csrc/pps_faces.h, the numpy
+smooth.py takes its adjacency from here, normals.py its incidence and fill.py its adjacency and its rims (section 19); the valid-face rule on the device is csrc/pps_faces.h, the numpy
 restatement tests/topology_spec.py.  One key kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end,
 ops.row_offsets for the rows.
 """
@@ -36,14 +36,19 @@ def checked_mesh(what, verts, faces, limit=False):
     return v, f
 
 
+def live_keys(keys):
+    """The keys int64 of a key entry in ascending order without the SENTINEL ones."""
+    keys = torch.sort(keys)[0]
+    return keys[keys != SENTINEL]
+
+
 def sorted_keys(entry, per_face, faces, nv):
     """(live keys int64 ascending, valid faces) of a key entry on contiguous device faces: ppsx_smooth_half_edges writes 6 keys per face,
     (src << 32) | dst, and ppsx_normals_corner_keys 3, (vertex << 32) | face; an invalid face gets SENTINEL for all of them, and those leave."""
     nf = int(faces.shape[0])
     keys = torch.empty(per_face * nf, dtype=torch.int64, device=faces.device)
     _lib.call(entry, faces, nf, nv, keys)
-    keys = torch.sort(keys)[0]
-    keys = keys[keys != SENTINEL]
+    keys = live_keys(keys)
     return keys, int(keys.shape[0]) // per_face
 
 
@@ -58,6 +63,25 @@ def incidence_rows(faces, nv):
     """(offsets, inc, valid faces) of contiguous device faces."""
     keys, valid = sorted_keys('ppsx_normals_corner_keys', 3, faces, nv)
     return ops.row_offsets(keys >> 32, nv), (keys & 0xFFFFFFFF).to(torch.int32), valid
+
+
+def rim_rows(faces, nv, offsets, nbr, mult):
+    """(succ int32 [nv], candidates int64 ascending, rim half-edges, rim vertices, simple rim vertices) of contiguous device faces and their
+    adjacency_rows: the rim half-edges of DESIGN.md section 19 (an edge of one valid face, loose triangles left out) as sorted keys
+    (src << 32) | dst, how many leave and enter every vertex, succ = the destination where exactly one leaves and one enters and -1
+    elsewhere, and the vertices with a succ.  The key count is no multiple of a face count, so this does not go through sorted_keys."""
+    nf = int(faces.shape[0])
+    keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
+    _lib.call('ppsx_fill_rim_keys', faces, nf, nv, offsets, nbr, mult, int(nbr.shape[0]), keys)
+    keys = live_keys(keys)
+    dst = keys & 0xFFFFFFFF
+    rows = ops.row_offsets(keys >> 32, nv)
+    leave, enter = rows[1:] - rows[:-1], torch.bincount(dst, minlength=nv)
+    simple = (leave == 1) & (enter == 1)
+    cand = torch.nonzero(simple).reshape(-1)
+    succ = torch.full((nv,), -1, dtype=torch.int32, device=faces.device)
+    succ[cand] = dst[rows[:-1][cand]].to(torch.int32)
+    return succ, cand, int(keys.shape[0]), int(((leave > 0) | (enter > 0)).sum().item()), int(cand.shape[0])
 
 
 def mesh_adjacency(faces: torch.Tensor, nv: int):

@@ -1022,6 +1022,105 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_h_kernel(const float* _
 #define PC_WFLOATS (4096 + 8192)       // conv0b + conv2 (fp32 floats; the f16x3 image has the same byte size)
 #define PC_LDS_BYTES ((PC_WFLOATS + PC_W_XYZ + PC_NBIAS) * 4)
 
+// One query of phase C once its matrix sits in registers as A fragments (th / tl: split precision, tf: fp32): conv0a ... conv2 over the
+// ceil(P/16) tiles of the patch, online softmax, pooled 128 channels to xbar.  Shared by pointnet_feat_rows_kernel (matrix read from memory) and
+// pointnet_fc3_feat_rows_kernel (matrix made in the same kernel), so both apply the same arithmetic in the same order.
+template <bool H>
+__device__ __forceinline__ void feat_rows_query(const float* __restrict__ patches, int64_t q, int P, int ntile_rows, const half8 (&th)[4][2],
+                                                const half8 (&tl)[4][2], const f32x4 (&tf)[4][4], const f32x4* bias4, const f32x4* u4,
+                                                const float* xyz_l, const f32x4* w_c0b, const f32x4* w_c2, float s0, float& amax, int lane,
+                                                float* __restrict__ xbar) {
+    const int n = lane & 15, g = lane >> 4;
+    // per-lane (unreduced) online-softmax state over the patch points (nn.py:91-93)
+    f32x4 acc[8];
+    float mrun = -INFINITY, ssum = 0.f;
+#pragma unroll
+    for (int bb = 0; bb < 8; ++bb) acc[bb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int rb = 0; rb < ntile_rows; ++rb) {
+        const int rowi = rb * 16 + n;
+        const bool valid = rowi < P;
+        const int rowc = valid ? rowi : P - 1;
+        const float coord = (g < 3) ? patches[(q * P + rowc) * 3 + g] : 0.f;
+        f32x4 x0[4], y[8];
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) x0[bb] = bias4[4 * bb + g];
+        xyz_blocks<4>(coord, x0, xyz_l, lane);
+        relu_blocks<4>(x0);
+        __builtin_amdgcn_s_setprio(PPS_PRIO_PN);
+        float s = 0.f;                                   // attention logit of row n: linear in conv2's output (u = W3^T wq packed by the host)
+        if (H) {
+            HiLo a[2], b[2];
+            a[0] = split_f16_r(amax, x0[0], x0[1]);
+            a[1] = split_f16_r(amax, x0[2], x0[3]);
+            dense_blocks_f16x3<2, 4, 1>(a, (const half8*)w_c0b, bias4 + 16, lane, [&](int i, const f32x4& o0, const f32x4& o1) { b[i] = split_f16_r(amax, o0, o1); });
+            // x <- M x: three f16 products per (output block, k-block), A operands from registers
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) {
+                f32x4 o = bias4[32 + 4 * ob + g], c = {0.f, 0.f, 0.f, 0.f};           // conv1's bias seeds the sum
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+                    o = __builtin_amdgcn_mfma_f32_16x16x32_f16(th[ob][kb], b[kb].hi, o, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(th[ob][kb], b[kb].lo, c, 0, 0, 0);
+                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tl[ob][kb], b[kb].hi, c, 0, 0, 0);
+                }
+                o += c;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x0[ob][r] = fmaxf(o[r], 0.f);
+            }
+            a[0] = split_f16_r(amax, x0[0], x0[1]);
+            a[1] = split_f16_r(amax, x0[2], x0[3]);
+            dense_blocks_f16x3<2, 8, 1>(a, (const half8*)w_c2, bias4 + 48, lane, [&](int i, const f32x4& o0, const f32x4& o1) {
+                const f32x4 w0 = u4[4 * (2 * i) + g], w1 = u4[4 * (2 * i + 1) + g];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s += w0[r] * o0[r] + w1[r] * o1[r];
+                y[2 * i] = o0;
+                y[2 * i + 1] = o1;
+            });
+        } else {
+            f32x4 x1[4];
+            dense_blocks<4, 4, 1>(x0, x1, w_c0b, bias4 + 16, lane);
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) {
+                f32x4 o = bias4[32 + 4 * ob + g];
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb) {
+                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].x, x1[kb].x, o, 0, 0, 0);
+                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].y, x1[kb].y, o, 0, 0, 0);
+                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].z, x1[kb].z, o, 0, 0, 0);
+                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].w, x1[kb].w, o, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) x0[ob][r] = fmaxf(o[r], 0.f);
+            }
+            dense_blocks<4, 8, 1>(x0, y, w_c2, bias4 + 48, lane);
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) {
+                const f32x4 w4 = u4[4 * bb + g];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s += w4[r] * y[bb][r];
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        s += s0;
+        // online softmax: advance the state with this tile's logits, then add its rows (conv3 acts on the pooled vector, in the tail)
+        const float mblk = row16_max(valid ? s : -INFINITY);
+        const float mnew = fmaxf(mrun, mblk);
+        const float scale = __expf(mrun - mnew);
+        const float en = valid ? __expf(s - mnew) : 0.f;
+        mrun = mnew;
+        ssum = ssum * scale + en;
+#pragma unroll
+        for (int bb = 0; bb < 8; ++bb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[bb][r] = acc[bb][r] * scale + en * y[bb][r];
+    }
+    const float inv = 1.f / row16_sum(ssum);
+    rows16_sum_transposed8(acc, lane);            // lane (n,g): acc[0] = sum over the 16 lanes of block n & 7
+    if (n < 8) ((f32x4*)(xbar + q * 128))[4 * n + g] = acc[0] * inv;
+}
+
 template <bool H>
 __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float* __restrict__ patches, const float* __restrict__ trans2,
                                                                     int64_t Q, int P, const float* __restrict__ wpack,
@@ -1066,96 +1165,158 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float*
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) tf[ob][kb] = tq[(16 * ob + n) * 16 + 4 * kb + g];
         }
-        // per-lane (unreduced) online-softmax state over the patch points (nn.py:91-93)
-        f32x4 acc[8];
-        float mrun = -INFINITY, ssum = 0.f;
-#pragma unroll
-        for (int bb = 0; bb < 8; ++bb) acc[bb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int rb = 0; rb < ntile_rows; ++rb) {
-            const int rowi = rb * 16 + n;
-            const bool valid = rowi < P;
-            const int rowc = valid ? rowi : P - 1;
-            const float coord = (g < 3) ? patches[(q * P + rowc) * 3 + g] : 0.f;
-            f32x4 x0[4], y[8];
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) x0[bb] = bias4[4 * bb + g];
-            xyz_blocks<4>(coord, x0, xyz_l, lane);
-            relu_blocks<4>(x0);
-            __builtin_amdgcn_s_setprio(PPS_PRIO_PN);
-            float s = 0.f;                                   // attention logit of row n: linear in conv2's output (u = W3^T wq packed by the host)
-            if (H) {
-                HiLo a[2], b[2];
-                a[0] = split_f16_r(amax, x0[0], x0[1]);
-                a[1] = split_f16_r(amax, x0[2], x0[3]);
-                dense_blocks_f16x3<2, 4, 1>(a, (const half8*)w_c0b, bias4 + 16, lane, [&](int i, const f32x4& o0, const f32x4& o1) { b[i] = split_f16_r(amax, o0, o1); });
-                // x <- M x: three f16 products per (output block, k-block), A operands from registers
-#pragma unroll
-                for (int ob = 0; ob < 4; ++ob) {
-                    f32x4 o = bias4[32 + 4 * ob + g], c = {0.f, 0.f, 0.f, 0.f};           // conv1's bias seeds the sum
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) {
-                        o = __builtin_amdgcn_mfma_f32_16x16x32_f16(th[ob][kb], b[kb].hi, o, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(th[ob][kb], b[kb].lo, c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(tl[ob][kb], b[kb].hi, c, 0, 0, 0);
-                    }
-                    o += c;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x0[ob][r] = fmaxf(o[r], 0.f);
-                }
-                a[0] = split_f16_r(amax, x0[0], x0[1]);
-                a[1] = split_f16_r(amax, x0[2], x0[3]);
-                dense_blocks_f16x3<2, 8, 1>(a, (const half8*)w_c2, bias4 + 48, lane, [&](int i, const f32x4& o0, const f32x4& o1) {
-                    const f32x4 w0 = u4[4 * (2 * i) + g], w1 = u4[4 * (2 * i + 1) + g];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s += w0[r] * o0[r] + w1[r] * o1[r];
-                    y[2 * i] = o0;
-                    y[2 * i + 1] = o1;
-                });
-            } else {
-                f32x4 x1[4];
-                dense_blocks<4, 4, 1>(x0, x1, w_c0b, bias4 + 16, lane);
-#pragma unroll
-                for (int ob = 0; ob < 4; ++ob) {
-                    f32x4 o = bias4[32 + 4 * ob + g];
-#pragma unroll
-                    for (int kb = 0; kb < 4; ++kb) {
-                        o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].x, x1[kb].x, o, 0, 0, 0);
-                        o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].y, x1[kb].y, o, 0, 0, 0);
-                        o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].z, x1[kb].z, o, 0, 0, 0);
-                        o = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[ob][kb].w, x1[kb].w, o, 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x0[ob][r] = fmaxf(o[r], 0.f);
-                }
-                dense_blocks<4, 8, 1>(x0, y, w_c2, bias4 + 48, lane);
-#pragma unroll
-                for (int bb = 0; bb < 8; ++bb) {
-                    const f32x4 w4 = u4[4 * bb + g];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s += w4[r] * y[bb][r];
-                }
-            }
-            __builtin_amdgcn_s_setprio(0);
-            s += __shfl_xor(s, 16);
-            s += __shfl_xor(s, 32);
-            s += s0;
-            // online softmax: advance the state with this tile's logits, then add its rows (conv3 acts on the pooled vector, in the tail)
-            const float mblk = row16_max(valid ? s : -INFINITY);
-            const float mnew = fmaxf(mrun, mblk);
-            const float scale = __expf(mrun - mnew);
-            const float en = valid ? __expf(s - mnew) : 0.f;
-            mrun = mnew;
-            ssum = ssum * scale + en;
-#pragma unroll
-            for (int bb = 0; bb < 8; ++bb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[bb][r] = acc[bb][r] * scale + en * y[bb][r];
-        }
-        const float inv = 1.f / row16_sum(ssum);
-        rows16_sum_transposed8(acc, lane);            // lane (n,g): acc[0] = sum over the 16 lanes of block n & 7
-        if (n < 8) ((f32x4*)(xbar + q * 128))[4 * n + g] = acc[0] * inv;
+        feat_rows_query<H>(patches, q, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
     }
     if (H) range_commit(amax, flag);
+}
+
+// =====================================================================================================
+// Split precision without the round trip of M through memory: phase B's head on its own, then ONE kernel that makes M slice by slice in LDS and
+// consumes it (fc3 + phase C).  pointnet_stn_fc_h_kernel / pointnet_feat_rows_kernel<true> stay as the two-kernel path (PPS_PN_FUSED=0).
+// =====================================================================================================
+// The head: g[q,256] -> fc1(128, ReLU) -> fc2(64, ReLU) = u, written ALREADY SPLIT as the B operand of fc3:  uh[q][kb 2][part 2][g 4][8 halfs]
+// (256 B per query; lane (query n, g) of the reader takes half8 (2 kb + part) * 4 + g).  Weight chunks 0..4 of the fc image, streamed as in
+// pointnet_stn_fc_h_kernel; the same values are split (and range-tracked) as there.
+#define PH_LDS_BYTES (2 * CH4 * 16)
+__global__ __launch_bounds__(NT, 2) void pointnet_stn_head_h_kernel(const float* __restrict__ gin, int64_t Q, const f32x4* __restrict__ w16,
+                                                                    const float* __restrict__ bias, half8* __restrict__ uh, int* __restrict__ range) {
+    float amax = 0.f;
+    f32x4* buf0 = (f32x4*)pps_smem;
+    f32x4* buf1 = buf0 + CH4;
+    const f32x4* wg = w16;
+    const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const f32x4* bias_g = (const f32x4*)bias;                  // biases of the two layers: [128][64] floats
+    stream_prologue<CH4>(wg, buf0);
+    stream_wait();
+    __syncthreads();
+    f32x4 *cur = buf0, *nxt = buf1;
+    const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
+    int first, count, stride;
+    xcd_tile_range(ntiles, first, count, stride);
+    for (int it = 0; it < count; ++it) {
+        const int64_t qi = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
+        const bool qv = qi < Q;
+        const int64_t qc = qv ? qi : Q - 1;
+        HiLo ah[8], h[4], u[2];
+        {
+            f32x4 a[16];
+            const f32x4* src = (const f32x4*)(gin + qc * 256) + g;
+#pragma unroll
+            for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
+#pragma unroll
+            for (int kb = 0; kb < 8; ++kb) ah[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt, [&](const f32x4* w) {
+                dense_blocks_f16x3<8, 2, 1>(ah, (const half8*)w, bias_g + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { h[c] = split_f16_r(amax, o0, o1); }); });
+        stream_step<CH4>(wg, cur, nxt, [&](const f32x4* w) {
+            dense_blocks_f16x3<4, 4, 1>(h, (const half8*)w, bias_g + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { u[i] = split_f16_r(amax, o0, o1); }); });
+        if (qv) {
+            half8* dst = uh + qc * 16 + g;
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) { dst[(2 * kb) * 4] = u[kb].hi; dst[(2 * kb + 1) * 4] = u[kb].lo; }
+        }
+    }
+    range_commit(amax, range);
+}
+
+// fc3 + phase C.  One 8-wave workgroup per CU; a pass handles 16 consecutive queries, wave w consumes queries w and w + 8 of them.
+// M is made in four slices of 16 rows (slice ob = rows 16 ob .. 16 ob + 15 = chunks 8 ob .. 8 ob + 7 of the packed fc3 image): wave w runs chunk
+// 8 ob + w (rows 2 w, 2 w + 1 of the slice) for all 16 queries with the very call pointnet_stn_fc_h_kernel makes, its A fragments read straight
+// from global memory (L2) -- no other wave of the workgroup wants them, so there is no LDS weight stream -- and stores the split result to an LDS
+// exchange buffer in the fragment order of `trans2h` for one slice:  [query][kb 2][part 2][slot 4 m + g][8 halfs], 4 KiB per query (+ 16 B of
+// padding: the 8 lanes a ds_write_b128 serves per cycle are 8 queries).  After a barrier every wave picks up the slice of its first query, 16
+// registers.  The second query's matrix cannot all wait in registers behind the first one's (the consumer loop needs ~197 of 256 with its own 64):
+// queries 8 .. 15 of the pass have TWO buffers, slice ob goes to buffer ob & 1, slices 0 and 1 are picked up (32 registers) and slices 2 and 3
+// stay where they were made until the second query's turn; the barrier at the head of the next pass keeps them until then.
+// LDS: 52 KiB of resident weights and biases + 3 x 8 queries x 4 KiB = 149 KiB.
+// Every (row of M, query) pair and every patch row is accumulated as in the two-kernel path: same bits.
+#define PF_NT 512
+#define PF_QSTRIDE 257                 // half8 per query of an exchange buffer: 4 KiB + 16 B
+#define PF_BUF (8 * PF_QSTRIDE)        // half8 per buffer of 8 queries
+#define PF_LDS_BYTES (PC_LDS_BYTES + 3 * PF_BUF * 16)
+__global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const float* __restrict__ patches, const half8* __restrict__ uh,
+                                                                          int64_t Q, int P, const f32x4* __restrict__ wfc,
+                                                                          const float* __restrict__ bias_fc, const float* __restrict__ wpack,
+                                                                          const f32x4* __restrict__ wdense, const float* __restrict__ bias,
+                                                                          float* __restrict__ xbar, int* __restrict__ flag) {
+    float amax = 0.f;
+    f32x4* w_l = (f32x4*)pps_smem;                       // [conv0b 1024 f32x4][conv2 2048 f32x4], packed A fragments
+    float* xyz_l = (float*)(w_l + PC_WFLOATS / 4);
+    float* bias_l = xyz_l + PC_W_XYZ;
+    half8* ex = (half8*)(bias_l + PC_NBIAS);
+    const f32x4* bias4 = (const f32x4*)bias_l;
+    const f32x4* u4 = bias4 + 144;                       // W3^T wq: 128 values in the block layout of conv2's output
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;
+    for (int i = threadIdx.x; i < PC_WFLOATS / 4; i += PF_NT) w_l[i] = wdense[i];
+    lds_fill(xyz_l, wpack, PC_W_XYZ);
+    lds_fill(bias_l, bias, PC_NBIAS);
+    const float s0 = bias[576 + 256];                    // wq . b3 + bq
+    const f32x4* w_c0b = w_l;
+    const f32x4* w_c2 = w_l + 1024;
+    const int ntile_rows = (P + 15) / 16;
+    const f32x4* w3 = wfc + 5 * CH4;                     // fc3: chunks 5 .. 36 of the fc image
+    const f32x4* b3 = (const f32x4*)(bias_fc + 192);
+    // producer: query n of the pass (n >= 8: buffer 1 + (ob & 1)), rows 2 wave, 2 wave + 1 of the slice
+    half8* ex_w = ex + (n < 8 ? n * PF_QSTRIDE : PF_BUF + (n - 8) * PF_QSTRIDE) + 8 * wave + g;
+    // consumer: slot 4 m + g of each 1 KiB fragment block of query `wave` (first) and `wave + 8` (second, its buffer 0)
+    const half8* ex_r = ex + wave * PF_QSTRIDE + 4 * n + g;
+    const half8* ex_r2 = ex_r + PF_BUF;
+
+    const int ntiles = (int)((Q + 15) / 16);
+    int first, count, stride;
+    xcd_tile_range(ntiles, first, count, stride);
+    const f32x4 tf[4][4] = {};                           // the fp32 matrix of feat_rows_query: not used in split precision
+    for (int it = 0; it < count; ++it) {
+        const int64_t q0 = (int64_t)(first + it * stride) * 16;
+        half8 th[4][2], tl[4][2], th2[2][2], tl2[2][2];
+        {
+            const int64_t qc = q0 + n < Q ? q0 + n : Q - 1;
+            HiLo u[2];
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) { u[kb].hi = uh[qc * 16 + (2 * kb) * 4 + g]; u[kb].lo = uh[qc * 16 + (2 * kb + 1) * 4 + g]; }
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) {
+                __syncthreads();                         // the slice in the buffer has been picked up (first pass: the resident weights are in place)
+                const int c = 8 * ob + wave;
+                const half8* wc = (const half8*)(w3 + c * CH4);
+                asm volatile("" : "+s"(wc));             // opaque: the chunk's 32 loads per lane stay behind the barrier instead of all four slices' being hoisted
+                dense_blocks_f16x3<2, 8, 0, false>(u, wc, b3 + 32 * c, lane, [&](int i, const f32x4& o0, const f32x4& o1) {
+                    // blocks 8c + 2i, 8c + 2i + 1: row 2 wave + (i >> 1) of the slice, k-block kb = i & 1
+                    const HiLo v = split_f16_r(amax, o0, o1);
+                    half8* d = ex_w + (n >= 8 ? (ob & 1) * PF_BUF : 0) + ((i & 1) * 2) * 64 + 4 * (i >> 1);
+                    d[0] = v.hi;
+                    d[64] = v.lo;
+                });
+                __syncthreads();
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+                    th[ob][kb] = ex_r[(2 * kb) * 64];
+                    tl[ob][kb] = ex_r[(2 * kb + 1) * 64];
+                    if (ob < 2) {
+                        th2[ob][kb] = ex_r2[ob * PF_BUF + (2 * kb) * 64];
+                        tl2[ob][kb] = ex_r2[ob * PF_BUF + (2 * kb + 1) * 64];
+                    }
+                }
+            }
+        }
+        if (q0 + wave < Q) feat_rows_query<true>(patches, q0 + wave, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
+        if (q0 + wave + 8 < Q) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+                for (int ob = 0; ob < 2; ++ob) {
+                    th[ob][kb] = th2[ob][kb];
+                    tl[ob][kb] = tl2[ob][kb];
+                    th[2 + ob][kb] = ex_r2[ob * PF_BUF + (2 * kb) * 64];
+                    tl[2 + ob][kb] = ex_r2[ob * PF_BUF + (2 * kb + 1) * 64];
+                }
+            }
+            feat_rows_query<true>(patches, q0 + wave + 8, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
+        }
+    }
+    range_commit(amax, flag);
 }
 
 // =====================================================================================================
@@ -1521,7 +1682,8 @@ int pps_pointnet_feat_rows_f32(const float* patches, const float* trans2, int64_
 }
 
 /* Split-precision PointNet branch ("f16x3"): w16[0..2] = f16x3 images of (c0b, s1, s2, s3), (fc1, fc2, fc3), (c0b, c1, c2, c3); the fp32
- * images supply the xyz layers and the biases.  trans2 (q x 16 KiB of scratch) holds the pre-split fragments between the kernels. */
+ * images supply the xyz layers and the biases.  trans2 (q x 16 KiB of scratch): its first q x 256 B hold the split output of the STN head between
+ * the kernels; with PPS_PN_FUSED=0 all of it holds the pre-split fragments of the per-query matrix. */
 int pps_pointnet_f16x3(const float* patches, int64_t q, int p, const float* const* weights /* [2..7] of the decode array */,
                        const void* const* w16, float* g, float* trans2, float* xbar, int32_t* range_flag, void* const* events, void* stream) {
     if (q < 0 || p < 1) return PPS_ERR_ARG;
@@ -1534,8 +1696,9 @@ int pps_pointnet_f16x3(const float* patches, int64_t q, int p, const float* cons
     if (rc != PPS_OK) return rc;
     static int once = set_lds(pointnet_stn_fc_h_kernel, PB_LDS_BYTES);
     (void)once;
-    // The per-query matrix M (16 KiB per query) crosses memory between these two kernels.  `sub` > 0: the pair runs sub-chunk by sub-chunk
-    // (M of a sub-chunk = sub x 16 KiB, written and read back to back; with `reuse` every sub-chunk uses the SAME scratch addresses) --
+    // Experiment hook of the two-kernel path, where the per-query matrix M (16 KiB per query) crosses memory between stn_fc_h and feat_rows.
+    // `sub` > 0: that pair runs sub-chunk by sub-chunk (M of a sub-chunk = sub x 16 KiB, written and read back to back; with `reuse` every
+    // sub-chunk uses the SAME scratch addresses) --
     // the measured answer to "does a cache-resident M help" (tools/time_pn_subchunks.py).  Results are bit-identical:
     // both kernels treat queries independently.
     static const int64_t sub = getenv("PPS_PN_SUB") ? atoll(getenv("PPS_PN_SUB")) : 0;
@@ -1552,13 +1715,33 @@ int pps_pointnet_f16x3(const float* patches, int64_t q, int p, const float* cons
         if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
         return rc;
     }
-    hipLaunchKernelGGL(pointnet_stn_fc_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), PB_LDS_BYTES, st, g, q,
+    // Default: M never leaves the CU.  The head writes u (256 B per query, already split) into the start of the trans2 slot, and one kernel runs
+    // fc3 and phase C (pointnet_fc3_feat_rows_kernel).  PPS_PN_FUSED=0 (read per call: a test switches it) keeps the two kernels with M in trans2.
+    const char* fused_env = getenv("PPS_PN_FUSED");
+    if (fused_env && fused_env[0] == '0' && fused_env[1] == 0) {
+        hipLaunchKernelGGL(pointnet_stn_fc_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), PB_LDS_BYTES, st, g, q,
+                           (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
+        if (events && events[1]) hipEventRecord((hipEvent_t)events[1], st);
+        if (hipGetLastError() != hipSuccess) return PPS_ERR_LAUNCH;
+        rc = launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
+        if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
+        return rc;
+    }
+    static int once_head = set_lds(pointnet_stn_head_h_kernel, PH_LDS_BYTES);
+    static int once_fused = set_lds(pointnet_fc3_feat_rows_kernel, PF_LDS_BYTES);
+    (void)once_head;
+    (void)once_fused;
+    hipLaunchKernelGGL(pointnet_stn_head_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), PH_LDS_BYTES, st, g, q,
                        (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
     if (events && events[1]) hipEventRecord((hipEvent_t)events[1], st);
     if (hipGetLastError() != hipSuccess) return PPS_ERR_LAUNCH;
-    rc = launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
+    int cus = cu_count();
+    if (cus <= 0) cus = 256;
+    const int64_t passes = (q + 15) / 16;
+    hipLaunchKernelGGL(pointnet_fc3_feat_rows_kernel, dim3((unsigned)(passes < cus ? passes : cus)), dim3(PF_NT), PF_LDS_BYTES, st, patches,
+                       (const half8*)trans2, q, p, (const f32x4*)w16[1], weights[3], weights[4], (const f32x4*)w16[2], weights[5], xbar, range);
     if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
-    return rc;
+    return PPS_LAUNCH_CHECK();
 }
 
 int pps_decode_tail_f32(const float* pooled, const float* xbar, int64_t q, const float* wpack, const float* bias,

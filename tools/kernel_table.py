@@ -4,6 +4,7 @@ import sys
 
 ORDER = ['interp_pool_kernel', 'interp_pool_f16x3_kernel', 'pointnet_feat_rows_kernel<false>', 'pointnet_feat_rows_kernel<true>',
          'pointnet_stn_rows_kernel<false>', 'pointnet_stn_rows_kernel<true>', 'pointnet_stn_fc_kernel', 'pointnet_stn_fc_h_kernel',
+         'pointnet_stn_head_h_kernel', 'pointnet_fc3_feat_rows_kernel',
          'pointnet_feat_rows_kernel', 'pointnet_stn_rows_kernel', 'knn_blocked_kernel<1>', 'decode_tail_kernel', 'decode_tail_h_kernel', 'patch_normalize_kernel',
          'rows_dense256_kernel']
 
@@ -11,7 +12,8 @@ ORDER = ['interp_pool_kernel', 'interp_pool_f16x3_kernel', 'pointnet_feat_rows_k
 def main(prefix):
     k = json.load(open(prefix + '_pmc.json'))['kernels']
     # a kernel whose name the profiler did not demangle (half8 arguments) is listed under its mangled name
-    k = dict(k, **{'pointnet_stn_fc_h_kernel': v for n, v in k.items() if 'pointnet_stn_fc_h_kernel' in n})
+    for plain in ('pointnet_stn_fc_h_kernel', 'pointnet_stn_head_h_kernel', 'pointnet_fc3_feat_rows_kernel'):
+        k = dict(k, **{plain: v for n, v in k.items() if plain in n})
     import os
     tag = os.path.basename(prefix)
     steps = None

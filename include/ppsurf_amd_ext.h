@@ -156,6 +156,44 @@ int ppsx_fill_loops(const int64_t* cand, int64_t nc, const int32_t* succ, int64_
 int ppsx_fill_emit(const float* verts, int64_t nv, const int32_t* succ, const int64_t* leader, const int32_t* len, const int64_t* vslot,
                    const int64_t* foff, int64_t nl, float* new_verts, int64_t nnew, int64_t* new_faces, int64_t nfnew, void* stream);
 
+/* ---- feature-preserving denoising: face-normal filtering, then a vertex update (csrc/pps_denoise.hip) ---------------------------------------
+ * new capability: replaces nothing -- the reference has no mesh denoising.  Driven by ppsurf_amd/denoise.py; the rule (Sun, Rosin, Martin,
+ * Langbein 2007) is written out at the top of csrc/pps_denoise.hip and in DESIGN.md section 20.  A face is valid when its three indices lie
+ * in [0, nv) and are pairwise distinct.  Row v of the incidence is the entries offsets[v] .. offsets[v + 1] - 1 (offsets int64 [nv + 1]) of
+ * inc int32 [ni], the valid faces that hold vertex v in ascending face index, as topology.incidence_rows builds them.  All arithmetic is
+ * fp64, every operation rounded on its own; one thread per face or vertex, no atomics: each entry is a pure function of its inputs.
+ *   ppsx_denoise_face_normals  normals f64 [nf,3]: for a valid face (a, b, c) of faces int64 [nf,3] over verts f32 [nv,3], widened:
+ *                              e1 = x_b - x_a, e2 = x_c - x_a, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x),
+ *                              L = sqrt((nx^2 + ny^2) + nz^2); n / L when L > 0 and finite, else (0, 0, 0).  An invalid face gets
+ *                              (0, 0, 0) and is not read through.
+ *                              nv < 0, nf < 0, nv or nf > 2^31 - 1, or -- with nf > 0 -- a NULL faces or normals or a NULL verts with
+ *                              nv > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_denoise_filter_pass   out f64 [nf,3]: one Jacobi pass of the normal filter over normals f64 [nf,3].  A valid face i = (a, b, c)
+ *                              merges the rows of a, b and c: the smallest head j is taken and every row that shows j moves on, so a
+ *                              face listed in several rows is visited once, in ascending index.  Per visit
+ *                              d = (n_i.x n_j.x + n_i.y n_j.y) + n_i.z n_j.z, and when d > threshold: w = (d - threshold) * (d - threshold),
+ *                              acc_c = acc_c + w * n_j.c.  L = sqrt((accx^2 + accy^2) + accz^2); out[i] = acc / L when L > 0 and finite,
+ *                              else n_i.  An invalid face gets (0, 0, 0).  A row whose offsets are not 0 <= offsets[v] <= offsets[v + 1]
+ *                              <= ni counts as empty and an entry outside [0, nf) is skipped; neither is read through.  The entries are
+ *                              taken as listed: the zero normal of an invalid face gives d = 0 and adds nothing.
+ *                              nv, nf or ni < 0, nv or nf > 2^31 - 1, a threshold that is NaN or outside [0, 1), out == normals, or --
+ *                              with nf > 0 -- a NULL faces, normals or out, a NULL offsets with nv > 0 or a NULL inc with ni > 0:
+ *                              PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_denoise_vertex_pass   out f64 [nv,3]: one Jacobi pass of the vertex update over x f64 [nv,3] with normals f64 [nf,3].  For the
+ *                              faces k = (a, b, c) of row v in row order: c_k = ((x_a + x_b) + x_c) / 3.0 per component, dv = c_k - x_v,
+ *                              t = (n_k.x dv.x + n_k.y dv.y) + n_k.z dv.z, acc = acc + n_k * t; out[v] = x_v + acc / double(count).  A
+ *                              row whose offsets are not 0 <= offsets[v] <= offsets[v + 1] <= ni is skipped whole; an entry outside
+ *                              [0, nf), an invalid face and a face that does not hold v are skipped and not counted; none is read
+ *                              through.  A vertex that counts no face: out[v] = x[v].
+ *                              nv, nf or ni < 0, nv or nf > 2^31 - 1, out == x, or -- with nv > 0 -- a NULL x, offsets or out, a NULL
+ *                              faces or normals with nf > 0 or a NULL inc with ni > 0: PPS_ERR_ARG, nothing is launched or written.
+ *                              nv == 0: 0, nothing is launched. */
+int ppsx_denoise_face_normals(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, double* normals, void* stream);
+int ppsx_denoise_filter_pass(const int64_t* faces, int64_t nf, int64_t nv, const int64_t* offsets, const int32_t* inc, int64_t ni,
+                             const double* normals, double threshold, double* out, void* stream);
+int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, int64_t nf, const double* normals, const int64_t* offsets,
+                             const int32_t* inc, int64_t ni, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

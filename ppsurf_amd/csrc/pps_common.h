@@ -59,6 +59,12 @@ __device__ __forceinline__ float max_raw(float a, float b) {
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// max(a, b, c) as ONE v_max3_f32: the value of max_raw(max_raw(a, b), c) (a maximum does not depend on the order of its arguments)
+__device__ __forceinline__ float max3_raw(float a, float b, float c) {
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 
 // The same reductions for FOUR values at once with the lane permutation folded INTO the arithmetic instruction (v_max_f32_dpp / v_add_f32_dpp: the
 // first source is read through the DPP permutation).  Written with dpp_mov the compiler keeps a separate v_mov_b32_dpp per step -- it pairs the

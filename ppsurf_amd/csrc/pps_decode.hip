@@ -738,9 +738,54 @@ __device__ __forceinline__ void stn_chain_h_tiles(const float (&coord)[T], const
     __builtin_amdgcn_s_setprio(0);
 }
 
-// H = false: fp32 (wdense = wpack + 256 floats of the same image); H = true: split precision (wdense = the f16x3 image)
+// ALL T full tiles of one query (T = fb <= 3: every patch below 64 rows) in ONE pass over the streamed weights.  No running maximum is kept: the T
+// copies of a pair of conv3 output blocks leave the matrix pipe together, are reduced over the tiles and with the query's parked left-over row
+// `prow` (-inf where the patch is not packed), then over the 16 rows, and stored.  The maximum is the same set of values as in the pass-by-pass
+// schedule, so g has the same bits.
+template <int T>
+__device__ __forceinline__ void stn_query_tiles(const float* __restrict__ qpatch, int P, const float* prow, float* gq, bool store, const float* xyz_l,
+                                                const f32x4* bias4, const f32x4* wg, f32x4*& cur, f32x4*& nxt, int lane, float& amax) {
+    const int n = lane & 15, g = lane >> 4;
+    float coord[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int row = t * 16 + n;
+        const int rowc = row < P ? row : P - 1;                   // padded rows repeat a valid point: max unaffected
+        coord[t] = (g < 3) ? qpatch[rowc * 3 + g] : 0.f;
+    }
+    f32x4 h0[T], h1[T];
+    stn_chain_h_tiles<T>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, [&](int t, int bb, const f32x4& o0, const f32x4& o1) {
+        h0[t] = o0; h1[t] = o1;
+        if (t != T - 1) return;
+        const f32x4 k0 = ((const f32x4*)prow)[4 * bb + g], k1 = ((const f32x4*)prow)[4 * (bb + 1) + g];
+        float p[4], s[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if constexpr (T == 3) {
+                p[r] = max_raw(max3_raw(h0[0][r], h0[1][r], h0[2][r]), k0[r]);
+                s[r] = max_raw(max3_raw(h1[0][r], h1[1][r], h1[2][r]), k1[r]);
+            } else if constexpr (T == 2) {
+                p[r] = max3_raw(h0[0][r], h0[1][r], k0[r]);
+                s[r] = max3_raw(h1[0][r], h1[1][r], k1[r]);
+            } else {
+                p[r] = max_raw(h0[0][r], k0[r]);
+                s[r] = max_raw(h1[0][r], k1[r]);
+            }
+        }
+        row16_max4(p[0], p[1], p[2], p[3]);
+        row16_max4(s[0], s[1], s[2], s[3]);
+        if (n == 0 && store) {
+            ((f32x4*)gq)[4 * bb + g] = f32x4{p[0], p[1], p[2], p[3]};
+            ((f32x4*)gq)[4 * (bb + 1) + g] = f32x4{s[0], s[1], s[2], s[3]};
+        }
+    });
+}
+
+// H = false: fp32 (wdense = wpack + 256 floats of the same image); H = true: split precision (wdense = the f16x3 image).
+// tmax (H only): 3 -- a query with at most three full tiles takes them through the chain in one pass (stn_query_tiles); 2 -- two tiles at a time
+// with a running maximum for every patch size (what fb > 3 always does).
 template <bool H>
-__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* __restrict__ patches, int64_t Q, int P, int pack,
+__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
                                                                    const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
                                                                    const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
     // flag: H -- where the range guard of the split reports (pps_common.h); !H -- gate of the fp32 fallback (may be null)
@@ -766,12 +811,16 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
     const PatchPacking pk = patch_packing(P, pack);
     const int64_t ngroups = (Q + pk.qg - 1) / pk.qg;
     const int ntiles = (int)((ngroups + PNW - 1) / PNW);
+    const bool one_pass = H && tmax >= 3 && pk.fb <= 3;
+    if (one_pass && !pk.packed)                                // no left-over rows: the wave's parked row (read by this wave alone) is the identity of max
+        for (int i = lane; i < PN_ROWF; i += 64) mypark[i] = -INFINITY;
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
         const int64_t q0 = ((int64_t)(first + it * stride) * PNW + wave) * pk.qg;
         if constexpr (H) {
-            // split precision: conv3's blocks are reduced as they are produced, and the full tiles of a query go through the chain two at a time
+            // split precision: conv3's blocks are reduced as they are produced, and the full tiles of a query go through the chain all at once (at
+            // most three: one_pass) or two at a time
             if (pk.packed) {
                 const int ql = n / pk.lo;
                 const int64_t qq = (q0 + ql < Q) ? q0 + ql : Q - 1;
@@ -782,6 +831,19 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
                     for (int r = 0; r < 4; ++r) { m0[r] = group_max(o0[r], pk.lo); m1[r] = group_max(o1[r], pk.lo); }
                     if ((n % pk.lo) == 0) { ((f32x4*)(mypark + ql * PN_ROWF))[4 * bb + g] = m0; ((f32x4*)(mypark + ql * PN_ROWF))[4 * (bb + 1) + g] = m1; }
                 });
+            }
+            if (one_pass) {
+                for (int qi = 0; qi < pk.qg; ++qi) {
+                    const int64_t q = q0 + qi;
+                    const bool qv = q < Q;
+                    const float* qpatch = patches + (qv ? q : Q - 1) * P * 3;
+                    const float* prow = mypark + qi * PN_ROWF;
+                    float* gq = gout + (qv ? q : 0) * 256;
+                    if (pk.fb == 3) stn_query_tiles<3>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
+                    else if (pk.fb == 2) stn_query_tiles<2>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
+                    else stn_query_tiles<1>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
+                }
+                continue;
             }
             for (int qi = 0; qi < pk.qg; ++qi) {
                 const int64_t q = q0 + qi;
@@ -1512,12 +1574,17 @@ static int launch_stn_rows(const float* patches, int64_t q, int p, const float* 
     static int once = set_lds(pointnet_stn_rows_kernel<H>, PA_LDS_BYTES);
     (void)once;
     const PnSplit sp = pn_split(q, p);
+    // split precision: the full tiles of a query in one pass where there are at most three; PPS_STN_TILES=2 (read per call: a test switches it) keeps
+    // the two-at-a-time schedule, same bits
+    const char* tiles_env = getenv("PPS_STN_TILES");
+    const int tmax = (tiles_env && atoi(tiles_env) == 2) ? 2 : 3;
     if (sp.q_packed > 0)
         hipLaunchKernelGGL(pointnet_stn_rows_kernel<H>, dim3(sp.grid_packed), dim3(PNT), PA_LDS_BYTES, (hipStream_t)stream, patches,
-                           sp.q_packed, p, 1, wpack, (const f32x4*)wdense, bias, g, flag);
+                           sp.q_packed, p, 1, tmax, wpack, (const f32x4*)wdense, bias, g, flag);
     if (q > sp.q_packed)
         hipLaunchKernelGGL(pointnet_stn_rows_kernel<H>, dim3(sp.grid_rest), dim3(PNT), PA_LDS_BYTES, (hipStream_t)stream,
-                           patches + sp.q_packed * p * 3, q - sp.q_packed, p, sp.rest_mode, wpack, (const f32x4*)wdense, bias, g + sp.q_packed * 256, flag);
+                           patches + sp.q_packed * p * 3, q - sp.q_packed, p, sp.rest_mode, tmax, wpack, (const f32x4*)wdense, bias,
+                           g + sp.q_packed * 256, flag);
     return PPS_LAUNCH_CHECK();
 }
 

@@ -279,10 +279,8 @@ __device__ __forceinline__ void join_f16(const HiLo& x, f32x4& y0, f32x4& y1) {
 // INIT = true: the main accumulators start from init[ob] (fp32 blocks of an earlier partial product over other input channels) instead of
 // the bias -- a layer whose input is the concatenation of two tensors is evaluated half by half.
 // `hook(ob, kb)` is called after the six MFMAs of every k-step have been issued: the place to issue ONE piece of the next weight chunk's copy
-// (see stream_step_spread in pps_decode.hip) -- the wave's own MFMAs are queued in the matrix pipe while the memory pipeline accepts the piece.
-// NP: f16 products per fp32 product -- 3 (hi.hi + hi.lo + lo.hi, the product's arithmetic), 2 (the weight's low part dropped) or 1 (plain f16):
-// the reduced forms exist for ONE measured experiment on fc_query (tools/fcq_products.md); nothing in the product instantiates them.
-template <int KB, int NOB, int ACT, bool FENCE = true, bool INIT = false, int NP = 3, class Sink, class Hook>
+// (see stream_step_spread_at in pps_decode.hip) -- the wave's own MFMAs are queued in the matrix pipe while the memory pipeline accepts the piece.
+template <int KB, int NOB, int ACT, bool FENCE = true, bool INIT = false, class Sink, class Hook>
 __device__ __forceinline__ void dense_blocks_f16x3_hook(const HiLo (&in)[KB], const half8* __restrict__ w, const f32x4* __restrict__ bias, int lane,
                                                         Sink&& sink, Hook&& hook, const f32x4* init = nullptr) {
     static_assert(NOB % 2 == 0, "output blocks are processed in pairs");
@@ -303,18 +301,14 @@ __device__ __forceinline__ void dense_blocks_f16x3_hook(const HiLo (&in)[KB], co
             }
             m0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, in[kb].hi, m0, 0, 0, 0);
             m1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, in[kb].hi, m1, 0, 0, 0);
-            if (NP >= 2) {
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, in[kb].lo, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, in[kb].lo, c1, 0, 0, 0);
-            }
-            if (NP >= 3) {
-                c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, in[kb].hi, c0, 0, 0, 0);
-                c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, in[kb].hi, c1, 0, 0, 0);
-            }
+            c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah0, in[kb].lo, c0, 0, 0, 0);
+            c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah1, in[kb].lo, c1, 0, 0, 0);
+            c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al0, in[kb].hi, c0, 0, 0, 0);
+            c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al1, in[kb].hi, c1, 0, 0, 0);
             hook(ob, kb);
             if (FENCE) {
-                __builtin_amdgcn_sched_group_barrier(PPS_SG_DSREAD, NP >= 3 ? 4 : 2, 0);
-                __builtin_amdgcn_sched_group_barrier(PPS_SG_MFMA, 2 * NP, 0);
+                __builtin_amdgcn_sched_group_barrier(PPS_SG_DSREAD, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(PPS_SG_MFMA, 6, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -424,23 +418,12 @@ __device__ __forceinline__ void chunk_copy_async(const f32x4* __restrict__ src, 
         asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds_addr), "v"(lane_off), "s"(piece) : "memory", "m0");
     }
 }
-// one 1 KiB-per-wave piece (index i of NF4) of the same copy: lets a caller spread the pieces of a chunk over its compute phase
-template <int NTHREADS>
-__device__ __forceinline__ void chunk_copy_piece(const f32x4* __restrict__ src, f32x4* dst, int i) {
-    unsigned lane_off = threadIdx.x * 16u;
-    asm volatile("" : "+v"(lane_off));
-    const int wave_base = threadIdx.x & ~63;
-    const char* piece = (const char*)src + (size_t)i * (NTHREADS * 16);
-    asm volatile("" : "+s"(piece));
-    const unsigned lds_addr = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + i * NTHREADS + wave_base));
-    asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds_addr), "v"(lane_off), "s"(piece) : "memory", "m0");
-}
-// The same piece with NO per-piece vector instruction: `voff` = this lane's byte offset INCLUDING the piece's (threadIdx.x * 16 + i * NTHREADS * 16),
+// One 1 KiB-per-wave piece (index i of NF4) of the same copy, so that a caller can spread the pieces of a chunk over its compute phase, with NO
+// per-piece vector instruction: `voff` = this lane's byte offset INCLUDING the piece's (threadIdx.x * 16 + i * NTHREADS * 16),
 // one VGPR per piece index made by stream_lane_offsets() once per kernel, and `chunk` = the chunk's first byte (one SGPR pair for all pieces of a
-// chunk, advanced by the caller).  chunk_copy_piece builds its lane offset and its source pointer per piece: the opaque "+v" copy of the offset is
-// a v_mov per piece, and the 18 x 4 piece pointers of a pass over the weights, all loop invariant, were hoisted out of the persistent loop and
-// spilled -- v_writelane / v_readlane: 227 of the 2264 vector instructions of a trip of interp_pool_f16x3_kernel
-// (profiles/round6_interp_isa_census.md).
+// chunk, advanced by the caller).  Built per piece, the opaque "+v" copy of the lane offset was a v_mov per piece, and the 18 x 4 piece pointers
+// of a pass over the weights, all loop invariant, were hoisted out of the persistent loop and spilled -- v_writelane / v_readlane: 227 of the
+// 2264 vector instructions of a trip of interp_pool_f16x3_kernel (profiles/round6_interp_isa_census.md).
 template <int NTHREADS, int NPIECES>
 __device__ __forceinline__ void stream_lane_offsets(unsigned (&voff)[NPIECES]) {
 #pragma unroll

@@ -1,11 +1,14 @@
 // Occupancy decoder of PPSurf for gfx950: interpolation-attention branch, PointNet patch branch, MLP tail.
 //
 // All kernels share one structure (pps_common.h):
-//   * a workgroup = 8 waves (512 threads, 2 waves per SIMD, <= 256 VGPRs), persistent over "tiles";
+//   * a workgroup = 4 waves (256 threads), two workgroups per CU, so that the two waves of a SIMD (<= 256 VGPRs each) belong to different
+//     workgroups and run decoupled; persistent over "tiles".  Two kernels run one 8-wave workgroup per CU instead: interp_pool_f16x3_kernel
+//     (2 queries per pass over the weights) and pointnet_fc3_feat_rows_kernel (16 queries per pass);
 //   * each wave owns 16 rows and keeps their activations in registers in the MFMA C/D layout of
 //     v_mfma_f32_16x16x4_f32 (exact fp32, 157 TFLOP/s peak), chaining layers without leaving registers;
-//   * the layer weights, packed on the host in A-operand order, are streamed global(L2) -> registers -> LDS
-//     in 8..32 KiB chunks, double buffered, one barrier per chunk, shared by the 8 waves.
+//   * the layer weights, packed on the host in A-operand order, are copied global(L2) -> LDS (global_load_lds, pps_common.h) in 16 or 32 KiB
+//     chunks, double buffered, one barrier per chunk, shared by the waves of the workgroup.  Weights that fit stay resident in LDS instead
+//     (interp_small, phase C of the PointNet branch).
 //
 // Reference semantics (eval mode, BatchNorm folded by the host, see ppsurf_amd/decoder.py):
 //   source/poco_model.py:381-419, source/base/nn.py:72-96,133-190,305-373,415-417, source/ppsurf_model.py:82-117.
@@ -15,13 +18,9 @@
 
 using namespace pps;
 
-#ifndef NT
 #define NT 256                 // threads per workgroup (4 waves); 2 workgroups per CU run decoupled
-#endif
 #define NW (NT / 64)            // waves per workgroup
-#ifndef WG_PER_CU
 #define WG_PER_CU (512 / NT)
-#endif
 #ifndef PPS_PRIO
 #define PPS_PRIO 1
 #endif
@@ -46,16 +45,7 @@ __device__ __forceinline__ void stream_step(const f32x4* __restrict__ gnext, f32
 // waves of a workgroup queue up in the CU's memory pipeline (32 KiB at 64 B/clk = 512 cycles per chunk) while every wave sits in the issue and the
 // matrix pipe is idle -- a cycle trace of the split-precision interpolation kernel (round 3, profiles/NOTES_r3.md) showed 12 % of a step in the issue
 // and 20 % in the barrier behind it; spread out, a piece is accepted while the wave's own queued MFMAs execute.
-template <int CHUNK_F4_NEXT, int NTH = NT, class F>
-__device__ __forceinline__ void stream_step_spread(const f32x4* __restrict__ gnext, f32x4*& cur, f32x4*& nxt, F&& compute) {
-    f32x4* dst = nxt;
-    compute((const f32x4*)cur, [&](int i) { if (i < CHUNK_F4_NEXT / NTH) chunk_copy_piece<NTH>(gnext, dst, i); });
-    stream_wait();
-    __syncthreads();
-    f32x4* t = cur; cur = nxt; nxt = t;
-}
-
-// stream_step_spread with the pieces addressed by chunk_copy_piece_at: `chunk` = first byte of the NEXT chunk (SGPR pair kept by the caller),
+// The pieces are addressed by chunk_copy_piece_at: `chunk` = first byte of the NEXT chunk (SGPR pair kept by the caller),
 // voff = the per-lane piece offsets of stream_lane_offsets (no vector instruction per piece)
 template <int CHUNK_F4_NEXT, int NTH = NT, class F>
 __device__ __forceinline__ void stream_step_spread_at(const char* chunk, const unsigned (&voff)[CHUNK_F4_NEXT / NTH], f32x4*& cur, f32x4*& nxt, F&& compute) {
@@ -66,10 +56,6 @@ __device__ __forceinline__ void stream_step_spread_at(const char* chunk, const u
     f32x4* t = cur; cur = nxt; nxt = t;
 }
 
-template <int CHUNK_F4, int NTH = NT>
-__device__ __forceinline__ void stream_prologue(const f32x4* __restrict__ g, f32x4* buf) {
-    chunk_copy_async<CHUNK_F4 / NTH, NTH>(g, buf);
-}
 
 __device__ __forceinline__ void lds_fill(float* dst, const float* __restrict__ src, int nfloats) {
     for (int i = threadIdx.x; i < nfloats; i += blockDim.x) dst[i] = src[i];
@@ -99,6 +85,43 @@ __device__ __forceinline__ void relu_blocks(f32x4* a) {
 
 extern __shared__ __attribute__((aligned(16))) char pps_smem[];
 
+// Head of every streamed kernel: the two chunk buffers (BUF_F4 f32x4 each) are the first 2 * BUF_F4 * 16 bytes of the dynamic LDS -- a kernel carves
+// its own arrays behind them and fills them BEFORE this call.  Fetches the first chunk (FIRST_F4 f32x4 at g), waits for it and publishes it together
+// with the kernel's own LDS fills; cur = the chunk to compute on, nxt = where the next one goes.
+template <int BUF_F4, int FIRST_F4 = BUF_F4, int NTH = NT>
+__device__ __forceinline__ void stream_begin(const f32x4* __restrict__ g, f32x4*& cur, f32x4*& nxt) {
+    chunk_copy_async<FIRST_F4 / NTH, NTH>(g, (f32x4*)pps_smem);
+    stream_wait();
+    __syncthreads();
+    cur = (f32x4*)pps_smem;
+    nxt = cur + BUF_F4;
+}
+
+// The row (query) of lane (n, .) of wave `wave` in tile `tile` of the kernels with 16 rows per wave and NW waves per tile: `valid` = inside the m
+// rows there are; c = the row clamped to the last one, so that the loads of an idle lane stay in bounds.
+struct TileRow { int64_t i, c; bool valid; };
+__device__ __forceinline__ TileRow tile_row(int tile, int wave, int n, int64_t m) {
+    TileRow r;
+    r.i = (int64_t)tile * (NW * 16) + wave * 16 + n;
+    r.valid = r.i < m;
+    r.c = r.valid ? r.i : m - 1;
+    return r;
+}
+
+// End of both tails: lane (query n, g = 0) holds the query's two logits in o.x, o.y; occupancy (optional) = softmax difference p0 - p1
+__device__ __forceinline__ void store_logits(const f32x4& o, const TileRow& q, int g, float* __restrict__ logits, float* __restrict__ occ) {
+    if (q.valid && g == 0) {
+        const float l0 = o.x, l1 = o.y;
+        logits[q.i * 2] = l0;
+        logits[q.i * 2 + 1] = l1;
+        if (occ) {
+            const float mx = fmaxf(l0, l1);
+            const float e0 = __expf(l0 - mx), e1 = __expf(l1 - mx);
+            occ[q.i] = (e0 - e1) / (e0 + e1);
+        }
+    }
+}
+
 
 // =====================================================================================================
 // rows_dense256: out[m,256] = in[m,256] W^T + b
@@ -108,44 +131,38 @@ extern __shared__ __attribute__((aligned(16))) char pps_smem[];
 __global__ __launch_bounds__(NT, 2) void rows_dense256_kernel(const float* __restrict__ in, int64_t rs, int64_t cs, int64_t m,
                                                               const float* __restrict__ wpack, const float* __restrict__ bias,
                                                               float* __restrict__ out) {
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* bias_l = (float*)(buf1 + CH4);
+    float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
     const f32x4* wg = (const f32x4*)wpack;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias, 256);
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
 
     const int ntiles = (int)((m + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        const int64_t row = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
-        const bool rv = row < m;
-        const int64_t rc = rv ? row : m - 1;
+        const TileRow r = tile_row(first + it * stride, wave, n, m);
         f32x4 a[16];
         if (cs == 1) {
-            const f32x4* src = (const f32x4*)(in + rc * rs) + g;
+            const f32x4* src = (const f32x4*)(in + r.c * rs) + g;
 #pragma unroll
             for (int b = 0; b < 16; ++b) a[b] = src[4 * b];
         } else {
 #pragma unroll
             for (int b = 0; b < 16; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) a[b][r] = in[rc * rs + (int64_t)(16 * b + 4 * g + r) * cs];
+                for (int j = 0; j < 4; ++j) a[b][j] = in[r.c * rs + (int64_t)(16 * b + 4 * g + j) * cs];
         }
-        f32x4* dst = (f32x4*)(out + rc * 256) + g;
+        f32x4* dst = (f32x4*)(out + r.c * 256) + g;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             f32x4 o[2];
             stream_step<CH4>(wg + ((c + 1) & 7) * CH4, cur, nxt,
                            [&](const f32x4* w) { dense_blocks<16, 2, 0>(a, o, w, bias4 + 8 * c, lane); });
-            if (rv) { dst[4 * (2 * c)] = o[0]; dst[4 * (2 * c + 1)] = o[1]; }
+            if (r.valid) { dst[4 * (2 * c)] = o[0]; dst[4 * (2 * c + 1)] = o[1]; }
         }
     }
 }
@@ -165,9 +182,7 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
                                                             const float* __restrict__ bias, float* __restrict__ pooled,
                                                             const int* __restrict__ gate) {
     if (gate_closed(gate)) return;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* xyz_l = (float*)(buf1 + CH4);
+    float* xyz_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     float* bias_l = xyz_l + IP_W_XYZ;
     float* msm = bias_l + IP_NBIAS;      // [8][64] per-wave row max of every head
     float* mss = msm + NW * 64;          // [NW][64] per-wave sum of exp
@@ -179,10 +194,8 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 
     lds_fill(xyz_l, wpack, IP_W_XYZ);
     lds_fill(bias_l, bias, IP_NBIAS);
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
 
     const int ntiles = (int)((Q + NW / 4 - 1) / (NW / 4));       // 4 waves (64 neighbours) per query
     int first, count, stride;
@@ -297,6 +310,7 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 #define IH_WG_PER_CU (512 / IH_NT)
 #define IH_CH4 (CH4 * IH_OB / 2)
 #define IH_NCH (32 / IH_OB + 4 / IH_OB)       // chunks per pass: fc2 and fc3 16 output blocks each, fc_query 4
+static_assert(IH_OB == 2, "the weight pointer of the kernel's layer step wraps behind the step that fetches the last chunk: right for two output blocks per chunk only");
 #define IH_LDS_BYTES (2 * IH_CH4 * 16 + (IP_W_XYZ + IP_NBIAS + IH_NW * 64 * 3 + IH_NW * 256) * 4)
 
 __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float* __restrict__ G, const float* __restrict__ pts,
@@ -305,9 +319,7 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
                                                                      const f32x4* __restrict__ w16, const float* __restrict__ bias,
                                                                      float* __restrict__ pooled, int* __restrict__ range) {
     float amax = 0.f;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + IH_CH4;
-    float* xyz_l = (float*)(buf1 + IH_CH4);
+    float* xyz_l = (float*)((f32x4*)pps_smem + 2 * IH_CH4);
     float* bias_l = xyz_l + IP_W_XYZ;
     float* msm = bias_l + IP_NBIAS;
     float* mss = msm + IH_NW * 64;
@@ -319,10 +331,8 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
 
     lds_fill(xyz_l, wxyz, IP_W_XYZ);
     lds_fill(bias_l, bias, IP_NBIAS);
-    stream_prologue<IH_CH4, IH_NT>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<IH_CH4, IH_CH4, IH_NT>(wg, cur, nxt);
     // the weight stream: one SGPR pointer to the chunk being fetched (advanced after every step, back to the first chunk after the last one) and
     // one VGPR byte offset per piece -- no vector instruction and no spilled pointer per piece (pps_common.h, chunk_copy_piece_at)
     unsigned voff[IH_CH4 / IH_NT];
@@ -355,17 +365,14 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
             for (int kb = 0; kb < 8; ++kb) x[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
         }
         __builtin_amdgcn_s_setprio(PPS_PRIO);
-        // the 4 (8-wave workgroup) pieces of the next chunk's copy go out after k-steps 0, 2, 4, 6 of the first output-block pair
-#ifndef PPS_FCQ_PRODUCTS
-#define PPS_FCQ_PRODUCTS 3      // f16 products per fp32 product in fc_query (2, 1: experiment builds only, python -m ppsurf_amd.build --variant)
-#endif
+        // One streamed layer step: IH_OB output blocks of ACTV(BIAS + W IN) from the current chunk, handed pair by pair to SINK; the 4 (8-wave
+        // workgroup) pieces of the next chunk's copy go out after k-steps 0, 2, 4, 6 of the first output-block pair.
         // LAST: the step that fetches the last chunk of the pass -- the pointer wraps to the first chunk behind it
-#define IH_STEP(LAST, IN, BIAS, ACTV, SINK) IH_STEP_NP(LAST, IN, BIAS, ACTV, SINK, 3)
-#define IH_STEP_NP(LAST, IN, BIAS, ACTV, SINK, NPR)                                                                                   \
+#define IH_STEP(LAST, IN, BIAS, ACTV, SINK)                                                                                           \
         {                                                                                                                             \
             stream_step_spread_at<IH_CH4, IH_NT>(snext, voff, cur, nxt, [&](const f32x4* w, auto&& piece) {                            \
-                dense_blocks_f16x3_hook<8, IH_OB, ACTV, true, false, NPR>(IN, (const half8*)w, BIAS, lane, SINK,                       \
-                                                    [&](int ob, int kb) { if (ob == 0 && (kb & 1) == 0) piece(kb >> 1); if (IH_CH4 / IH_NT > 4 && ob == 0 && (kb & 1)) piece(4 + (kb >> 1)); }); }); \
+                dense_blocks_f16x3_hook<8, IH_OB, ACTV>(IN, (const half8*)w, BIAS, lane, SINK,                                         \
+                                                        [&](int ob, int kb) { if (ob == 0 && (kb & 1) == 0) piece(kb >> 1); }); });    \
             snext = (LAST) ? wfirst : snext + (size_t)IH_CH4 * 16;                                                                     \
             asm volatile("" : "+s"(snext));      /* opaque: one running pointer, not 18 hoisted ones */                                \
         }
@@ -378,10 +385,9 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
         f32x4 b[4];
 #pragma unroll
         for (int c = 0; c < 4 / IH_OB; ++c)                            // fc_query: 64 heads
-            IH_STEP_NP(c + 32 / IH_OB + 2 == IH_NCH, x, bias4 + 128 + 4 * IH_OB * c, 0,
-                       ([&](int p, const f32x4& o0, const f32x4& o1) { b[IH_OB * c + 2 * p] = o0; b[IH_OB * c + 2 * p + 1] = o1; }), PPS_FCQ_PRODUCTS);
+            IH_STEP(c + 32 / IH_OB + 2 == IH_NCH, x, bias4 + 128 + 4 * IH_OB * c, 0,
+                    ([&](int p, const f32x4& o0, const f32x4& o1) { b[IH_OB * c + 2 * p] = o0; b[IH_OB * c + 2 * p + 1] = o1; }));
 #undef IH_STEP
-#undef IH_STEP_NP
         __builtin_amdgcn_s_setprio(0);
         // ---- softmax over the 64 neighbours (4 waves x 16 rows) for each of the 64 heads: as in interp_pool_kernel -------------
         float e[16];
@@ -598,13 +604,9 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
 // Two INDEPENDENT 4-wave workgroups per CU (16 KiB weight chunks so that both fit the LDS next to the parked rows) instead of
 // one 8-wave workgroup with 32 KiB chunks: the two waves of a SIMD then belong to different workgroups, drift out of phase and --
 // with the wave priority raised for the MFMA phase -- keep the matrix pipe fed while the other one reduces / parks
-// (stn_rows 2.00 -> 1.95 ms, feat_rows 2.47 -> 2.30 ms per 50000 queries; PNT=512 / PCH4=2048 is the old configuration).
-#ifndef PNT
+// (stn_rows 2.00 -> 1.95 ms, feat_rows 2.47 -> 2.30 ms per 50000 queries against 512 threads / 32 KiB chunks).
 #define PNT 256                // threads of the PointNet row kernels
-#endif
-#ifndef PCH4
 #define PCH4 1024              // f32x4 per streamed weight chunk of the PointNet row kernels (1024 = 16 KiB)
-#endif
 #define PNW (PNT / 64)
 #define PN_WG_PER_CU (512 / PNT)
 #define PN_C2N (2048 / PCH4)   // chunks of conv2 (64 -> 128: 2048 f32x4) and of conv3 (128 -> 256: 8192 f32x4)
@@ -662,46 +664,11 @@ __device__ __forceinline__ void stn_chain(float coord, f32x4 (&z)[16], const flo
     __builtin_amdgcn_s_setprio(0);
 }
 
-// the same chain in split precision (decoder dtype "f16x3"): conv0a stays an fp32 MFMA (K = 3), the four dense layers run as
-// three f16 products each; `wg` -> pps_pack_dense_f16x3 images of c0b, s1, s2, s3 (same byte sizes and chunk boundaries as fp32)
-__device__ __forceinline__ void stn_chain_h(float coord, f32x4 (&z)[16], const float* xyz_l, const f32x4* bias4, const f32x4* wg,
-                                            f32x4*& cur, f32x4*& nxt, int lane, float& amax) {
-    const int g = lane >> 4;
-    HiLo a[2], b[2], y[4];
-    {
-        f32x4 x0[4];
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) x0[bb] = bias4[4 * bb + g];
-        xyz_blocks<4>(coord, x0, xyz_l, lane);
-        relu_blocks<4>(x0);
-        a[0] = split_f16_r(amax, x0[0], x0[1]);
-        a[1] = split_f16_r(amax, x0[2], x0[3]);
-    }
-    __builtin_amdgcn_s_setprio(PPS_PRIO_PN);
-    stream_step<1024, PNT>(wg + 1024, cur, nxt, [&](const f32x4* w) {
-        dense_blocks_f16x3<2, 4, 1>(a, (const half8*)w, bias4 + 16, lane, [&](int i, const f32x4& o0, const f32x4& o1) { b[i] = split_f16_r(amax, o0, o1); }); });
-    stream_step<PCH4, PNT>(wg + 2048, cur, nxt, [&](const f32x4* w) {
-        dense_blocks_f16x3<2, 4, 1>(b, (const half8*)w, bias4 + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { a[i] = split_f16_r(amax, o0, o1); }); });
-#pragma unroll
-    for (int h = 0; h < PN_C2N; ++h)
-        stream_step<PCH4, PNT>(wg + 2048 + (h + 1) * PCH4, cur, nxt, [&](const f32x4* w) {
-            dense_blocks_f16x3<2, PN_C2OB, 1>(a, (const half8*)w, bias4 + 48 + 4 * PN_C2OB * h, lane,
-                                              [&](int i, const f32x4& o0, const f32x4& o1) { y[PN_C2OB / 2 * h + i] = split_f16_r(amax, o0, o1); }); });
-#pragma unroll
-    for (int c = 0; c < PN_C3N - 1; ++c)
-        stream_step<PCH4, PNT>(wg + 4096 + (c + 1) * PCH4, cur, nxt, [&](const f32x4* w) {
-            dense_blocks_f16x3<4, PN_C3OB, 1>(y, (const half8*)w, bias4 + 80 + 4 * PN_C3OB * c, lane,
-                                              [&](int i, const f32x4& o0, const f32x4& o1) { z[PN_C3OB * c + 2 * i] = o0; z[PN_C3OB * c + 2 * i + 1] = o1; }); });
-    stream_step<1024, PNT>(wg, cur, nxt, [&](const f32x4* w) {
-        dense_blocks_f16x3<4, PN_C3OB, 1>(y, (const half8*)w, bias4 + 80 + 4 * PN_C3OB * (PN_C3N - 1), lane,
-                                          [&](int i, const f32x4& o0, const f32x4& o1) { z[PN_C3OB * (PN_C3N - 1) + 2 * i] = o0; z[PN_C3OB * (PN_C3N - 1) + 2 * i + 1] = o1; }); });
-    __builtin_amdgcn_s_setprio(0);
-}
-
 // The split-precision chain for T tiles of one wave at once (pps_common.h, dense_blocks_f16x3_tiles): one pass over the streamed weights and one set
 // of A-fragment reads serve T x 16 rows.  conv3's output blocks are handed to zsink(tile, first_block, o0, o1) as they leave the matrix pipe (the
-// callers reduce them at once: a tile's 256 channels are never held).  Per tile the arithmetic is exactly that of stn_chain_h: results do not
-// depend on how tiles are grouped.
+// callers reduce them at once: a tile's 256 channels are never held).  conv0a stays an fp32 MFMA (K = 3), the four dense layers run as three f16
+// products each; `wg` -> pps_pack_dense_f16x3 images of c0b, s1, s2, s3 (same byte sizes and chunk boundaries as fp32).  Per tile the arithmetic does
+// not depend on T: results do not depend on how tiles are grouped.
 template <int T, class ZSink>
 __device__ __forceinline__ void stn_chain_h_tiles(const float (&coord)[T], const float* xyz_l, const f32x4* bias4, const f32x4* wg,
                                                   f32x4*& cur, f32x4*& nxt, int lane, float& amax, ZSink&& zsink) {
@@ -791,9 +758,7 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
     // flag: H -- where the range guard of the split reports (pps_common.h); !H -- gate of the fp32 fallback (may be null)
     if (!H && gate_closed(flag)) return;
     float amax = 0.f;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + PCH4;
-    float* xyz_l = (float*)(buf1 + PCH4);
+    float* xyz_l = (float*)((f32x4*)pps_smem + 2 * PCH4);
     float* bias_l = xyz_l + PA_W_XYZ;
     float* park = bias_l + PA_NBIAS;                       // [PNW][PN_PARK_ROWS][PN_ROWF] per-query left-over maxima
     const f32x4* bias4 = (const f32x4*)bias_l;
@@ -803,10 +768,8 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
 
     lds_fill(xyz_l, wpack, PA_W_XYZ);
     lds_fill(bias_l, bias, PA_NBIAS);
-    stream_prologue<1024, PNT>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<PCH4, 1024, PNT>(wg, cur, nxt);
 
     const PatchPacking pk = patch_packing(P, pack);
     const int64_t ngroups = (Q + pk.qg - 1) / pk.qg;
@@ -819,8 +782,8 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
     for (int it = 0; it < count; ++it) {
         const int64_t q0 = ((int64_t)(first + it * stride) * PNW + wave) * pk.qg;
         if constexpr (H) {
-            // split precision: conv3's blocks are reduced as they are produced, and the full tiles of a query go through the chain all at once (at
-            // most three: one_pass) or two at a time
+            // ---- split-precision schedule: conv3's blocks are reduced as they are produced, and the full tiles of a query go through the chain all
+            // at once (at most three: one_pass) or two at a time
             if (pk.packed) {
                 const int ql = n / pk.lo;
                 const int64_t qq = (q0 + ql < Q) ? q0 + ql : Q - 1;
@@ -843,7 +806,57 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
                     else if (pk.fb == 2) stn_query_tiles<2>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
                     else stn_query_tiles<1>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
                 }
-                continue;
+            } else {
+                for (int qi = 0; qi < pk.qg; ++qi) {
+                    const int64_t q = q0 + qi;
+                    const bool qv = q < Q;
+                    const int64_t qc = qv ? q : Q - 1;
+                    f32x4 rmax[16];
+#pragma unroll
+                    for (int bb = 0; bb < 16; ++bb)
+                        rmax[bb] = pk.packed ? ((const f32x4*)(mypark + qi * PN_ROWF))[4 * bb + g] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                    auto zmax = [&](int, int bb, const f32x4& o0, const f32x4& o1) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) { rmax[bb][r] = max_raw(rmax[bb][r], o0[r]); rmax[bb + 1][r] = max_raw(rmax[bb + 1][r], o1[r]); }
+                    };
+                    auto row_coord = [&](int rb) {
+                        const int row = rb * 16 + n;
+                        const int rowc = row < P ? row : P - 1;       // padded rows repeat a valid point: max unaffected
+                        return (g < 3) ? patches[(qc * P + rowc) * 3 + g] : 0.f;
+                    };
+                    int rb = 0;
+                    for (; rb + 1 < pk.fb; rb += 2) {
+                        const float coord[2] = {row_coord(rb), row_coord(rb + 1)};
+                        stn_chain_h_tiles<2>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
+                    }
+                    if (rb < pk.fb) {
+                        const float coord[1] = {row_coord(rb)};
+                        stn_chain_h_tiles<1>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
+                    }
+#pragma unroll
+                    for (int bb = 0; bb < 16; ++bb) {
+                        float p0 = rmax[bb][0], p1 = rmax[bb][1], p2 = rmax[bb][2], p3 = rmax[bb][3];
+                        row16_max4(p0, p1, p2, p3);                   // (the lane permutation folded into v_max_f32_dpp, pps_common.h)
+                        if (n == 0 && qv) ((f32x4*)(gout + q * 256))[4 * bb + g] = f32x4{p0, p1, p2, p3};
+                    }
+                }
+            }
+        } else {
+            // ---- fp32 schedule: one tile at a time, a running maximum over the tiles of a query
+            f32x4 z[16];
+            if (pk.packed) {
+                // the LO left-over rows of the QG queries of this wave, one tile
+                const int ql = n / pk.lo;
+                const int64_t qq = (q0 + ql < Q) ? q0 + ql : Q - 1;
+                const float coord = (g < 3) ? patches[(qq * P + pk.fb * 16 + (n % pk.lo)) * 3 + g] : 0.f;
+                stn_chain(coord, z, xyz_l, bias4, wg, cur, nxt, lane);
+#pragma unroll
+                for (int bb = 0; bb < 16; ++bb) {
+                    f32x4 m;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) m[r] = group_max(z[bb][r], pk.lo);
+                    if ((n % pk.lo) == 0) ((f32x4*)(mypark + ql * PN_ROWF))[4 * bb + g] = m;
+                }
             }
             for (int qi = 0; qi < pk.qg; ++qi) {
                 const int64_t q = q0 + qi;
@@ -853,72 +866,23 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
 #pragma unroll
                 for (int bb = 0; bb < 16; ++bb)
                     rmax[bb] = pk.packed ? ((const f32x4*)(mypark + qi * PN_ROWF))[4 * bb + g] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                auto zmax = [&](int, int bb, const f32x4& o0, const f32x4& o1) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { rmax[bb][r] = max_raw(rmax[bb][r], o0[r]); rmax[bb + 1][r] = max_raw(rmax[bb + 1][r], o1[r]); }
-                };
-                auto row_coord = [&](int rb) {
+                for (int rb = 0; rb < pk.fb; ++rb) {
                     const int row = rb * 16 + n;
                     const int rowc = row < P ? row : P - 1;       // padded rows repeat a valid point: max unaffected
-                    return (g < 3) ? patches[(qc * P + rowc) * 3 + g] : 0.f;
-                };
-                int rb = 0;
-                for (; rb + 1 < pk.fb; rb += 2) {
-                    const float coord[2] = {row_coord(rb), row_coord(rb + 1)};
-                    stn_chain_h_tiles<2>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
-                }
-                if (rb < pk.fb) {
-                    const float coord[1] = {row_coord(rb)};
-                    stn_chain_h_tiles<1>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
+                    const float coord = (g < 3) ? patches[(qc * P + rowc) * 3 + g] : 0.f;
+                    stn_chain(coord, z, xyz_l, bias4, wg, cur, nxt, lane);
+#pragma unroll
+                    for (int bb = 0; bb < 16; ++bb)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) rmax[bb][r] = max_raw(rmax[bb][r], z[bb][r]);
                 }
 #pragma unroll
                 for (int bb = 0; bb < 16; ++bb) {
                     float p0 = rmax[bb][0], p1 = rmax[bb][1], p2 = rmax[bb][2], p3 = rmax[bb][3];
-                    row16_max4(p0, p1, p2, p3);                   // (the lane permutation folded into v_max_f32_dpp, pps_common.h)
-                    if (n == 0 && qv) ((f32x4*)(gout + q * 256))[4 * bb + g] = f32x4{p0, p1, p2, p3};
+                    row16_max4(p0, p1, p2, p3);
+                    const f32x4 p = {p0, p1, p2, p3};
+                    if (n == 0 && qv) ((f32x4*)(gout + q * 256))[4 * bb + g] = p;
                 }
-            }
-            continue;
-        }
-        f32x4 z[16];
-        if (pk.packed) {
-            // the LO left-over rows of the QG queries of this wave, one tile
-            const int ql = n / pk.lo;
-            const int64_t qq = (q0 + ql < Q) ? q0 + ql : Q - 1;
-            const float coord = (g < 3) ? patches[(qq * P + pk.fb * 16 + (n % pk.lo)) * 3 + g] : 0.f;
-            if (H) stn_chain_h(coord, z, xyz_l, bias4, wg, cur, nxt, lane, amax); else stn_chain(coord, z, xyz_l, bias4, wg, cur, nxt, lane);
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb) {
-                f32x4 m;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) m[r] = group_max(z[bb][r], pk.lo);
-                if ((n % pk.lo) == 0) ((f32x4*)(mypark + ql * PN_ROWF))[4 * bb + g] = m;
-            }
-        }
-        for (int qi = 0; qi < pk.qg; ++qi) {
-            const int64_t q = q0 + qi;
-            const bool qv = q < Q;
-            const int64_t qc = qv ? q : Q - 1;
-            f32x4 rmax[16];
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb)
-                rmax[bb] = pk.packed ? ((const f32x4*)(mypark + qi * PN_ROWF))[4 * bb + g] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            for (int rb = 0; rb < pk.fb; ++rb) {
-                const int row = rb * 16 + n;
-                const int rowc = row < P ? row : P - 1;       // padded rows repeat a valid point: max unaffected
-                const float coord = (g < 3) ? patches[(qc * P + rowc) * 3 + g] : 0.f;
-                if (H) stn_chain_h(coord, z, xyz_l, bias4, wg, cur, nxt, lane, amax); else stn_chain(coord, z, xyz_l, bias4, wg, cur, nxt, lane);
-#pragma unroll
-                for (int bb = 0; bb < 16; ++bb)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) rmax[bb][r] = max_raw(rmax[bb][r], z[bb][r]);
-            }
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb) {
-                float p0 = rmax[bb][0], p1 = rmax[bb][1], p2 = rmax[bb][2], p3 = rmax[bb][3];
-                row16_max4(p0, p1, p2, p3);
-                const f32x4 p = {p0, p1, p2, p3};
-                if (n == 0 && qv) ((f32x4*)(gout + q * 256))[4 * bb + g] = p;
             }
         }
     }
@@ -934,74 +898,72 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
 // also kept the 768 bytes of the first two layers' biases there: 165 376 bytes for two workgroups, 1.5 KiB too many -- the kernel ran ONE 4-wave
 // workgroup per CU.)  The small biases are read from global memory, five times per tile.
 #define PB_LDS_BYTES (2 * CH4 * 16 + 4096 * 4)
-#ifndef PB_T
-#define PB_T 1                 // 16-query tiles a wave carries through fc3 together (2: no gain, 3: slower -- measured)
-#endif
 
 __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_kernel(const float* __restrict__ gin, int64_t Q,
                                                                 const float* __restrict__ wpack, const float* __restrict__ bias,
                                                                 float* __restrict__ trans2, const int* __restrict__ gate) {
     if (gate_closed(gate)) return;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* bias_l = (float*)(buf1 + CH4);
+    float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
     const f32x4* wg = (const f32x4*)wpack;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias + 192, 4096);
     const f32x4* bias_g = (const f32x4*)bias;                  // biases of the first two layers: [128][64] floats
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
 
-    // A wave carries PB_T tiles of 16 queries through the last layer together: its 1 MiB of weights is the bulk of the stream,
-    // and with one tile per wave the two workgroups of a CU would need 16 B/clk of LDS-DMA to keep the MFMA pipe busy (9.8 TB/s
-    // chip-wide, above what the path delivers); fc1 / fc2 (0.16 MiB) are simply streamed once per tile.
-    const int ntiles = (int)((Q + NW * 16 * PB_T - 1) / (NW * 16 * PB_T));
+    // One 16-query tile per wave: fc1 / fc2 (0.16 MiB) and fc3 (1 MiB, the bulk of the stream) are streamed once per tile.  Carrying two tiles of a
+    // wave through fc3 together gave no gain, three were slower (measured).
+    const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        f32x4 u[PB_T][4];
-        int64_t qcs[PB_T];
-        bool qvs[PB_T];
+        const TileRow q = tile_row(first + it * stride, wave, n, Q);
+        f32x4 a[16], h[8], u[4];
+        {
+            const f32x4* src = (const f32x4*)(gin + q.c * 256) + g;
 #pragma unroll
-        for (int t = 0; t < PB_T; ++t) {
-            const int64_t qi = (int64_t)(first + it * stride) * (NW * 16 * PB_T) + (wave * PB_T + t) * 16 + n;
-            qvs[t] = qi < Q;
-            qcs[t] = qvs[t] ? qi : Q - 1;
-            f32x4 a[16], h[8];
-            {
-                const f32x4* src = (const f32x4*)(gin + qcs[t] * 256) + g;
-#pragma unroll
-                for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt,
-                               [&](const f32x4* w) { dense_blocks<16, 2, 1>(a, &h[2 * c], w, bias_g + 8 * c, lane); });
-            stream_step<CH4>(t + 1 < PB_T ? wg : wg + 5 * CH4, cur, nxt,
-                           [&](const f32x4* w) { dense_blocks<8, 4, 1>(h, u[t], w, bias_g + 32, lane); });
+            for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
         }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt,
+                           [&](const f32x4* w) { dense_blocks<16, 2, 1>(a, &h[2 * c], w, bias_g + 8 * c, lane); });
+        stream_step<CH4>(wg + 5 * CH4, cur, nxt, [&](const f32x4* w) { dense_blocks<8, 4, 1>(h, u, w, bias_g + 32, lane); });
+        f32x4* dst = (f32x4*)(trans2 + q.c * 4096) + g;
 #pragma unroll 1
         for (int c = 0; c < 32; ++c) {
-            f32x4 o[PB_T][8];
+            f32x4 o[8];
             const f32x4* gn = (c + 1 < 32) ? wg + (6 + c) * CH4 : wg;
-            stream_step<CH4>(gn, cur, nxt, [&](const f32x4* w) {
+            stream_step<CH4>(gn, cur, nxt, [&](const f32x4* w) { dense_blocks<4, 8, 0>(u, o, w, bias4 + 32 * c, lane); });
+            if (q.valid) {
 #pragma unroll
-                for (int t = 0; t < PB_T; ++t) dense_blocks<4, 8, 0>(u[t], o[t], w, bias4 + 32 * c, lane);
-            });
-#pragma unroll
-            for (int t = 0; t < PB_T; ++t) {
-                if (qvs[t]) {
-                    f32x4* dst = (f32x4*)(trans2 + qcs[t] * 4096) + g;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) dst[4 * (8 * c + j)] = o[t][j];
-                }
+                for (int j = 0; j < 8; ++j) dst[4 * (8 * c + j)] = o[j];
             }
         }
     }
+}
+
+// The STN head in split precision, shared by the two kernels below: one row g[256] per lane (n, .) -> fc1(128, ReLU) -> fc2(64, ReLU) = u, every
+// layer input split (and range-tracked) on the way.  Weight chunks 0..4 of the fc image; `after` = the chunk fetched behind fc2.
+__device__ __forceinline__ void stn_head_h(const float* __restrict__ grow, const f32x4* wg, const f32x4* after, const f32x4* __restrict__ bias_g,
+                                           f32x4*& cur, f32x4*& nxt, int lane, float& amax, HiLo (&u)[2]) {
+    HiLo ah[8], h[4];
+    {
+        f32x4 a[16];
+        const f32x4* src = (const f32x4*)grow + (lane >> 4);
+#pragma unroll
+        for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
+#pragma unroll
+        for (int kb = 0; kb < 8; ++kb) ah[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt, [&](const f32x4* w) {
+            dense_blocks_f16x3<8, 2, 1>(ah, (const half8*)w, bias_g + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { h[c] = split_f16_r(amax, o0, o1); }); });
+    stream_step<CH4>(after, cur, nxt, [&](const f32x4* w) {
+        dense_blocks_f16x3<4, 4, 1>(h, (const half8*)w, bias_g + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { u[i] = split_f16_r(amax, o0, o1); }); });
 }
 
 // Split-precision variant ("f16x3"): the three layers as f16 hi/lo products, and trans2 is written ALREADY SPLIT in the A-operand
@@ -1012,42 +974,23 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_kernel(const float* __r
 __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_h_kernel(const float* __restrict__ gin, int64_t Q, const f32x4* __restrict__ w16,
                                                                   const float* __restrict__ bias, half8* __restrict__ trans2h, int* __restrict__ range) {
     float amax = 0.f;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* bias_l = (float*)(buf1 + CH4);
+    float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
     const f32x4* wg = w16;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias + 192, 4096);
     const f32x4* bias_g = (const f32x4*)bias;                  // biases of the first two layers: [128][64] floats
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        const int64_t qi = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
-        const bool qv = qi < Q;
-        const int64_t qc = qv ? qi : Q - 1;
-        HiLo ah[8], h[4], u[2];
-        {
-            f32x4 a[16];
-            const f32x4* src = (const f32x4*)(gin + qc * 256) + g;
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
-#pragma unroll
-            for (int kb = 0; kb < 8; ++kb) ah[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt, [&](const f32x4* w) {
-                dense_blocks_f16x3<8, 2, 1>(ah, (const half8*)w, bias_g + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { h[c] = split_f16_r(amax, o0, o1); }); });
-        stream_step<CH4>(wg + 5 * CH4, cur, nxt, [&](const f32x4* w) {
-            dense_blocks_f16x3<4, 4, 1>(h, (const half8*)w, bias_g + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { u[i] = split_f16_r(amax, o0, o1); }); });
-        half8* dst = trans2h + qc * 1024 + g;                         // + ((ob*2 + kb)*2 + part)*64 + 4*m
+        const TileRow q = tile_row(first + it * stride, wave, n, Q);
+        HiLo u[2];
+        stn_head_h(gin + q.c * 256, wg, wg + 5 * CH4, bias_g, cur, nxt, lane, amax, u);
+        half8* dst = trans2h + q.c * 1024 + g;                         // + ((ob*2 + kb)*2 + part)*64 + 4*m
 #pragma unroll 1
         for (int c = 0; c < 32; ++c) {
             const f32x4* gn = (c + 1 < 32) ? wg + (6 + c) * CH4 : wg;
@@ -1056,7 +999,7 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_h_kernel(const float* _
                     // blocks 8c + 2i, 8c + 2i + 1: row a = 2c + (i >> 1), k-block kb = i & 1
                     const int a = 2 * c + (i >> 1), kb = i & 1;
                     const HiLo v = split_f16_r(amax, o0, o1);
-                    if (qv) {
+                    if (q.valid) {
                         half8* d = dst + (((a >> 4) * 2 + kb) * 2) * 64 + 4 * (a & 15);
                         d[0] = v.hi;
                         d[64] = v.lo;
@@ -1084,15 +1027,34 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_h_kernel(const float* _
 #define PC_WFLOATS (4096 + 8192)       // conv0b + conv2 (fp32 floats; the f16x3 image has the same byte size)
 #define PC_LDS_BYTES ((PC_WFLOATS + PC_W_XYZ + PC_NBIAS) * 4)
 
+// Set-up of phase C: the resident conv0b / conv2 weights (packed A fragments: [conv0b 1024 f32x4][conv2 2048 f32x4]), the xyz layer and the biases
+// go to the first PC_LDS_BYTES of the dynamic LDS, all NTH threads copying; they are in place after the caller's next barrier.
+struct PhaseC {
+    const f32x4 *w_c0b, *w_c2, *bias4, *u4;      // u4 = W3^T wq: 128 values in the block layout of conv2's output
+    const float* xyz_l;
+};
+template <int NTH>
+__device__ __forceinline__ PhaseC phase_c_setup(const float* __restrict__ wpack, const f32x4* __restrict__ wdense, const float* __restrict__ bias) {
+    f32x4* w_l = (f32x4*)pps_smem;
+    float* xyz_l = (float*)(w_l + PC_WFLOATS / 4);
+    float* bias_l = xyz_l + PC_W_XYZ;
+    for (int i = threadIdx.x; i < PC_WFLOATS / 4; i += NTH) w_l[i] = wdense[i];
+    lds_fill(xyz_l, wpack, PC_W_XYZ);
+    lds_fill(bias_l, bias, PC_NBIAS);
+    const f32x4* bias4 = (const f32x4*)bias_l;
+    return PhaseC{w_l, w_l + 1024, bias4, bias4 + 144, xyz_l};
+}
+
 // One query of phase C once its matrix sits in registers as A fragments (th / tl: split precision, tf: fp32): conv0a ... conv2 over the
 // ceil(P/16) tiles of the patch, online softmax, pooled 128 channels to xbar.  Shared by pointnet_feat_rows_kernel (matrix read from memory) and
 // pointnet_fc3_feat_rows_kernel (matrix made in the same kernel), so both apply the same arithmetic in the same order.
 template <bool H>
 __device__ __forceinline__ void feat_rows_query(const float* __restrict__ patches, int64_t q, int P, int ntile_rows, const half8 (&th)[4][2],
-                                                const half8 (&tl)[4][2], const f32x4 (&tf)[4][4], const f32x4* bias4, const f32x4* u4,
-                                                const float* xyz_l, const f32x4* w_c0b, const f32x4* w_c2, float s0, float& amax, int lane,
+                                                const half8 (&tl)[4][2], const f32x4 (&tf)[4][4], const PhaseC& pc, float s0, float& amax, int lane,
                                                 float* __restrict__ xbar) {
     const int n = lane & 15, g = lane >> 4;
+    const f32x4 *bias4 = pc.bias4, *u4 = pc.u4, *w_c0b = pc.w_c0b, *w_c2 = pc.w_c2;
+    const float* xyz_l = pc.xyz_l;
     // per-lane (unreduced) online-softmax state over the patch points (nn.py:91-93)
     f32x4 acc[8];
     float mrun = -INFINITY, ssum = 0.f;
@@ -1190,19 +1152,10 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float*
                                                                     float* __restrict__ xbar, int* __restrict__ flag) {
     if (!H && gate_closed(flag)) return;
     float amax = 0.f;
-    f32x4* w_l = (f32x4*)pps_smem;                       // [conv0b 1024 f32x4][conv2 2048 f32x4], packed A fragments
-    float* xyz_l = (float*)(w_l + PC_WFLOATS / 4);
-    float* bias_l = xyz_l + PC_W_XYZ;
-    const f32x4* bias4 = (const f32x4*)bias_l;
-    const f32x4* u4 = bias4 + 144;                       // W3^T wq: 128 values in the block layout of conv2's output
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    for (int i = threadIdx.x; i < PC_WFLOATS / 4; i += PNT) w_l[i] = wdense[i];
-    lds_fill(xyz_l, wpack, PC_W_XYZ);
-    lds_fill(bias_l, bias, PC_NBIAS);
+    const PhaseC pc = phase_c_setup<PNT>(wpack, wdense, bias);
     __syncthreads();
-    const float s0 = bias_l[576 + 256];                   // wq . b3 + bq
-    const f32x4* w_c0b = w_l;
-    const f32x4* w_c2 = w_l + 1024;
+    const float s0 = ((const float*)pc.bias4)[576 + 256];     // wq . b3 + bq
     const int ntile_rows = (P + 15) / 16;
 
     const int ntiles = (int)((Q + PNW - 1) / PNW);
@@ -1227,7 +1180,7 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float*
 #pragma unroll
                 for (int kb = 0; kb < 4; ++kb) tf[ob][kb] = tq[(16 * ob + n) * 16 + 4 * kb + g];
         }
-        feat_rows_query<H>(patches, q, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
+        feat_rows_query<H>(patches, q, P, ntile_rows, th, tl, tf, pc, s0, amax, lane, xbar);
     }
     if (H) range_commit(amax, flag);
 }
@@ -1243,39 +1196,20 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float*
 __global__ __launch_bounds__(NT, 2) void pointnet_stn_head_h_kernel(const float* __restrict__ gin, int64_t Q, const f32x4* __restrict__ w16,
                                                                     const float* __restrict__ bias, half8* __restrict__ uh, int* __restrict__ range) {
     float amax = 0.f;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
     const f32x4* wg = w16;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     const f32x4* bias_g = (const f32x4*)bias;                  // biases of the two layers: [128][64] floats
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        const int64_t qi = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
-        const bool qv = qi < Q;
-        const int64_t qc = qv ? qi : Q - 1;
-        HiLo ah[8], h[4], u[2];
-        {
-            f32x4 a[16];
-            const f32x4* src = (const f32x4*)(gin + qc * 256) + g;
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb) a[bb] = src[4 * bb];
-#pragma unroll
-            for (int kb = 0; kb < 8; ++kb) ah[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt, [&](const f32x4* w) {
-                dense_blocks_f16x3<8, 2, 1>(ah, (const half8*)w, bias_g + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { h[c] = split_f16_r(amax, o0, o1); }); });
-        stream_step<CH4>(wg, cur, nxt, [&](const f32x4* w) {
-            dense_blocks_f16x3<4, 4, 1>(h, (const half8*)w, bias_g + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { u[i] = split_f16_r(amax, o0, o1); }); });
-        if (qv) {
-            half8* dst = uh + qc * 16 + g;
+        const TileRow q = tile_row(first + it * stride, wave, n, Q);
+        HiLo u[2];
+        stn_head_h(gin + q.c * 256, wg, wg, bias_g, cur, nxt, lane, amax, u);
+        if (q.valid) {
+            half8* dst = uh + q.c * 16 + g;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) { dst[(2 * kb) * 4] = u[kb].hi; dst[(2 * kb + 1) * 4] = u[kb].lo; }
         }
@@ -1304,19 +1238,10 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
                                                                           const f32x4* __restrict__ wdense, const float* __restrict__ bias,
                                                                           float* __restrict__ xbar, int* __restrict__ flag) {
     float amax = 0.f;
-    f32x4* w_l = (f32x4*)pps_smem;                       // [conv0b 1024 f32x4][conv2 2048 f32x4], packed A fragments
-    float* xyz_l = (float*)(w_l + PC_WFLOATS / 4);
-    float* bias_l = xyz_l + PC_W_XYZ;
-    half8* ex = (half8*)(bias_l + PC_NBIAS);
-    const f32x4* bias4 = (const f32x4*)bias_l;
-    const f32x4* u4 = bias4 + 144;                       // W3^T wq: 128 values in the block layout of conv2's output
+    half8* ex = (half8*)(pps_smem + PC_LDS_BYTES);       // the exchange buffers, behind phase C's resident arrays
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;
-    for (int i = threadIdx.x; i < PC_WFLOATS / 4; i += PF_NT) w_l[i] = wdense[i];
-    lds_fill(xyz_l, wpack, PC_W_XYZ);
-    lds_fill(bias_l, bias, PC_NBIAS);
+    const PhaseC pc = phase_c_setup<PF_NT>(wpack, wdense, bias);
     const float s0 = bias[576 + 256];                    // wq . b3 + bq
-    const f32x4* w_c0b = w_l;
-    const f32x4* w_c2 = w_l + 1024;
     const int ntile_rows = (P + 15) / 16;
     const f32x4* w3 = wfc + 5 * CH4;                     // fc3: chunks 5 .. 36 of the fc image
     const f32x4* b3 = (const f32x4*)(bias_fc + 192);
@@ -1363,7 +1288,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
                 }
             }
         }
-        if (q0 + wave < Q) feat_rows_query<true>(patches, q0 + wave, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
+        if (q0 + wave < Q) feat_rows_query<true>(patches, q0 + wave, P, ntile_rows, th, tl, tf, pc, s0, amax, lane, xbar);
         if (q0 + wave + 8 < Q) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
@@ -1375,7 +1300,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
                     tl[2 + ob][kb] = ex_r2[ob * PF_BUF + (2 * kb + 1) * 64];
                 }
             }
-            feat_rows_query<true>(patches, q0 + wave + 8, P, ntile_rows, th, tl, tf, bias4, u4, xyz_l, w_c0b, w_c2, s0, amax, lane, xbar);
+            feat_rows_query<true>(patches, q0 + wave + 8, P, ntile_rows, th, tl, tf, pc, s0, amax, lane, xbar);
         }
     }
     range_commit(amax, flag);
@@ -1395,30 +1320,24 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_kernel(const float* __restr
     // [1] counts such chunks (read by DecoderPlan.range_fallbacks())
     if (gate_closed(gate)) return;
     if (gate != nullptr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(gate + 1, 1);
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* bias_l = (float*)(buf1 + CH4);
+    float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
     const f32x4* wg = (const f32x4*)wpack;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias, TL_NBIAS);
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
 
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        const int64_t qi = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
-        const bool qv = qi < Q;
-        const int64_t qc = qv ? qi : Q - 1;
+        const TileRow q = tile_row(first + it * stride, wave, n, Q);
         f32x4 p[16], x[8], h[16];
         {
-            const f32x4* sp = (const f32x4*)(pooled + qc * 256) + g;
-            const f32x4* sx = (const f32x4*)(xbar + qc * 128) + g;
+            const f32x4* sp = (const f32x4*)(pooled + q.c * 256) + g;
+            const f32x4* sx = (const f32x4*)(xbar + q.c * 128) + g;
 #pragma unroll
             for (int bb = 0; bb < 16; ++bb) p[bb] = sp[4 * bb];
 #pragma unroll
@@ -1438,16 +1357,7 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_kernel(const float* __restr
                            [&](const f32x4* w) { dense_blocks<16, 2, 1>(h, &p[2 * c], w, bias4 + 64 + 8 * c, lane); });
         f32x4 o[2];
         stream_step<CH4>(wg, cur, nxt, [&](const f32x4* w) { dense_blocks<16, 2, 0>(p, o, w, bias4 + 128, lane); });
-        if (qv && g == 0) {
-            const float l0 = o[0].x, l1 = o[0].y;
-            logits[qi * 2] = l0;
-            logits[qi * 2 + 1] = l1;
-            if (occ) {
-                const float mx = fmaxf(l0, l1);
-                const float e0 = __expf(l0 - mx), e1 = __expf(l1 - mx);
-                occ[qi] = (e0 - e1) / (e0 + e1);
-            }
-        }
+        store_logits(o[0], q, g, logits, occ);
     }
 }
 
@@ -1459,30 +1369,24 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __res
                                                               const f32x4* __restrict__ w16, const float* __restrict__ bias,
                                                               float* __restrict__ logits, float* __restrict__ occ, int* __restrict__ range) {
     float amax = 0.f;
-    f32x4* buf0 = (f32x4*)pps_smem;
-    f32x4* buf1 = buf0 + CH4;
-    float* bias_l = (float*)(buf1 + CH4);
+    float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
     const f32x4* wg = w16;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias, TL_NBIAS);
-    stream_prologue<CH4>(wg, buf0);
-    stream_wait();
-    __syncthreads();
-    f32x4 *cur = buf0, *nxt = buf1;
+    f32x4 *cur, *nxt;
+    stream_begin<CH4>(wg, cur, nxt);
 
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     for (int it = 0; it < count; ++it) {
-        const int64_t qi = (int64_t)(first + it * stride) * (NW * 16) + wave * 16 + n;
-        const bool qv = qi < Q;
-        const int64_t qc = qv ? qi : Q - 1;
+        const TileRow q = tile_row(first + it * stride, wave, n, Q);
         HiLo p[8], x[4];
         {
-            const f32x4* sp = (const f32x4*)(pooled + qc * 256) + g;
-            const f32x4* sx = (const f32x4*)(xbar + qc * 128) + g;
+            const f32x4* sp = (const f32x4*)(pooled + q.c * 256) + g;
+            const f32x4* sx = (const f32x4*)(xbar + q.c * 128) + g;
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) p[kb] = split_f16_r(amax, sp[4 * (2 * kb)], sp[4 * (2 * kb + 1)]);
 #pragma unroll
@@ -1505,16 +1409,7 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __res
         f32x4 o[2];
         stream_step<CH4>(wg, cur, nxt, [&](const f32x4* w) {
             dense_blocks_f16x3<8, 2, 0>(p, (const half8*)w, bias4 + 128, lane, [&](int, const f32x4& o0, const f32x4& o1) { o[0] = o0; o[1] = o1; }); });
-        if (qv && g == 0) {
-            const float l0 = o[0].x, l1 = o[0].y;
-            logits[qi * 2] = l0;
-            logits[qi * 2 + 1] = l1;
-            if (occ) {
-                const float mx = fmaxf(l0, l1);
-                const float e0 = __expf(l0 - mx), e1 = __expf(l1 - mx);
-                occ[qi] = (e0 - e1) / (e0 + e1);
-            }
-        }
+        store_logits(o[0], q, g, logits, occ);
     }
     range_commit(amax, range);
 }
@@ -1533,16 +1428,25 @@ static int cu_count() {
     return g_cu_count;
 }
 
-template <class K>
-static int set_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 0 : 1;
+// workgroups on the chip at `per_cu` per CU (256 CUs where the device cannot be asked)
+static int chip_wgs(int per_cu) {
+    const int cus = cu_count();
+    return (cus > 0 ? cus : 256) * per_cu;
 }
 
-static int grid_for(int64_t ntiles) {
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    cus *= WG_PER_CU;
-    return (int)(ntiles < cus ? (ntiles > 0 ? ntiles : 1) : cus);
+// persistent grid: one workgroup per tile up to `wgs`, at least one
+static int grid_for(int64_t ntiles, int wgs = chip_wgs(WG_PER_CU)) {
+    return (int)(ntiles < wgs ? (ntiles > 0 ? ntiles : 1) : wgs);
+}
+
+// One launch of Kernel: the first call raises the kernel's limit of dynamic LDS to `lds` bytes (a fixed number per kernel; 0 = none used), then
+// the launch and its error check.
+template <auto Kernel, class... Args>
+static int launch(int grid, int threads, int lds, void* stream, Args... args) {
+    static const bool once = lds > 0 && hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+    (void)once;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, (hipStream_t)stream, args...);
+    return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 
 // PointNet row kernels: PN_WG_PER_CU workgroups of PNW waves per CU.  Packed wave groups (qg queries, no padded rows) are used for as many
@@ -1551,56 +1455,42 @@ static int grid_for(int64_t ntiles) {
 // per wave instead of 100).
 struct PnSplit { int64_t q_packed; int grid_packed, grid_rest, rest_mode; };
 static PnSplit pn_split(int64_t q, int p) {
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
     const PatchPacking pk = patch_packing(p);
     PnSplit sp;
-    const int wgs = cus * PN_WG_PER_CU;
+    const int wgs = chip_wgs(PN_WG_PER_CU);
     const int64_t per_round = (int64_t)wgs * PNW * pk.qg;
     sp.q_packed = pk.packed ? (q / per_round) * per_round : 0;
     if (pk.packed && getenv("PPS_PN_FORCE_PACK")) sp.q_packed = q;      // test hook: packed path for any query count
     sp.grid_packed = wgs;
     sp.rest_mode = pk.packed ? 2 : 0;                // the remainder in the packed arithmetic, one query per wave group: same bits as a packed round
-    const int64_t rest_tiles = (q - sp.q_packed + PNW - 1) / PNW;
-    sp.grid_rest = (int)(rest_tiles < wgs ? rest_tiles : wgs);
+    sp.grid_rest = grid_for((q - sp.q_packed + PNW - 1) / PNW, wgs);
     return sp;
 }
-
-#define PPS_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH)
 
 template <bool H>
 static int launch_stn_rows(const float* patches, int64_t q, int p, const float* wpack, const void* wdense, const float* bias, float* g,
                            int* flag, void* stream) {
-    static int once = set_lds(pointnet_stn_rows_kernel<H>, PA_LDS_BYTES);
-    (void)once;
     const PnSplit sp = pn_split(q, p);
     // split precision: the full tiles of a query in one pass where there are at most three; PPS_STN_TILES=2 (read per call: a test switches it) keeps
     // the two-at-a-time schedule, same bits
     const char* tiles_env = getenv("PPS_STN_TILES");
     const int tmax = (tiles_env && atoi(tiles_env) == 2) ? 2 : 3;
+    int rc = PPS_OK;
     if (sp.q_packed > 0)
-        hipLaunchKernelGGL(pointnet_stn_rows_kernel<H>, dim3(sp.grid_packed), dim3(PNT), PA_LDS_BYTES, (hipStream_t)stream, patches,
-                           sp.q_packed, p, 1, tmax, wpack, (const f32x4*)wdense, bias, g, flag);
-    if (q > sp.q_packed)
-        hipLaunchKernelGGL(pointnet_stn_rows_kernel<H>, dim3(sp.grid_rest), dim3(PNT), PA_LDS_BYTES, (hipStream_t)stream,
-                           patches + sp.q_packed * p * 3, q - sp.q_packed, p, sp.rest_mode, tmax, wpack, (const f32x4*)wdense, bias,
-                           g + sp.q_packed * 256, flag);
-    return PPS_LAUNCH_CHECK();
+        rc = launch<pointnet_stn_rows_kernel<H>>(sp.grid_packed, PNT, PA_LDS_BYTES, stream, patches, sp.q_packed, p, 1, tmax, wpack,
+                                                 (const f32x4*)wdense, bias, g, flag);
+    if (rc == PPS_OK && q > sp.q_packed)
+        rc = launch<pointnet_stn_rows_kernel<H>>(sp.grid_rest, PNT, PA_LDS_BYTES, stream, patches + sp.q_packed * p * 3, q - sp.q_packed, p,
+                                                 sp.rest_mode, tmax, wpack, (const f32x4*)wdense, bias, g + sp.q_packed * 256, flag);
+    return rc;
 }
 
 template <bool H>
 static int launch_feat_rows(const float* patches, const float* trans2, int64_t q, int p, const float* wpack, const void* wdense,
                             const float* bias, float* xbar, int* flag, void* stream) {
-    static int once = set_lds(pointnet_feat_rows_kernel<H>, PC_LDS_BYTES);
-    (void)once;
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    const int64_t ntiles = (q + PNW - 1) / PNW, wgs = (int64_t)cus * PN_WG_PER_CU;
-    hipLaunchKernelGGL(pointnet_feat_rows_kernel<H>, dim3((unsigned)(ntiles < wgs ? ntiles : wgs)), dim3(PNT), PC_LDS_BYTES, (hipStream_t)stream, patches,
-                       trans2, q, p, wpack, (const f32x4*)wdense, bias, xbar, flag);
-    return PPS_LAUNCH_CHECK();
+    return launch<pointnet_feat_rows_kernel<H>>(grid_for((q + PNW - 1) / PNW, chip_wgs(PN_WG_PER_CU)), PNT, PC_LDS_BYTES, stream, patches, trans2, q,
+                                                p, wpack, (const f32x4*)wdense, bias, xbar, flag);
 }
-
 
 // ---- launchers with the range-guard plumbing (the extern "C" entry points below are thin wrappers) ----------------------------------------------
 // gate (fp32 kernels): null = run; otherwise the launch returns at once unless gate[0] != 0.  range (split-precision kernels): where a kernel reports
@@ -1610,22 +1500,15 @@ static int interp_pool_f32_impl(const float* G, const float* pts, const float* q
     if (q < 0 || k < 1 || k > 64) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!G || !pts || !query || !idx || !wpack || !bias || !pooled) return PPS_ERR_ARG;
-    static int once = set_lds(interp_pool_kernel, IP_LDS_BYTES);
-    (void)once;
-    hipLaunchKernelGGL(interp_pool_kernel, dim3(grid_for((q + NW / 4 - 1) / (NW / 4))), dim3(NT), IP_LDS_BYTES, (hipStream_t)stream,
-                       G, pts, query, idx, q, k, wpack, bias, pooled, gate);
-    return PPS_LAUNCH_CHECK();
+    return launch<interp_pool_kernel>(grid_for((q + NW / 4 - 1) / (NW / 4)), NT, IP_LDS_BYTES, stream, G, pts, query, idx, q, k, wpack, bias, pooled,
+                                      gate);
 }
 
 static int stn_fc_f32_impl(const float* g, int64_t q, const float* wpack, const float* bias, float* trans2, const int* gate, void* stream) {
     if (q < 0) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!g || !wpack || !bias || !trans2) return PPS_ERR_ARG;
-    static int once = set_lds(pointnet_stn_fc_kernel, PB_LDS_BYTES);
-    (void)once;
-    hipLaunchKernelGGL(pointnet_stn_fc_kernel, dim3(grid_for((q + NW * 16 * PB_T - 1) / (NW * 16 * PB_T))), dim3(NT), PB_LDS_BYTES, (hipStream_t)stream,
-                       g, q, wpack, bias, trans2, gate);
-    return PPS_LAUNCH_CHECK();
+    return launch<pointnet_stn_fc_kernel>(grid_for((q + NW * 16 - 1) / (NW * 16)), NT, PB_LDS_BYTES, stream, g, q, wpack, bias, trans2, gate);
 }
 
 static int decode_tail_f32_impl(const float* pooled, const float* xbar, int64_t q, const float* wpack, const float* bias,
@@ -1633,27 +1516,14 @@ static int decode_tail_f32_impl(const float* pooled, const float* xbar, int64_t 
     if (q < 0) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!pooled || !xbar || !wpack || !bias || !logits) return PPS_ERR_ARG;
-    static int once = set_lds(decode_tail_kernel, TL_LDS_BYTES);
-    (void)once;
-    hipLaunchKernelGGL(decode_tail_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), TL_LDS_BYTES, (hipStream_t)stream,
-                       pooled, xbar, q, wpack, bias, logits, occ, gate);
-    return PPS_LAUNCH_CHECK();
+    return launch<decode_tail_kernel>(grid_for((q + NW * 16 - 1) / (NW * 16)), NT, TL_LDS_BYTES, stream, pooled, xbar, q, wpack, bias, logits, occ,
+                                      gate);
 }
 
 extern "C" {
 
 int pps_abi_version(void) { return 2; }
 
-// development aid (not part of the public header): resident workgroups per CU of the decoder kernels
-int pps_debug_occupancy(int which) {
-    int n = -1;
-    if (which == 0) { set_lds(interp_pool_kernel, IP_LDS_BYTES); hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, interp_pool_kernel, NT, IP_LDS_BYTES); }
-    if (which == 1) { set_lds(pointnet_stn_rows_kernel<false>, PA_LDS_BYTES); hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pointnet_stn_rows_kernel<false>, PNT, PA_LDS_BYTES); }
-    if (which == 3) { set_lds(pointnet_stn_fc_kernel, PB_LDS_BYTES); hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pointnet_stn_fc_kernel, NT, PB_LDS_BYTES); }
-    if (which == 4) { set_lds(pointnet_stn_fc_h_kernel, PB_LDS_BYTES); hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pointnet_stn_fc_h_kernel, NT, PB_LDS_BYTES); }
-    if (which == 2) { set_lds(pointnet_feat_rows_kernel<false>, PC_LDS_BYTES); hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pointnet_feat_rows_kernel<false>, PNT, PC_LDS_BYTES); }
-    return n;
-}
 int pps_device_cu_count(void) { return cu_count(); }
 
 int pps_rows_dense256_f32(const float* in, int64_t rs, int64_t cs, int64_t m, const float* wpack, const float* bias,
@@ -1662,11 +1532,7 @@ int pps_rows_dense256_f32(const float* in, int64_t rs, int64_t cs, int64_t m, co
     if (m == 0) return PPS_OK;
     if (!in || !wpack || !bias || !out) return PPS_ERR_ARG;
     if (cs == 1 && (rs % 4) != 0) return PPS_ERR_ARG;
-    static int once = set_lds(rows_dense256_kernel, RD_LDS_BYTES);
-    (void)once;
-    hipLaunchKernelGGL(rows_dense256_kernel, dim3(grid_for((m + NW * 16 - 1) / (NW * 16))), dim3(NT), RD_LDS_BYTES, (hipStream_t)stream,
-                       in, rs, cs, m, wpack, bias, out);
-    return PPS_LAUNCH_CHECK();
+    return launch<rows_dense256_kernel>(grid_for((m + NW * 16 - 1) / (NW * 16)), NT, RD_LDS_BYTES, stream, in, rs, cs, m, wpack, bias, out);
 }
 
 int pps_interp_pool_f32(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k,
@@ -1679,16 +1545,9 @@ int pps_interp_pool_f16x3(const float* G, const float* pts, const float* query, 
     if (q < 0 || k < 1 || k > 64) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!G || !pts || !query || !idx || !wxyz || !w16 || !bias || !pooled) return PPS_ERR_ARG;
-    static int once = set_lds(interp_pool_f16x3_kernel, IH_LDS_BYTES);
-    (void)once;
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    const int64_t ntiles = (q + IH_NW / 4 - 1) / (IH_NW / 4);
-    const int64_t wgs = (int64_t)cus * IH_WG_PER_CU;                  // one 8-wave workgroup per CU (IH_NT = 512)
-    const int grid = (int)(ntiles < wgs ? ntiles : wgs);
-    hipLaunchKernelGGL(interp_pool_f16x3_kernel, dim3(grid), dim3(IH_NT), IH_LDS_BYTES, (hipStream_t)stream,
-                       G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled, (int*)range_flag);
-    return PPS_LAUNCH_CHECK();
+    const int grid = grid_for((q + IH_NW / 4 - 1) / (IH_NW / 4), chip_wgs(IH_WG_PER_CU));      // one 8-wave workgroup per CU (IH_NT = 512)
+    return launch<interp_pool_f16x3_kernel>(grid, IH_NT, IH_LDS_BYTES, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled,
+                                            (int*)range_flag);
 }
 
 int pps_interp_small_f32(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k, int c,
@@ -1696,13 +1555,9 @@ int pps_interp_small_f32(const float* G, const float* pts, const float* query, c
     if (q < 0 || k < 1 || k > 64 || (c != 32 && c != 64) || nout < 1 || nout > IS_MAX_OUT) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!G || !pts || !query || !idx || !wpack || !bias || !wtail || !out) return PPS_ERR_ARG;
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    const int grid = (int)(q < (int64_t)cus * 8 ? q : (int64_t)cus * 8);
-    hipStream_t st = (hipStream_t)stream;
-    if (c == 32) hipLaunchKernelGGL((interp_small_kernel<2, false>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, nullptr);
-    else hipLaunchKernelGGL((interp_small_kernel<4, false>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, nullptr);
-    return PPS_LAUNCH_CHECK();
+    const int grid = grid_for(q, chip_wgs(8));
+    if (c == 32) return launch<interp_small_kernel<2, false>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, nullptr);
+    return launch<interp_small_kernel<4, false>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, nullptr);
 }
 
 int pps_interp_small_f16x3(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k, int c,
@@ -1711,21 +1566,19 @@ int pps_interp_small_f16x3(const float* G, const float* pts, const float* query,
     if (q < 0 || k < 1 || k > 64 || (c != 32 && c != 64) || nout < 1 || nout > IS_MAX_OUT) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!G || !pts || !query || !idx || !wpack || !w16 || !bias || !wtail || !out || !guard) return PPS_ERR_ARG;
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    const int grid = (int)(q < (int64_t)cus * 8 ? q : (int64_t)cus * 8);
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(guard, 0, sizeof(int), st) != hipSuccess) return PPS_ERR_LAUNCH;
+    const int grid = grid_for(q, chip_wgs(8));
+    if (hipMemsetAsync(guard, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return PPS_ERR_LAUNCH;
     const float* wh = (const float*)w16;
     // split precision first; the fp32 kernel behind it runs only if an activation left the f16 range (no host round trip)
+    int rc;
     if (c == 32) {
-        hipLaunchKernelGGL((interp_small_kernel<2, true>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, wh, bias, wtail, nout, out, guard);
-        hipLaunchKernelGGL((interp_small_kernel<2, false>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, guard);
+        rc = launch<interp_small_kernel<2, true>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, wh, bias, wtail, nout, out, guard);
+        if (rc == PPS_OK) rc = launch<interp_small_kernel<2, false>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, guard);
     } else {
-        hipLaunchKernelGGL((interp_small_kernel<4, true>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, wh, bias, wtail, nout, out, guard);
-        hipLaunchKernelGGL((interp_small_kernel<4, false>), dim3(grid), dim3(IS_NT), 0, st, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, guard);
+        rc = launch<interp_small_kernel<4, true>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, wh, bias, wtail, nout, out, guard);
+        if (rc == PPS_OK) rc = launch<interp_small_kernel<4, false>>(grid, IS_NT, 0, stream, G, pts, query, idx, q, k, wpack, nullptr, bias, wtail, nout, out, guard);
     }
-    return PPS_LAUNCH_CHECK();
+    return rc;
 }
 
 int pps_pointnet_stn_rows_f32(const float* patches, int64_t q, int p, const float* wpack, const float* bias, float* g,
@@ -1756,59 +1609,25 @@ int pps_pointnet_f16x3(const float* patches, int64_t q, int p, const float* cons
     if (q < 0 || p < 1) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!patches || !weights || !w16 || !w16[0] || !w16[1] || !w16[2] || !g || !trans2 || !xbar) return PPS_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     int* range = (int*)range_flag;
+    auto mark = [&](int i) { if (events && events[i]) hipEventRecord((hipEvent_t)events[i], (hipStream_t)stream); };
     int rc = launch_stn_rows<true>(patches, q, p, weights[0], w16[0], weights[1], g, range, stream);
-    if (events && events[0]) hipEventRecord((hipEvent_t)events[0], st);
+    mark(0);
     if (rc != PPS_OK) return rc;
-    static int once = set_lds(pointnet_stn_fc_h_kernel, PB_LDS_BYTES);
-    (void)once;
-    // Experiment hook of the two-kernel path, where the per-query matrix M (16 KiB per query) crosses memory between stn_fc_h and feat_rows.
-    // `sub` > 0: that pair runs sub-chunk by sub-chunk (M of a sub-chunk = sub x 16 KiB, written and read back to back; with `reuse` every
-    // sub-chunk uses the SAME scratch addresses) --
-    // the measured answer to "does a cache-resident M help" (tools/time_pn_subchunks.py).  Results are bit-identical:
-    // both kernels treat queries independently.
-    static const int64_t sub = getenv("PPS_PN_SUB") ? atoll(getenv("PPS_PN_SUB")) : 0;
-    static const bool reuse = getenv("PPS_PN_SUB_REUSE") != nullptr;
-    if (sub > 0 && sub < q) {
-        for (int64_t off = 0; off < q && rc == PPS_OK; off += sub) {
-            const int64_t n = q - off < sub ? q - off : sub;
-            float* t2 = reuse ? trans2 : trans2 + off * 4096;
-            hipLaunchKernelGGL(pointnet_stn_fc_h_kernel, dim3(grid_for((n + NW * 16 - 1) / (NW * 16))), dim3(NT), PB_LDS_BYTES, st, g + off * 256, n,
-                               (const f32x4*)w16[1], weights[3], (half8*)t2, range);
-            rc = launch_feat_rows<true>(patches + off * p * 3, t2, n, p, weights[4], w16[2], weights[5], xbar + off * 128, range, stream);
-        }
-        if (events && events[1]) hipEventRecord((hipEvent_t)events[1], st);
-        if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
-        return rc;
-    }
+    const int head_grid = grid_for((q + NW * 16 - 1) / (NW * 16));
     // Default: M never leaves the CU.  The head writes u (256 B per query, already split) into the start of the trans2 slot, and one kernel runs
     // fc3 and phase C (pointnet_fc3_feat_rows_kernel).  PPS_PN_FUSED=0 (read per call: a test switches it) keeps the two kernels with M in trans2.
     const char* fused_env = getenv("PPS_PN_FUSED");
-    if (fused_env && fused_env[0] == '0' && fused_env[1] == 0) {
-        hipLaunchKernelGGL(pointnet_stn_fc_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), PB_LDS_BYTES, st, g, q,
-                           (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
-        if (events && events[1]) hipEventRecord((hipEvent_t)events[1], st);
-        if (hipGetLastError() != hipSuccess) return PPS_ERR_LAUNCH;
-        rc = launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
-        if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
-        return rc;
-    }
-    static int once_head = set_lds(pointnet_stn_head_h_kernel, PH_LDS_BYTES);
-    static int once_fused = set_lds(pointnet_fc3_feat_rows_kernel, PF_LDS_BYTES);
-    (void)once_head;
-    (void)once_fused;
-    hipLaunchKernelGGL(pointnet_stn_head_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), PH_LDS_BYTES, st, g, q,
-                       (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
-    if (events && events[1]) hipEventRecord((hipEvent_t)events[1], st);
-    if (hipGetLastError() != hipSuccess) return PPS_ERR_LAUNCH;
-    int cus = cu_count();
-    if (cus <= 0) cus = 256;
-    const int64_t passes = (q + 15) / 16;
-    hipLaunchKernelGGL(pointnet_fc3_feat_rows_kernel, dim3((unsigned)(passes < cus ? passes : cus)), dim3(PF_NT), PF_LDS_BYTES, st, patches,
-                       (const half8*)trans2, q, p, (const f32x4*)w16[1], weights[3], weights[4], (const f32x4*)w16[2], weights[5], xbar, range);
-    if (events && events[2]) hipEventRecord((hipEvent_t)events[2], st);
-    return PPS_LAUNCH_CHECK();
+    const bool fused = !(fused_env && fused_env[0] == '0' && fused_env[1] == 0);
+    rc = fused ? launch<pointnet_stn_head_h_kernel>(head_grid, NT, PH_LDS_BYTES, stream, g, q, (const f32x4*)w16[1], weights[3], (half8*)trans2, range)
+               : launch<pointnet_stn_fc_h_kernel>(head_grid, NT, PB_LDS_BYTES, stream, g, q, (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
+    mark(1);
+    if (rc != PPS_OK) return rc;
+    rc = fused ? launch<pointnet_fc3_feat_rows_kernel>(grid_for((q + 15) / 16, chip_wgs(1)), PF_NT, PF_LDS_BYTES, stream, patches, (const half8*)trans2,
+                                                       q, p, (const f32x4*)w16[1], weights[3], weights[4], (const f32x4*)w16[2], weights[5], xbar, range)
+               : launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
+    mark(2);
+    return rc;
 }
 
 int pps_decode_tail_f32(const float* pooled, const float* xbar, int64_t q, const float* wpack, const float* bias,
@@ -1821,11 +1640,8 @@ int pps_decode_tail_f16x3(const float* pooled, const float* xbar, int64_t q, con
     if (q < 0) return PPS_ERR_ARG;
     if (q == 0) return PPS_OK;
     if (!pooled || !xbar || !w16 || !bias || !logits) return PPS_ERR_ARG;
-    static int once = set_lds(decode_tail_h_kernel, TL_LDS_BYTES);
-    (void)once;
-    hipLaunchKernelGGL(decode_tail_h_kernel, dim3(grid_for((q + NW * 16 - 1) / (NW * 16))), dim3(NT), TL_LDS_BYTES, (hipStream_t)stream,
-                       pooled, xbar, q, (const f32x4*)w16, bias, logits, occ, (int*)range_flag);
-    return PPS_LAUNCH_CHECK();
+    return launch<decode_tail_h_kernel>(grid_for((q + NW * 16 - 1) / (NW * 16)), NT, TL_LDS_BYTES, stream, pooled, xbar, q, (const f32x4*)w16, bias,
+                                        logits, occ, (int*)range_flag);
 }
 
 /* The whole decoder of one query chunk in one call: the five launches above on `stream`, intermediates in caller scratch (the first 64 bytes of it

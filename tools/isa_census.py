@@ -85,7 +85,7 @@ def phases_interp_f16x3(decode, common):
         (common, c('f32x4 o0 = m0 + c0, o1 = m1 + c1;'), c('f32x4 o0 = m0 + c0, o1 = m1 + c1;'), 'accumulator join (main + correction)'),
         (common, c('for (int r = 0; r < 4; ++r) { o0[r] = fmaxf(o0[r], 0.f); o1[r] = fmaxf(o1[r], 0.f); }'),
          c('for (int r = 0; r < 4; ++r) { o0[r] = fmaxf(o0[r], 0.f); o1[r] = fmaxf(o1[r], 0.f); }'), 'ReLU of the layer output'),
-        (common, c('template <int KB, int NOB, int ACT, bool FENCE = true, bool INIT = false, int NP = 3, class Sink, class Hook>'),
+        (common, c('template <int KB, int NOB, int ACT, bool FENCE = true, bool INIT = false, class Sink, class Hook>'),
          c('sink(ob >> 1, o0, o1);'), 'dense layer loop (MFMA, fragment reads, bias)'),
         (common, c('__device__ __forceinline__ void xyz_blocks('), c('// ---- cooperative weight-chunk streaming') - 1, 'xyz layer (K = 3 MFMA)'),
         (common, c('// ---- cooperative weight-chunk streaming'), c('// XCD-aware persistent tile order') - 1, 'weight stream (global_load_lds, waits)'),

@@ -194,6 +194,53 @@ int ppsx_denoise_filter_pass(const int64_t* faces, int64_t nf, int64_t nv, const
 int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, int64_t nf, const double* normals, const int64_t* offsets,
                              const int32_t* inc, int64_t ni, double* out, void* stream);
 
+/* ---- isolated pieces: face components, a table per component, the rules that drop components (csrc/pps_pieces.hip) -----------------------
+ * new capability: replaces nothing -- the reference's rule, remove_small_connected_components(num_faces = 6), stays with
+ * pps_mesh_small_components.  Driven by ppsurf_amd/pieces.py (the keys by ppsurf_amd/topology.py); the rule and the argument for the
+ * labelling are written out at the top of csrc/pps_pieces.hip and in DESIGN.md section 21.  A face is valid when its three indices lie in
+ * [0, nv) and are pairwise distinct; two valid faces are adjacent when they share an undirected edge that exactly two valid faces hold; a
+ * component's leader is its smallest face index.
+ *   ppsx_pieces_edge_keys  keys int64 [3 nf]: per valid face (a, b, c) of faces int64 [nf,3] the keys of the undirected edges ab, bc, ca in
+ *                          that order, (min << 32) | max; INT64_MAX three times for an invalid face, so those sort last.  Sorted, a run of
+ *                          exactly two equal keys is an edge that joins its two owners (position / 3).
+ *                          nf < 0, nv < 0, nf or nv > 2^31 - 1, or a NULL pointer with nf > 0: PPS_ERR_ARG, nothing is launched or
+ *                          written.  nf == 0: 0, nothing is launched.
+ *   ppsx_pieces_hook       one hooking round over the pairs fa, fb int32 [np] on label int32 [nf] (label[f] = f to begin with, -1 for an
+ *                          invalid face): a pair (a, b) walks label from a and from b -- a walk steps from x to label[x] while
+ *                          0 <= label[x] < x -- to the ends ra, rb, and when ra != rb does atomicMin(&label[max], min) and stores 1 to
+ *                          *changed (int32, device; the caller zeroes it before).  A pair with an entry outside [0, nf) or onto a face
+ *                          with a negative label is skipped.  No read relies on a write of the same launch; see the .hip file.
+ *                          np < 0, nf < 0, np or nf > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is
+ *                          launched or written.  np == 0 or nf == 0: 0, nothing is launched.
+ *   ppsx_pieces_compress   every face f with label[f] >= 0 stores the end of its walk in label[f]; a face with a negative label is not
+ *                          touched.  A walk reads no slot outside [0, f] and takes at most f steps.
+ *                          nf < 0, nf > 2^31 - 1 or a NULL label with nf > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0,
+ *                          nothing is launched.
+ *   ppsx_pieces_stats      count int64 [nc], lo, hi f32 [nc,3]: per component c the number of its faces and the box of their corners over
+ *                          verts f32 [nv,3], every coordinate taken as x + 0.0f.  Face f belongs to cid[f] (int32 [nf]); a face with
+ *                          label[f] < 0, an invalid face and a face with cid[f] outside [0, nc) are skipped and not read through.  A
+ *                          component without a face gets 0, +inf and -inf.  Integer atomics after a combine per wave and per workgroup:
+ *                          exact in any order.  Every row of the outputs is written.
+ *                          nv, nf or nc < 0 or > 2^31 - 1, or -- with nc > 0 -- a NULL count, lo or hi, lo == hi, with nf > 0 a NULL
+ *                          faces, label or cid, with nf > 0 and nv > 0 a NULL verts: PPS_ERR_ARG, nothing is launched or written.
+ *                          nc == 0: 0, nothing is launched.
+ *   ppsx_pieces_select     keep u8 [nc]: 1 when component c passes every rule whose flag is 1.  min_faces: count[c] >= min_faces.
+ *                          min_diag_frac: diag2 >= (min_diag_frac * min_diag_frac) * box_diag2 in fp64, diag2 = (dx dx + dy dy) + dz dz,
+ *                          dx = double(hi.x) - double(lo.x) and so on, every operation rounded on its own.  keep_largest:
+ *                          0 <= rank[c] < keep_largest (rank int64 [nc]: by faces descending, then leader ascending).
+ *                          nc < 0 or > 2^31 - 1, a flag that is not 0 or 1, no flag set, with its flag set a min_faces or keep_largest
+ *                          outside 1..2^31 - 1 or a min_diag_frac that is NaN or outside [0, 1], a box_diag2 that is negative or not
+ *                          finite, or -- with nc > 0 -- a NULL keep or a NULL table that a set rule reads: PPS_ERR_ARG, nothing is
+ *                          launched or written.  nc == 0: 0, nothing is launched. */
+int ppsx_pieces_edge_keys(const int64_t* faces, int64_t nf, int64_t nv, int64_t* keys, void* stream);
+int ppsx_pieces_hook(const int32_t* fa, const int32_t* fb, int64_t np, int32_t* label, int64_t nf, int32_t* changed, void* stream);
+int ppsx_pieces_compress(int32_t* label, int64_t nf, void* stream);
+int ppsx_pieces_stats(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int32_t* label, const int32_t* cid, int64_t nc,
+                      int64_t* count, float* lo, float* hi, void* stream);
+int ppsx_pieces_select(const int64_t* count, const float* lo, const float* hi, const int64_t* rank, int64_t nc, int has_min_faces,
+                       int64_t min_faces, int has_min_diag_frac, double min_diag_frac, int has_keep_largest, int64_t keep_largest,
+                       double box_diag2, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

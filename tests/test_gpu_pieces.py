@@ -1,0 +1,362 @@
+"""GPU tier of the removal of isolated pieces: the kernels of csrc/pps_pieces.hip and ppsurf_amd/pieces.py against the
+numpy specification tests/pieces_spec.py, byte for byte and twice; the components against the shipped bounded walk
+(ops.mesh_small_components); each kernel alone on hand-made tables; the argument rules of the C entries; `python -m ppsurf_amd.pieces` end
+to end."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import pieces_spec as S
+import smooth_spec
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda:0'
+I32, I64, F32 = torch.int32, torch.int64, torch.float32
+OTHER_RULES = ((1, None, None), (2, None, None), (34, None, None), (None, 0.5, None), (None, None, 1), (3, 0.25, 4))
+_cache = {}
+
+
+def dev(a):
+    return torch.from_numpy(np.array(a)).to(DEV)                      # (a copy: from_numpy wants a writable array)
+
+
+def mesh(name):
+    """(verts f32, faces int64, the rules to try) of a named fixture."""
+    kind, _, arg = name.partition(':')
+    if kind == 'scene':
+        return S.scene(arg or 'built') + (tuple(r for r, _ in S.SCENE_GRID),)
+    if kind == 'cube8':
+        return S.cube8(int(arg)) + (OTHER_RULES,)
+    if kind == 'strip':
+        n, _, order = arg.partition(',')
+        return S.strip(int(n), order or 'ascending') + (((None, None, 1), (1000, 1.0, None)),)
+    if kind == 'debris':
+        return S.debris() + (OTHER_RULES,)
+    if kind == 'sphere':                                              # one component over two workgroups of the statistics
+        return smooth_spec.noisy_sphere() + (((None, 1.0, 1),),)
+    return S.small(name)[:2] + (OTHER_RULES,)
+
+
+def spec_table(name):
+    """The specification's table of a fixture, computed once."""
+    if name not in _cache:
+        verts, faces, _ = mesh(name)
+        _cache[name] = S.table_spec(verts, faces)
+    return _cache[name]
+
+
+def same_table(got, want):
+    assert got['label'].dtype == I32 and got['leader'].dtype == I64 and got['faces'].dtype == I64 and got['diag2'].dtype == torch.float64
+    assert got['lo'].dtype == F32 and got['hi'].dtype == F32 and isinstance(got['box_diag2'], float)
+    assert sorted(got) == ['box_diag2', 'diag2', 'faces', 'hi', 'label', 'leader', 'lo']
+    for key in ('label', 'leader', 'faces', 'lo', 'hi', 'diag2'):
+        g = got[key].cpu().numpy()
+        assert g.shape == want[key].shape and g.tobytes() == want[key].tobytes(), '{}: {} against {}'.format(key, g[:8], want[key][:8])
+    assert got['box_diag2'] == want['box_diag2']
+
+
+NAMES = ['scene', 'scene:robin', 'scene:permuted', 'scene:invalid', 'cube8:255', 'cube8:257', 'cube8:766', 'strip:1000', 'strip:1000,reversed',
+         'strip:1000,permuted', 'strip:20000', 'strip:20000,reversed', 'strip:20000,permuted', 'debris', 'sphere'] + list(S.SMALL)
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_labels_table_and_removal_match_the_spec_bytewise(name):
+    from ppsurf_amd import pieces
+    verts, faces, grid = mesh(name)
+    want = spec_table(name)
+    v, f = dev(verts), dev(faces)
+    for _ in range(2):
+        label = pieces.face_components(f, verts.shape[0])
+        assert label.dtype == I32 and label.cpu().numpy().tobytes() == want['label'].tobytes()
+        same_table(pieces.component_table(v, f), want)
+    for rules in grid:
+        want_v, want_f, want_info, _ = S.remove_spec(verts, faces, *rules)
+        for _ in range(2):
+            out_v, out_f, info = pieces.remove_pieces(v, f, *rules)
+            assert out_v.dtype == F32 and out_f.dtype == I64 and info == want_info, (rules, info, want_info)
+            assert out_v.cpu().numpy().tobytes() == want_v.tobytes() and out_f.cpu().numpy().tobytes() == want_f.tobytes(), rules
+        assert json.loads(json.dumps(info)) == info
+
+
+def test_the_scene_keeps_the_leaders_written_out_by_hand():
+    from ppsurf_amd import pieces
+    verts, faces = S.scene()
+    v, f = dev(verts), dev(faces)
+    table = pieces.component_table(v, f)
+    assert dict(zip(table['leader'].tolist(), table['faces'].tolist())) == S.SCENE_FACES and table['box_diag2'] == 768.0
+    assert dict(zip(table['leader'].tolist(), table['diag2'].tolist())) == S.SCENE_DIAG2
+    label = table['label'].cpu().numpy()
+    for rules, leaders in S.SCENE_GRID:
+        out_v, out_f, info = pieces.remove_pieces(v, f, *rules)
+        assert info['components_kept'] == len(leaders) and info['faces_out'] == sum(S.SCENE_FACES[l] for l in leaders), rules
+        assert out_v.cpu().numpy()[out_f.cpu().numpy()].tobytes() == verts[faces[np.isin(label, leaders)]].tobytes(), rules
+
+
+def test_empty_and_all_invalid_meshes_come_back_as_given():
+    from ppsurf_amd import pieces
+    verts = S.fins()[0]
+    bad = np.array([[0, 0, 1], [-1, 2, 3], [1, 2, 5], [0, 1, 1 << 40], [-(1 << 40), 1, 2], [0, 1, (1 << 32) + 2]], dtype=np.int64)
+    for hv, hf in ((verts, np.zeros((0, 3), np.int64)), (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int64)), (verts, bad),
+                   (np.zeros((0, 3), np.float32), np.array([[0, 1, 2]], np.int64))):
+        v, f = dev(hv), dev(hf)
+        same_table(pieces.component_table(v, f), S.table_spec(hv, hf))
+        out_v, out_f, info = pieces.remove_pieces(v, f, 1, 0.5, 1)
+        assert out_v is v and out_f is f and info == S.remove_spec(hv, hf, 1, 0.5, 1)[2] and info['components'] == 0
+    mixed = np.concatenate([bad[:3], S.fins()[1], bad[3:]])
+    out_v, out_f, info = pieces.remove_pieces(dev(verts), dev(mixed), 1)
+    assert out_f.cpu().numpy().tobytes() == S.fins()[1].tobytes() and info == S.remove_spec(verts, mixed, 1)[2] and info['faces_valid'] == 3
+
+
+@pytest.mark.parametrize('name', ['scene', 'scene:robin', 'debris', 'cube8:255', 'cube8:257', 'cube8:766'])
+def test_the_components_agree_with_the_shipped_bounded_walk(name):
+    from ppsurf_amd import ops, pieces
+    verts, faces, _ = mesh(name)
+    v, f = dev(verts), dev(faces)
+    table = pieces.component_table(v, f)
+    cid = torch.searchsorted(table['leader'], table['label'].long())
+    size = table['faces'][cid]
+    if name == 'debris':
+        assert int((table['faces'] == 33).sum()) == 2                 # components just past k = 32
+    for k in (1, 6, 12, 32):
+        small = ops.mesh_small_components(f, verts.shape[0], k)
+        assert torch.equal(small, size <= k), k
+
+
+def fixed_point(fa, fb, label, nf):
+    """The host loop of pieces._labels on hand-made tables."""
+    from ppsurf_amd import _lib
+    changed = torch.zeros(1, dtype=I32, device=DEV)
+    for rounds in range(1, 100):
+        changed.zero_()
+        _lib.call('ppsx_pieces_hook', fa, fb, int(fa.shape[0]), label, nf, changed)
+        assert int(changed.item()) in (0, 1)
+        if int(changed.item()) == 0:
+            return rounds
+        _lib.call('ppsx_pieces_compress', label, nf)
+    raise AssertionError('no fixed point')
+
+
+def test_hook_and_compress_alone_skip_bad_pairs_and_invalid_faces():
+    from ppsurf_amd import _lib
+    # nf = 8, face 3 invalid; pairs onto it, out of range on either side, and three good ones
+    buf = torch.full((10,), -7, dtype=I32, device=DEV)
+    buf[1:9] = dev(np.array([0, 1, 2, -1, 4, 5, 6, 7], dtype=np.int32))
+    label = buf[1:9]
+    fa = dev(np.array([0, 2, 2, 4, -1, 6, 3, 8, 2 ** 31 - 1], dtype=np.int32))
+    fb = dev(np.array([1, 1, 3, 9, 5, 5, 7, 0, 0], dtype=np.int32))
+    changed = torch.zeros(1, dtype=I32, device=DEV)
+    _lib.call('ppsx_pieces_hook', fa, fb, 9, label, 8, changed)
+    one = label.cpu().numpy()
+    # one round: the labels have only fallen, stay in their component, and the skipped faces are as they were
+    assert int(changed.item()) == 1 and one[1] == 0 and one[2] in (0, 1) and one[6] == 5 and one[[0, 3, 4, 5, 7]].tolist() == [0, -1, 4, 5, 7]
+    _lib.call('ppsx_pieces_compress', label, 8)                       # a hook that raised the flag is followed by a compress
+    fixed_point(fa, fb, label, 8)
+    assert label.cpu().numpy().tolist() == [0, 0, 0, -1, 4, 5, 5, 7] and buf[0].item() == -7 and buf[9].item() == -7
+    # a fixed point leaves the flag down at once and writes nothing
+    assert fixed_point(fa, fb, label, 8) == 1 and label.cpu().numpy().tolist() == [0, 0, 0, -1, 4, 5, 5, 7]
+    # compress alone: chains, an untouched invalid face, and a label above its slot, where a walk ends as at a root
+    buf[1:9] = dev(np.array([0, 0, 1, 2, -1, 7, 5, 3], dtype=np.int32))
+    _lib.call('ppsx_pieces_compress', label, 8)
+    assert label.cpu().numpy().tolist() == [0, 0, 0, 0, -1, 5, 5, 0] and buf[0].item() == -7 and buf[9].item() == -7
+    # np = 0: nothing to do
+    _lib.call('ppsx_pieces_hook', None, None, 0, label, 8, changed, on=torch.device(DEV))
+
+
+def stats_by_hand(verts, faces, label, cid, nc):
+    count = np.zeros(nc, dtype=np.int64)
+    lo, hi = np.full((nc, 3), np.inf, dtype=np.float32), np.full((nc, 3), -np.inf, dtype=np.float32)
+    ok = S.valid_faces(faces, verts.shape[0])
+    for t in range(faces.shape[0]):
+        if ok[t] and label[t] >= 0 and 0 <= cid[t] < nc:
+            corners = verts[faces[t]] + np.float32(0.0)
+            count[cid[t]] += 1
+            lo[cid[t]] = np.minimum(lo[cid[t]], corners.min(axis=0))
+            hi[cid[t]] = np.maximum(hi[cid[t]], corners.max(axis=0))
+    return count, lo, hi
+
+
+@pytest.mark.parametrize('nf', [255, 256, 257, 1280])
+@pytest.mark.parametrize('mix', ['interleaved', 'many', 'one'])
+def test_stats_alone(nf, mix):
+    from ppsurf_amd import _lib
+    verts, faces = smooth_spec.noisy_sphere()
+    verts, faces = verts.copy(), np.array(faces[:nf])
+    verts[faces[0, 0]] = [-0.0, -0.0, -0.0]
+    t = np.arange(nf)
+    nc = {'interleaved': 6, 'many': 70, 'one': 1}[mix]
+    cid = {'interleaved': t % 5, 'many': (t * 7) % 70, 'one': t * 0}[mix].astype(np.int32)          # 'interleaved' leaves component 5 empty
+    label = t.astype(np.int32)
+    if mix != 'one':
+        cid[11::17] = nc                                              # out of range, on either side
+        cid[5::29] = -2
+        label[3::23] = -1
+        faces[::31, 1] = -1                                           # invalid one way or another
+        faces[7::31, 2] = 642
+        faces[9::31, 0] = faces[9::31, 1]
+    count = torch.full((nc + 2,), -7, dtype=I64, device=DEV)
+    lo, hi = torch.full((nc + 2, 3), -7.0, dtype=F32, device=DEV), torch.full((nc + 2, 3), -7.0, dtype=F32, device=DEV)
+    want = stats_by_hand(verts, faces, label, cid, nc)
+    for _ in range(2):
+        _lib.call('ppsx_pieces_stats', dev(verts), 642, dev(faces), nf, dev(label), dev(cid), nc, count[1:nc + 1], lo[1:nc + 1], hi[1:nc + 1])
+        for got, exp in zip((count, lo, hi), want):
+            g = got.cpu().numpy()
+            assert g[1:nc + 1].tobytes() == exp.tobytes() and (g[0] == -7).all() and (g[-1] == -7).all()
+    if mix == 'interleaved':
+        assert want[0][5] == 0 and np.isposinf(want[1][5]).all() and np.isneginf(want[2][5]).all()
+    if mix == 'one':
+        assert want[0].tolist() == [nf]
+
+
+def test_select_alone_at_the_exact_thresholds():
+    from ppsurf_amd import _lib
+    half_up = float(np.nextafter(0.5, 1.0))
+    table = {'leader': np.arange(7, dtype=np.int64), 'faces': np.array([768, 192, 48, 48, 12, 192, 2 ** 31 - 1], dtype=np.int64),
+             'lo': np.zeros((7, 3), dtype=np.float32),
+             'hi': np.array([[8, 8, 8], [4, 4, 4], [2, 2, 2], [2, 2, 2], [1, 1, 1], [2, 2, 2], [16, 0, 0]], dtype=np.float32), 'box_diag2': 768.0}
+    table['diag2'] = S.diag2_of(table['lo'], table['hi'])
+    assert table['diag2'].tolist() == [192, 48, 12, 12, 3, 12, 256]
+    rank = S.rank_spec(table['faces'])
+    assert rank.tolist() == [1, 2, 4, 5, 6, 3, 0]
+    count, lo, hi, drank = dev(table['faces']), dev(table['lo']), dev(table['hi']), dev(rank)
+    keep = torch.full((9,), 7, dtype=torch.uint8, device=DEV)
+
+    def run(min_faces=None, frac=None, largest=None, D2=768.0):
+        _lib.call('ppsx_pieces_select', count, lo, hi, drank, 7, int(min_faces is not None), min_faces or 1, int(frac is not None), frac or 0.0,
+                  int(largest is not None), largest or 1, D2, keep[1:8])
+        assert keep[0].item() == 7 and keep[8].item() == 7
+        return keep[1:8].cpu().numpy().astype(bool)
+
+    for rules in ((None, 0.5, None), (None, half_up, None), (None, 0.25, None), (None, 0.125, None), (None, 0.0, None), (None, 1.0, None),
+                  (48, None, None), (49, None, None), (2 ** 31 - 1, None, None), (1, None, None), (None, None, 1), (None, None, 3), (None, None, 7),
+                  (None, None, 2 ** 31 - 1), (13, 0.125, 3), (193, 0.25, 2), (12, float(np.nextafter(0.0625, 0.0)), None)):
+        assert np.array_equal(run(*rules), S.select_spec(table, *rules)), rules
+    assert run(frac=0.5).tolist() == [True, False, False, False, False, False, True]           # 0.25 * 768 == 192: equality passes
+    assert run(frac=half_up).tolist() == [False] * 6 + [True]
+    assert run(largest=3).tolist() == [True, True, False, False, False, False, True]            # the tie of 192 goes to the smaller leader
+    assert run(frac=1.0, D2=0.0).all() and run(frac=0.0).all()
+    # a rule whose flag is down is not read: NULL tables
+    _lib.call('ppsx_pieces_select', count, None, None, None, 7, 1, 48, 0, 0.0, 0, 1, 768.0, keep[1:8])
+    assert keep[1:8].cpu().numpy().tolist() == [1, 1, 1, 1, 0, 1, 1]
+
+
+def test_bad_arguments_are_an_error_return_and_write_nothing():
+    from ppsurf_amd import _lib, pieces, topology
+    hv, hf = S.scene()
+    verts, faces = dev(hv), dev(hf)
+    nv, nf = 642, 1260
+    want = spec_table('scene')
+    fa, fb, valid = topology.manifold_pairs(faces, nv)
+    pairs = int(fa.shape[0])
+    assert fa.dtype == I32 and fb.dtype == I32 and valid.dtype == torch.bool and bool(valid.all()) and pairs == 1260 * 3 // 2
+    assert set(zip(torch.minimum(fa, fb).tolist(), torch.maximum(fa, fb).tolist())) == S.pairs(hf, nv)
+    label0 = torch.arange(nf, dtype=I32, device=DEV)
+    label, cid = dev(want['label']), dev(want['cid'].astype(np.int32))
+    count, lo, hi, rank = dev(want['faces']), dev(want['lo']), dev(want['hi']), dev(S.rank_spec(want['faces']))
+    keys = torch.full((3 * nf,), -7, dtype=I64, device=DEV)
+    work = label0.clone()
+    changed = torch.zeros(1, dtype=I32, device=DEV)
+    out_n, out_lo, out_hi = torch.full((6,), -7, dtype=I64, device=DEV), torch.full((6, 3), -7.0, device=DEV), torch.full((6, 3), -7.0, device=DEV)
+    keep = torch.full((6,), 7, dtype=torch.uint8, device=DEV)
+    big = 2 ** 31
+
+    def run(name, *args):
+        rc = _lib.call(name, *args, on=torch.device(DEV), unchecked=True)
+        torch.cuda.synchronize()
+        return rc
+
+    def edge_keys(faces=faces, nf=nf, nv=nv, keys=keys):
+        return run('ppsx_pieces_edge_keys', faces, nf, nv, keys)
+
+    def hook(fa=fa, fb=fb, np_=pairs, label=work, nf=nf, changed=changed):
+        return run('ppsx_pieces_hook', fa, fb, np_, label, nf, changed)
+
+    def compress(label=work, nf=nf):
+        return run('ppsx_pieces_compress', label, nf)
+
+    def stats(verts=verts, nv=nv, faces=faces, nf=nf, label=label, cid=cid, nc=6, count=out_n, lo=out_lo, hi=out_hi):
+        return run('ppsx_pieces_stats', verts, nv, faces, nf, label, cid, nc, count, lo, hi)
+
+    def select(count=count, lo=lo, hi=hi, rank=rank, nc=6, has_n=1, n=48, has_f=1, f=0.5, has_k=1, k=3, D2=768.0, keep=keep):
+        return run('ppsx_pieces_select', count, lo, hi, rank, nc, has_n, n, has_f, f, has_k, k, D2, keep)
+
+    for kw in (dict(nf=-1), dict(nv=-1), dict(nf=big), dict(nv=big), dict(faces=None)):
+        assert edge_keys(**kw) == 1, kw
+        assert bool((keys == -7).all()), kw
+    assert edge_keys(keys=None) == 1 and edge_keys(nf=0) == 0 and edge_keys(nf=0, faces=None, keys=None) == 0 and bool((keys == -7).all())
+    for kw in (dict(np_=-1), dict(nf=-1), dict(np_=big), dict(nf=big), dict(fa=None), dict(fb=None), dict(changed=None)):
+        assert hook(**kw) == 1, kw
+        assert torch.equal(work, label0) and changed.item() == 0, kw
+    assert hook(label=None) == 1 and hook(np_=0) == 0 and hook(nf=0) == 0 and hook(np_=0, fa=None, fb=None, label=None, changed=None) == 0
+    for kw in (dict(nf=-1), dict(nf=big), dict(label=None)):
+        assert compress(**kw) == 1, kw
+    assert compress(nf=0) == 0 and compress(nf=0, label=None) == 0 and torch.equal(work, label0) and changed.item() == 0
+    for kw in (dict(nv=-1), dict(nf=-1), dict(nc=-1), dict(nv=big), dict(nf=big), dict(nc=big), dict(verts=None), dict(faces=None), dict(label=None),
+               dict(cid=None), dict(count=None), dict(lo=None), dict(hi=None), dict(hi=out_lo)):
+        assert stats(**kw) == 1, kw
+        assert bool((out_n == -7).all()) and bool((out_lo == -7).all()) and bool((out_hi == -7).all()), kw
+    assert stats(nc=0) == 0 and stats(nc=0, verts=None, faces=None, label=None, cid=None, count=None, lo=None, hi=None) == 0
+    assert bool((out_n == -7).all()) and bool((out_lo == -7).all()) and bool((out_hi == -7).all())
+    for kw in (dict(nc=-1), dict(nc=big), dict(has_n=2), dict(has_f=-1), dict(has_k=2), dict(has_n=0, has_f=0, has_k=0), dict(n=0), dict(n=big), dict(k=0),
+               dict(k=big), dict(f=-0.1), dict(f=float(np.nextafter(1.0, 2.0))), dict(f=float('nan')), dict(f=float('inf')), dict(D2=-1.0),
+               dict(D2=float('nan')), dict(D2=float('inf')), dict(count=None), dict(lo=None), dict(hi=None), dict(rank=None)):
+        assert select(**kw) == 1, kw
+        assert bool((keep == 7).all()), kw
+    assert select(keep=None) == 1 and select(nc=0) == 0 and select(nc=0, count=None, lo=None, hi=None, rank=None, keep=None) == 0
+    assert bool((keep == 7).all())
+    with pytest.raises(_lib.PpsError, match='ppsx_pieces_select failed with status 1'):
+        _lib.call('ppsx_pieces_select', count, lo, hi, rank, 6, 0, 1, 0, 0.0, 0, 1, 768.0, keep)
+    # the good calls after the refused ones
+    assert edge_keys() == 0 and keys.cpu().numpy().tobytes() == S.edge_keys(hf, nv).tobytes()
+    assert fixed_point(fa, fb, work, nf) >= 2 and work.cpu().numpy().tobytes() == want['label'].tobytes()
+    assert stats() == 0 and out_n.cpu().numpy().tobytes() == want['faces'].tobytes()
+    assert out_lo.cpu().numpy().tobytes() == want['lo'].tobytes() and out_hi.cpu().numpy().tobytes() == want['hi'].tobytes()
+    assert select() == 0 and keep.cpu().numpy().astype(bool).tolist() == S.select_spec(want, 48, 0.5, 3).tolist()
+    # no faces: every component is empty
+    assert stats(nf=0, faces=None, label=None, cid=None) == 0 and bool((out_n == 0).all()) and bool(torch.isposinf(out_lo).all())
+    # the Python layer
+    for fn in (lambda v: pieces.remove_pieces(v, faces[:1], 1), lambda v: pieces.component_table(v, faces[:1])):
+        with pytest.raises(ValueError, match='non-finite'):
+            fn(torch.cat([verts[:5], torch.full((1, 3), float('nan'), device=DEV)]))
+    with pytest.raises(ValueError, match='min_faces'):
+        pieces.remove_pieces(verts.cpu(), faces, 0)                       # the parameters come first
+    with pytest.raises(pieces.CpuTensorError, match='no CPU'):
+        pieces.remove_pieces(verts.cpu(), faces, 1)
+    with pytest.raises(ValueError, match='nv'):
+        pieces.face_components(faces, -1)
+
+
+@pytest.mark.parametrize('double', [False, True])
+def test_the_command_removes_pieces_of_a_coloured_ply(tmp_path, capsys, double):
+    from ppsurf_amd import meshio, pieces
+    verts, faces = S.scene()
+    # a face with a repeated index after face 300 (a PLY holds no index out of range), and a single face across the first and the last cube
+    faces = np.concatenate([faces[:301], [[0, 0, 1]], faces[301:], [[640, 641, 1]]])
+    offset = np.array([5.0e5, -2.5e5, 120.0]) if double else np.array([10.0, -20.0, 5.0])
+    verts = verts.astype(np.float64) + offset[None]
+    rgb = np.random.default_rng(5).integers(0, 256, size=(verts.shape[0], 3)).astype(np.uint8)
+    src, dst = str(tmp_path / 'in.ply'), str(tmp_path / 'out.ply')
+    meshio.write_ply_mesh_colored(src, verts, faces, rgb, double=double)
+    report = pieces.main([src, dst, '--min_faces', '49', '--min_diag_frac', '0.125'])
+    assert json.loads(capsys.readouterr().out.strip().split('\n')[-1]) == report
+    stored, stored_f = meshio.read_ply_mesh(src, dtype=np.float64)
+    assert np.array_equal(stored_f, faces)
+    centre = (stored.min(axis=0) + stored.max(axis=0)) * 0.5
+    local = (stored - centre[None]).astype(np.float32)
+    want_v, want_f, want_info, leaders = S.remove_spec(local, faces, 49, 0.125, None)
+    top = report.pop('top')
+    assert report == want_info and report['faces_out'] == 1152 and report['faces_in'] == 1262 and report['faces_valid'] == 1261
+    assert leaders == [0, 769, 1069] and report['components'] == 7 and report['box_diag2'] == 768.0
+    assert top == [[0, 768, 0.25], [769, 192, 0.0625], [1069, 192, 0.015625], [961, 48, 0.015625], [1009, 48, 0.015625], [1057, 12, 0.00390625],
+                   [1261, 1, top[6][2]]] and 0 < top[6][2] < 1
+    table = S.table_spec(local, faces)
+    used = np.zeros(verts.shape[0], dtype=bool)
+    used[faces[np.isin(table['label'], leaders)].reshape(-1)] = True
+    got_v, got_f = meshio.read_ply_mesh(dst, dtype=np.float64)
+    assert np.array_equal(got_f, want_f) and np.array_equal(got_v, stored[used])              # the kept rows as read
+    assert np.array_equal(meshio.read_ply_vertex_colors(dst), rgb[used])
+    assert (b'property double x' in open(dst, 'rb').read(300)) == double
+    with pytest.raises(SystemExit):
+        pieces.main([src, dst])                                        # no rule: no default is proposed

@@ -241,6 +241,67 @@ int ppsx_pieces_select(const int64_t* count, const float* lo, const float* hi, c
                        int64_t min_faces, int has_min_diag_frac, double min_diag_frac, int has_keep_largest, int64_t keep_largest,
                        double box_diag2, uint8_t* keep, void* stream);
 
+/* ---- edge-collapse decimation: quadric error metric, rounds of independent collapses (csrc/pps_decimate.hip) -------------------------------
+ * new capability: replaces nothing -- the reference has no decimation and the vertex clustering (pps_simplify_*) stays as it is.  Driven by
+ * ppsurf_amd/decimate.py (the rows by ppsurf_amd/topology.py); the rule and the argument for the independence of a round's winners are
+ * written out at the top of csrc/pps_decimate.hip and in DESIGN.md section 22.  Row v of the adjacency is the entries offsets[v] ..
+ * offsets[v + 1] - 1 (offsets int64 [nv + 1]) of nbr int32 [ne] (ascending) and mult int32 [ne]; src int32 [ne] is the row of every entry;
+ * row v of the incidence is the entries inc_offsets[v] .. inc_offsets[v + 1] - 1 of inc int32 [ni] (ascending), as topology.adjacency_rows
+ * and topology.incidence_rows build them.  A priority is three uint64 compared lexicographically: the bits of the fp64 cost, h(key) and
+ * key = (a << 32) | b, h the splitmix64 finaliser of key + 0x9E3779B97F4A7C15; NONE is 2^64 - 1 three times.  All arithmetic is fp64, every
+ * operation rounded on its own; one thread per entry, vertex, winner or face; no atomics: each entry is a pure function of its inputs.  A
+ * row whose offsets are not 0 <= o0 <= o1 <= the count is taken as empty and an index out of range is skipped; neither is read through.
+ *   ppsx_decimate_regular     regular u8 [nv]: 1 when the vertex has a face, every entry of its adjacency row has mult == 2 and its incidence
+ *                             row is as long as its adjacency row, else 0.
+ *                             nv < 0 or > 2^31 - 1, ne or ni < 0, or -- with nv > 0 -- a NULL offsets, inc_offsets or regular or a NULL mult
+ *                             with ne > 0: PPS_ERR_ARG, nothing is launched or written.  nv == 0: 0, nothing is launched.
+ *   ppsx_decimate_edges       prio u64 [ne,3], x f64 [ne,3], fell u8 [ne]: for the entry e = (a, b) = (src[e], nbr[e]) with a < b, both ends
+ *                             regular, exactly two common entries c, d in the rows of a and b, and not (a face of a holds c and d and a
+ *                             face of b holds c and d): the placement x relative to mid = (P_a + P_b) * 0.5 over the faces of a ascending,
+ *                             then the faces of b that do not hold a (the quadric, lambda = 1e-3 trace, the cofactor solve; x = 0 and
+ *                             fell = 1 when the trace is 0, x is not finite or (x_0^2 + x_1^2) + x_2^2 > |P_b - P_a|^2), the cost = the sum
+ *                             of (n . x - m)^2 over the same faces in the same order, and the fold rule (every face that holds one end only
+ *                             keeps a positive n . n' with that end at x).  A candidate gets its priority, x and fell; every other entry
+ *                             gets NONE, x = 0 and fell = 0.  Every row of the outputs is written.  The formulas are at the top of the
+ *                             .hip file.
+ *                             nv or nf < 0 or > 2^31 - 1, ne or ni < 0, or -- with ne > 0 -- a NULL nbr, src, prio, x or fell, with nv > 0
+ *                             a NULL pos, offsets, inc_offsets or regular, a NULL faces with nf > 0 or a NULL inc with ni > 0: PPS_ERR_ARG,
+ *                             nothing is launched or written.  ne == 0: 0, nothing is launched.
+ *   ppsx_decimate_vertex_min  m1 u64 [nv,3]: the minimum priority over the entries of row u; the entry (u, v) with u > v is read at its
+ *                             mirror, the entry of row v that names u (a binary search; skipped when there is none).  NONE for an empty row.
+ *                             nv < 0 or > 2^31 - 1, ne < 0, or -- with nv > 0 -- a NULL offsets or m1 or, with ne > 0, a NULL nbr or prio:
+ *                             PPS_ERR_ARG, nothing is launched or written.  nv == 0: 0, nothing is launched.
+ *   ppsx_decimate_ring_min    best u64 [nv,3]: the minimum of m1 u64 [nv,3] over w and the entries of row w.
+ *                             nv < 0 or > 2^31 - 1, ne < 0, best == m1, or -- with nv > 0 -- a NULL offsets, m1 or best or a NULL nbr with
+ *                             ne > 0: PPS_ERR_ARG, nothing is launched or written.  nv == 0: 0, nothing is launched.
+ *   ppsx_decimate_winners     flag u8 [ne]: 1 for an entry (a, b), a < b, whose priority is not NONE and equals best[a] and best[b], else 0.
+ *                             nv < 0 or > 2^31 - 1, ne < 0, or -- with ne > 0 -- a NULL src, nbr, prio or flag or a NULL best with nv > 0:
+ *                             PPS_ERR_ARG, nothing is launched or written.  ne == 0: 0, nothing is launched.
+ *   ppsx_decimate_move        for every winner e = win[i] (int64 [nw]) with (a, b) = (src[e], nbr[e]): pos[a] = (pos[a] + pos[b]) * 0.5 +
+ *                             x[e] per component and rename[b] = a (rename int32 [nv], the identity before).  The winners of a round share
+ *                             no end, so no two threads touch one row.  An e outside [0, ne) or an entry without 0 <= a < b < nv is
+ *                             skipped.
+ *                             nv or nw < 0 or > 2^31 - 1, ne < 0, or -- with nw > 0 -- a NULL win, with ne > 0 a NULL src, nbr or x, with
+ *                             nv > 0 a NULL pos or rename: PPS_ERR_ARG, nothing is launched or written.  nw == 0 (or ne == 0, nv == 0): 0,
+ *                             nothing is launched.
+ *   ppsx_decimate_rename      out int64 [nf,3], keep u8 [nf]: the face with every index i replaced by rename[i], and keep = 1 when the three
+ *                             new indices lie in [0, nv) and are pairwise distinct.  A face with an index outside [0, nv) is copied as it
+ *                             is with keep = 0.
+ *                             nv or nf < 0 or > 2^31 - 1, or -- with nf > 0 -- a NULL faces, out or keep or a NULL rename with nv > 0:
+ *                             PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched. */
+int ppsx_decimate_regular(const int64_t* offsets, const int32_t* mult, int64_t ne, const int64_t* inc_offsets, int64_t ni, int64_t nv,
+                          uint8_t* regular, void* stream);
+int ppsx_decimate_edges(const double* pos, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* offsets, const int32_t* nbr,
+                        const int32_t* src, int64_t ne, const int64_t* inc_offsets, const int32_t* inc, int64_t ni, const uint8_t* regular,
+                        uint64_t* prio, double* x, uint8_t* fell, void* stream);
+int ppsx_decimate_vertex_min(const int64_t* offsets, const int32_t* nbr, int64_t ne, int64_t nv, const uint64_t* prio, uint64_t* m1, void* stream);
+int ppsx_decimate_ring_min(const int64_t* offsets, const int32_t* nbr, int64_t ne, int64_t nv, const uint64_t* m1, uint64_t* best, void* stream);
+int ppsx_decimate_winners(const int32_t* src, const int32_t* nbr, int64_t ne, int64_t nv, const uint64_t* prio, const uint64_t* best, uint8_t* flag,
+                          void* stream);
+int ppsx_decimate_move(const int64_t* win, int64_t nw, const int32_t* src, const int32_t* nbr, int64_t ne, const double* x, double* pos, int64_t nv,
+                       int32_t* rename, void* stream);
+int ppsx_decimate_rename(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* rename, int64_t* out, uint8_t* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

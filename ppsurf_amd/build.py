@@ -1,11 +1,13 @@
 """Builds libppsurf_amd.so (HIP kernels + C ABI, gfx950 only) in-tree with hipcc.
 
-    python -m ppsurf_amd.build [--force] [--variant NAME -DFLAG ...]
+    python -m ppsurf_amd.build [--force] [--variant NAME [--for SOURCE] -DFLAG ...]
 
 hipcc cross-compiles without a GPU; the .so is git-ignored but travels with the repo snapshot to the GPU box.
 Every source is compiled to its own object (in parallel, only when it or a header changed) and the objects are linked into the
 shared library.  `--variant NAME` builds libppsurf_amd_NAME.so with extra -D switches (ablation / tuning builds for tools/;
-selected at run time with PPS_LIB_VARIANT=NAME, never used by the product or the tests).
+selected at run time with PPS_LIB_VARIANT=NAME, never used by the product or the tests).  The switches may be any -D / -f / -m option or
+`-Xclang ARG` pairs; `--for SOURCE` gives them to that one source only, e.g. the measuring build of profiles/NOTES_unpacked_valu.md:
+    python -m ppsurf_amd.build --variant nopk --for pps_decode.hip -Xclang -target-feature -Xclang -packed-fp32-ops
 """
 import concurrent.futures
 import os
@@ -29,7 +31,7 @@ def _newer(path, deps):
     return any(os.path.getmtime(d) > t for d in deps if os.path.isfile(d))
 
 
-def build(force=False, verbose=False, variant=None, defines=()):
+def build(force=False, verbose=False, variant=None, defines=(), only=None):
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     lib = LIB if not variant else os.path.join(HERE, 'libppsurf_amd_{}.so'.format(variant))
     objdir = os.path.join(CSRC, 'build' + ('_' + variant if variant else ''))
@@ -40,7 +42,7 @@ def build(force=False, verbose=False, variant=None, defines=()):
     for s in srcs:
         src, obj = os.path.join(CSRC, s), os.path.join(objdir, os.path.splitext(s)[0] + '.o')
         if force or _newer(obj, [src] + headers):
-            jobs.append([hipcc] + FLAGS + list(defines) + ['-c', src, '-o', obj])
+            jobs.append([hipcc] + FLAGS + (list(defines) if only in (None, s) else []) + ['-c', src, '-o', obj])
     if jobs:
         def run(cmd):
             if verbose:
@@ -61,7 +63,14 @@ def build(force=False, verbose=False, variant=None, defines=()):
 
 if __name__ == '__main__':
     argv = sys.argv[1:]
-    variant, defines = None, [a for a in argv if a.startswith(('-D', '-f', '-m'))]
+    variant, only, defines = None, None, []
+    for i, a in enumerate(argv):
+        if a == '-Xclang':
+            defines += [a, argv[i + 1]]
+        elif a.startswith(('-D', '-f', '-m')) and (i == 0 or argv[i - 1] != '-Xclang'):
+            defines.append(a)
     if '--variant' in argv:
         variant = argv[argv.index('--variant') + 1]
-    print(build(force='--force' in argv, verbose=True, variant=variant, defines=defines))
+    if '--for' in argv:
+        only = argv[argv.index('--for') + 1]
+    print(build(force='--force' in argv, verbose=True, variant=variant, defines=defines, only=only))

@@ -25,9 +25,34 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define PPS_SG_DSREAD 0x100
 #define PPS_SG_VALU 0x002
 
+// Kernel attribute: no packed fp32 VALU (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) in this kernel and in everything inlined into it.  hipcc forms
+// them from every f32x4 + f32x4 and pairs neighbouring scalar adds under -O3; beside MFMAs a packed op holds its SIMD's issue slot for longer than
+// the two plain ops it replaces, and most of what packing saves goes into v_pk_mov / v_mov register pairing (profiles/NOTES_unpacked_valu.md).
+// The plain ops round exactly as the packed ones.  Device pass only: the host pass of the same source knows no such feature.
+// The inliner takes a plain `inline` function into a caller with other target features only where it must: such a kernel would CALL the HIP headers'
+// __syncthreads and __shfl_xor (s_swappc_b64).  Every helper of ours is __forceinline__; pps::wg_barrier and pps::shfl_xor_f32 below stand for the two.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PPS_PLAIN_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define PPS_PLAIN_F32
+#endif
+
 namespace pps {
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// __syncthreads() and __shfl_xor(float, mask) of the HIP headers (wave of 64), statement for statement, but always inlined (see PPS_PLAIN_F32)
+__device__ __forceinline__ __attribute__((convergent)) void wg_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+__device__ __forceinline__ float shfl_xor_f32(float v, int lane_mask) {
+    const int self = (int)__builtin_amdgcn_mbcnt_hi(-1, __builtin_amdgcn_mbcnt_lo(-1, 0));
+    int index = self ^ lane_mask;
+    index = index >= ((self + PPS_WAVE) & ~(PPS_WAVE - 1)) ? self : index;
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(index << 2, __builtin_bit_cast(int, v)));
+}
 
 // ---- reductions over the 16 rows of a tile (lanes with equal l>>4), pure DPP ------------------------
 template <int CTRL>

@@ -36,7 +36,7 @@ __device__ __forceinline__ void stream_step(const f32x4* __restrict__ gnext, f32
     chunk_copy_async<CHUNK_F4_NEXT / NTH, NTH>(gnext, nxt);
     compute((const f32x4*)cur);
     stream_wait();
-    __syncthreads();
+    wg_barrier();
     f32x4* t = cur; cur = nxt; nxt = t;
 }
 
@@ -52,7 +52,7 @@ __device__ __forceinline__ void stream_step_spread_at(const char* chunk, const u
     f32x4* dst = nxt;
     compute((const f32x4*)cur, [&](int i) { if (i < CHUNK_F4_NEXT / NTH) chunk_copy_piece_at<NTH>(chunk, dst, i, voff[i]); });
     stream_wait();
-    __syncthreads();
+    wg_barrier();
     f32x4* t = cur; cur = nxt; nxt = t;
 }
 
@@ -92,7 +92,7 @@ template <int BUF_F4, int FIRST_F4 = BUF_F4, int NTH = NT>
 __device__ __forceinline__ void stream_begin(const f32x4* __restrict__ g, f32x4*& cur, f32x4*& nxt) {
     chunk_copy_async<FIRST_F4 / NTH, NTH>(g, (f32x4*)pps_smem);
     stream_wait();
-    __syncthreads();
+    wg_barrier();
     cur = (f32x4*)pps_smem;
     nxt = cur + BUF_F4;
 }
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
                 ((f32x4*)(mss + wave * 64))[4 * n + g] = ss;
             }
         }
-        __syncthreads();
+        wg_barrier();
         {
             // lane = head: combine the 4 waves of this query
             float mw[4], sw[4];
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
             for (int w2 = 0; w2 < 4; ++w2) S += sw[w2] * __expf(mw[w2] - M);
             f_l[wave * 64 + lane] = __expf(mw[wq] - M) / (64.f * S);
         }
-        __syncthreads();
+        wg_barrier();
         float an = 0.f;
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) {
@@ -278,13 +278,13 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) an += e[bb * 4 + r] * f4[r];
         }
-        an += __shfl_xor(an, 16);
-        an += __shfl_xor(an, 32);           // attention weight of row n (mean over the 64 heads)
+        an += shfl_xor_f32(an, 16);
+        an += shfl_xor_f32(an, 32);           // attention weight of row n (mean over the 64 heads)
 #pragma unroll
         for (int bb = 0; bb < 16; ++bb) a[bb] *= an;
         rows16_sum_transposed(a, lane);                     // lane (n,g): a[0] = sum over the 16 rows of block n
         ((f32x4*)(part + wave * 256))[4 * n + g] = a[0];
-        __syncthreads();
+        wg_barrier();
         if (wq == 0 && qv) {
             f32x4 s = ((const f32x4*)(part + (wbase + 0) * 256))[lane];
             s += ((const f32x4*)(part + (wbase + 1) * 256))[lane];
@@ -313,6 +313,7 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 static_assert(IH_OB == 2, "the weight pointer of the kernel's layer step wraps behind the step that fetches the last chunk: right for two output blocks per chunk only");
 #define IH_LDS_BYTES (2 * IH_CH4 * 16 + (IP_W_XYZ + IP_NBIAS + IH_NW * 64 * 3 + IH_NW * 256) * 4)
 
+PPS_PLAIN_F32
 __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float* __restrict__ G, const float* __restrict__ pts,
                                                                      const float* __restrict__ query, const int64_t* __restrict__ idx,
                                                                      int64_t Q, int k, const float* __restrict__ wxyz,
@@ -344,6 +345,9 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     const int wq = wave & 3, wbase = wave & ~3;
+    // Static priority instead of a flip around the MFMA phase of every pass: the second-dispatched half of the workgroup (waves 4-7, the second query)
+    // loses the issue arbitration to its older SIMD partner on every phase; raised once, it takes the partner's timing (profiles/NOTES_unpacked_valu.md)
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
     for (int it = 0; it < count; ++it) {
         const int64_t qi = (int64_t)(first + it * stride) * (IH_NW / 4) + (wave >> 2);
         const bool qv = qi < Q;
@@ -364,7 +368,6 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) x[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
         }
-        __builtin_amdgcn_s_setprio(PPS_PRIO);
         // One streamed layer step: IH_OB output blocks of ACTV(BIAS + W IN) from the current chunk, handed pair by pair to SINK; the 4 (8-wave
         // workgroup) pieces of the next chunk's copy go out after k-steps 0, 2, 4, 6 of the first output-block pair.
         // LAST: the step that fetches the last chunk of the pass -- the pointer wraps to the first chunk behind it
@@ -388,7 +391,6 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
             IH_STEP(c + 32 / IH_OB + 2 == IH_NCH, x, bias4 + 128 + 4 * IH_OB * c, 0,
                     ([&](int p, const f32x4& o0, const f32x4& o1) { b[IH_OB * c + 2 * p] = o0; b[IH_OB * c + 2 * p + 1] = o1; }));
 #undef IH_STEP
-        __builtin_amdgcn_s_setprio(0);
         // ---- softmax over the 64 neighbours (4 waves x 16 rows) for each of the 64 heads: as in interp_pool_kernel -------------
         float e[16];
         {
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
                 ((f32x4*)(mss + wave * 64))[4 * n + g] = ss;
             }
         }
-        __syncthreads();
+        wg_barrier();
         {
             float mw[4], sw[4];
 #pragma unroll
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
             for (int w2 = 0; w2 < 4; ++w2) S += sw[w2] * __expf(mw[w2] - M);
             f_l[wave * 64 + lane] = __expf(mw[wq] - M) / (64.f * S);
         }
-        __syncthreads();
+        wg_barrier();
         float an = 0.f;
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) {
@@ -436,8 +438,8 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
 #pragma unroll
             for (int r = 0; r < 4; ++r) an += e[bb * 4 + r] * f4[r];
         }
-        an += __shfl_xor(an, 16);
-        an += __shfl_xor(an, 32);           // attention weight of row n (mean over the 64 heads)
+        an += shfl_xor_f32(an, 16);
+        an += shfl_xor_f32(an, 32);           // attention weight of row n (mean over the 64 heads)
         f32x4 a[16];
 #pragma unroll
         for (int kb = 0; kb < 8; ++kb) {                               // h3 back to fp32 (hi + lo) in the standard block layout
@@ -447,7 +449,7 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
         }
         rows16_sum_transposed(a, lane);
         ((f32x4*)(part + wave * 256))[4 * n + g] = a[0];
-        __syncthreads();
+        wg_barrier();
         if (wq == 0 && qv) {
             f32x4 s = ((const f32x4*)(part + (wbase + 0) * 256))[lane];
             s += ((const f32x4*)(part + (wbase + 1) * 256))[lane];
@@ -502,7 +504,7 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
     }
     for (int i = threadIdx.x; i < NB; i += IS_NT) bias_l[i] = bias[i];
     for (int i = threadIdx.x; i < nout * (C + 1); i += IS_NT) tail_l[i] = wtail[i];
-    __syncthreads();
+    wg_barrier();
     for (int64_t qi = blockIdx.x; qi < Q; qi += gridDim.x) {
         const int row = wave * 16 + n;
         const bool valid = row < k;
@@ -553,7 +555,7 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
                 ((f32x4*)(mss + wave * 64))[4 * n + g] = ss;
             }
         }
-        __syncthreads();
+        wg_barrier();
         {
             float mw[4], sw[4];
 #pragma unroll
@@ -564,7 +566,7 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
             for (int w2i = 0; w2i < 4; ++w2i) S += sw[w2i] * __expf(mw[w2i] - M);
             f_l[wave * 64 + lane] = __expf(mw[wave] - M) / (64.f * S);
         }
-        __syncthreads();
+        wg_barrier();
         float an = 0.f;
 #pragma unroll
         for (int bb = 0; bb < 4; ++bb) {
@@ -572,8 +574,8 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
 #pragma unroll
             for (int r = 0; r < 4; ++r) an += e[bb * 4 + r] * f4[r];
         }
-        an += __shfl_xor(an, 16);
-        an += __shfl_xor(an, 32);
+        an += shfl_xor_f32(an, 16);
+        an += shfl_xor_f32(an, 32);
 #pragma unroll
         for (int bb = 0; bb < CB; ++bb) {
             f32x4 p;
@@ -581,7 +583,7 @@ __global__ __launch_bounds__(IS_NT) void interp_small_kernel(const float* __rest
             for (int r = 0; r < 4; ++r) p[r] = row16_sum(an * a[bb][r]);
             if (n == 0) ((f32x4*)(part + wave * C))[4 * bb + g] = p;
         }
-        __syncthreads();
+        wg_barrier();
         if (threadIdx.x < nout) {
             float acc = tail_l[nout * C + threadIdx.x];
             for (int c = 0; c < C; ++c) acc += tail_l[threadIdx.x * C + c] * (part[c] + part[C + c] + part[2 * C + c] + part[3 * C + c]);
@@ -752,9 +754,9 @@ __device__ __forceinline__ void stn_query_tiles(const float* __restrict__ qpatch
 // tmax (H only): 3 -- a query with at most three full tiles takes them through the chain in one pass (stn_query_tiles); 2 -- two tiles at a time
 // with a running maximum for every patch size (what fb > 3 always does).
 template <bool H>
-__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
-                                                                   const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
-                                                                   const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
+__device__ __forceinline__ void pointnet_stn_rows_body(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
+                                                       const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
+                                                       const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
     // flag: H -- where the range guard of the split reports (pps_common.h); !H -- gate of the fp32 fallback (may be null)
     if (!H && gate_closed(flag)) return;
     float amax = 0.f;
@@ -887,6 +889,20 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* 
         }
     }
     if (H) range_commit(amax, flag);
+}
+// the kernel proper; the split-precision instantiation alone is compiled without packed fp32 VALU (PPS_PLAIN_F32, pps_common.h)
+template <bool H>
+__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
+                                                                   const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
+                                                                   const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
+    pointnet_stn_rows_body<H>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag);
+}
+template <>
+PPS_PLAIN_F32
+__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel<true>(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
+                                                                         const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
+                                                                         const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
+    pointnet_stn_rows_body<true>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag);
 }
 
 // =====================================================================================================
@@ -1125,8 +1141,8 @@ __device__ __forceinline__ void feat_rows_query(const float* __restrict__ patche
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
+        s += shfl_xor_f32(s, 16);
+        s += shfl_xor_f32(s, 32);
         s += s0;
         // online softmax: advance the state with this tile's logits, then add its rows (conv3 acts on the pooled vector, in the tail)
         const float mblk = row16_max(valid ? s : -INFINITY);
@@ -1146,15 +1162,15 @@ __device__ __forceinline__ void feat_rows_query(const float* __restrict__ patche
 }
 
 template <bool H>
-__global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float* __restrict__ patches, const float* __restrict__ trans2,
-                                                                    int64_t Q, int P, const float* __restrict__ wpack,
-                                                                    const f32x4* __restrict__ wdense, const float* __restrict__ bias,
-                                                                    float* __restrict__ xbar, int* __restrict__ flag) {
+__device__ __forceinline__ void pointnet_feat_rows_body(const float* __restrict__ patches, const float* __restrict__ trans2,
+                                                        int64_t Q, int P, const float* __restrict__ wpack,
+                                                        const f32x4* __restrict__ wdense, const float* __restrict__ bias,
+                                                        float* __restrict__ xbar, int* __restrict__ flag) {
     if (!H && gate_closed(flag)) return;
     float amax = 0.f;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     const PhaseC pc = phase_c_setup<PNT>(wpack, wdense, bias);
-    __syncthreads();
+    wg_barrier();
     const float s0 = ((const float*)pc.bias4)[576 + 256];     // wq . b3 + bq
     const int ntile_rows = (P + 15) / 16;
 
@@ -1183,6 +1199,22 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float*
         feat_rows_query<H>(patches, q, P, ntile_rows, th, tl, tf, pc, s0, amax, lane, xbar);
     }
     if (H) range_commit(amax, flag);
+}
+// as for pointnet_stn_rows_kernel: the split-precision instantiation alone without packed fp32 VALU
+template <bool H>
+__global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel(const float* __restrict__ patches, const float* __restrict__ trans2,
+                                                                    int64_t Q, int P, const float* __restrict__ wpack,
+                                                                    const f32x4* __restrict__ wdense, const float* __restrict__ bias,
+                                                                    float* __restrict__ xbar, int* __restrict__ flag) {
+    pointnet_feat_rows_body<H>(patches, trans2, Q, P, wpack, wdense, bias, xbar, flag);
+}
+template <>
+PPS_PLAIN_F32
+__global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel<true>(const float* __restrict__ patches, const float* __restrict__ trans2,
+                                                                          int64_t Q, int P, const float* __restrict__ wpack,
+                                                                          const f32x4* __restrict__ wdense, const float* __restrict__ bias,
+                                                                          float* __restrict__ xbar, int* __restrict__ flag) {
+    pointnet_feat_rows_body<true>(patches, trans2, Q, P, wpack, wdense, bias, xbar, flag);
 }
 
 // =====================================================================================================
@@ -1232,6 +1264,7 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_head_h_kernel(const float*
 #define PF_QSTRIDE 257                 // half8 per query of an exchange buffer: 4 KiB + 16 B
 #define PF_BUF (8 * PF_QSTRIDE)        // half8 per buffer of 8 queries
 #define PF_LDS_BYTES (PC_LDS_BYTES + 3 * PF_BUF * 16)
+PPS_PLAIN_F32
 __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const float* __restrict__ patches, const half8* __restrict__ uh,
                                                                           int64_t Q, int P, const f32x4* __restrict__ wfc,
                                                                           const float* __restrict__ bias_fc, const float* __restrict__ wpack,
@@ -1265,7 +1298,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
             for (int kb = 0; kb < 2; ++kb) { u[kb].hi = uh[qc * 16 + (2 * kb) * 4 + g]; u[kb].lo = uh[qc * 16 + (2 * kb + 1) * 4 + g]; }
 #pragma unroll
             for (int ob = 0; ob < 4; ++ob) {
-                __syncthreads();                         // the slice in the buffer has been picked up (first pass: the resident weights are in place)
+                wg_barrier();                         // the slice in the buffer has been picked up (first pass: the resident weights are in place)
                 const int c = 8 * ob + wave;
                 const half8* wc = (const half8*)(w3 + c * CH4);
                 asm volatile("" : "+s"(wc));             // opaque: the chunk's 32 loads per lane stay behind the barrier instead of all four slices' being hoisted
@@ -1276,7 +1309,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
                     d[0] = v.hi;
                     d[64] = v.lo;
                 });
-                __syncthreads();
+                wg_barrier();
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb) {
                     th[ob][kb] = ex_r[(2 * kb) * 64];
@@ -1365,6 +1398,7 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_kernel(const float* __restr
 // two 256 -> 256 halves ([pooled | xbar] are two tensors), the second starts from the fp32 accumulators of the first.
 // w16 (half8 fragments): pps_pack_dense_f16x3 images, 32 KiB chunks (two output blocks each): Wa and Wb ALTERNATING chunk by chunk (the pair of
 // output blocks 2c, 2c+1 is finished before the next one starts: two live accumulator blocks instead of sixteen), then [L2][L3].
+PPS_PLAIN_F32
 __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __restrict__ pooled, const float* __restrict__ xbar, int64_t Q,
                                                               const f32x4* __restrict__ w16, const float* __restrict__ bias,
                                                               float* __restrict__ logits, float* __restrict__ occ, int* __restrict__ range) {

@@ -28,9 +28,28 @@ from .ops import csr_build, csr_build_table           # csr() below calls csr_bu
 LOW = (torch.bfloat16, torch.float16)          # 16-bit storage types of the fused training ops (trainer.precision bf16-mixed / 16-mixed)
 
 
+_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
 def _code(dt):
-    """dtype argument of the C entries: 1 bfloat16, 2 IEEE half."""
-    return 1 if dt == torch.bfloat16 else 2
+    """dtype argument of the C entries: 0 float32, 1 bfloat16, 2 IEEE half; no other type reaches a kernel."""
+    if dt not in _CODES:
+        raise ValueError('train_ops: no kernel reads {}'.format(dt))
+    return _CODES[dt]
+
+
+def _f32(t):
+    """t as the fp32 contiguous constant the kernels read (weights, affine pairs, points); None stays None."""
+    return None if t is None else t.detach().float().contiguous()
+
+
+def _empty32(dev, *shape):
+    return torch.empty(shape, device=dev, dtype=torch.float32)
+
+
+def _ws(nbytes, dev, floor=0):
+    """Scratch of one call, sized by the library's *_ws_bytes (floor: where the entry wants a valid address even for a shape that needs none)."""
+    return torch.empty((max(int(nbytes), floor),), device=dev, dtype=torch.uint8)
 
 
 def _low(t, like=None):
@@ -99,7 +118,7 @@ class _GatherRows(torch.autograd.Function):
             return torch.zeros((ctx.n, dout.shape[1]), device=dout.device, dtype=ctx.dtype), None
         order, offsets = csr(idx, ctx.n)
         dout = dout.contiguous()
-        dx = torch.empty((ctx.n, dout.shape[1]), device=dout.device, dtype=torch.float32)
+        dx = _empty32(dout.device, ctx.n, dout.shape[1])
         if dout.dtype in LOW and dout.shape[1] % 4 == 0:
             _lib.call('pps_segment_sum_rows_16', dout, order, offsets, ctx.n, dout.shape[1], _code(dout.dtype), dx)
         else:
@@ -117,33 +136,36 @@ class _HeadInput(torch.autograd.Function):
         _lib.need_device('train_ops', table, ids, pts, query, wx)
         table = _low(table)
         ids = ids.contiguous()
-        pts32, q32 = pts.detach().float().contiguous(), query.detach().float().contiguous()
-        wx32 = wx.detach().float().contiguous()
+        pts32, q32, wx32 = _f32(pts), _f32(query), _f32(wx)
         nq, c = q32.shape[0], table.shape[1]
         h1 = torch.empty((nq * k, c), device=table.device, dtype=table.dtype)
         _lib.call('pps_head_input_fwd', table, ids, pts32, q32, nq, k, c, _code(table.dtype), wx32, h1)
         ctx.save_for_backward(ids, pts32, q32)
-        ctx.meta = (table.shape[0], k, c, wx.dtype, wx.shape, table.dtype)
+        ctx.meta = (table.shape[0], k, wx.dtype, wx.shape, table.dtype)
         return h1
 
     @staticmethod
     def backward(ctx, dh1):
-        ids, pts32, q32 = ctx.saved_tensors
-        n, k, c, wdt, wshape, dt = ctx.meta
-        L = _lib.lib()
-        dh1 = dh1.to(dt).contiguous()
-        dtable = dwx = None
-        if ctx.needs_input_grad[0]:
-            order, offsets = csr(ids, n)
-            dt32 = torch.empty((n, c), device=dh1.device, dtype=torch.float32)
-            _lib.call('pps_segment_sum_rows_16', dh1, order, offsets, n, c, _code(dt), dt32)
-            dtable = dt32.to(dt)
-        if ctx.needs_input_grad[5]:
-            dwx = torch.empty((c, 3), device=dh1.device, dtype=torch.float32)
-            ws = torch.empty((L.pps_head_input_ws_bytes(c),), device=dh1.device, dtype=torch.uint8)
-            _lib.call('pps_head_input_dwx', dh1, ids, pts32, q32, q32.shape[0], k, c, _code(dt), dwx, ws)
-            dwx = dwx.reshape(wshape).to(wdt)
+        n, k, wdt, wshape, dt = ctx.meta
+        dtable, dwx = _head_input_bwd(dh1.to(dt).contiguous(), *ctx.saved_tensors, n, k, wshape, wdt, ctx.needs_input_grad[0], ctx.needs_input_grad[5])
         return dtable, None, None, None, None, dwx
+
+
+def _head_input_bwd(dh1, ids, pts32, q32, n, k, wshape, wdt, need_table, need_wx):
+    """Backward of the head's first layer from dh1 [Q*k, C] (16-bit, contiguous) -> (d table [n, C] in dh1's type by the segmented sum of the gather,
+    d wx in wx's shape and type by pps_head_input_dwx); None for what is not needed.  Shared by _HeadInput and _HeadChain."""
+    c, dt, dev = dh1.shape[1], dh1.dtype, dh1.device
+    dtable = dwx = None
+    if need_table:
+        order, offsets = csr(ids, n)
+        dt32 = _empty32(dev, n, c)
+        _lib.call('pps_segment_sum_rows_16', dh1, order, offsets, n, c, _code(dt), dt32)
+        dtable = dt32.to(dt)
+    if need_wx:
+        dwx = _empty32(dev, c, 3)
+        _lib.call('pps_head_input_dwx', dh1, ids, pts32, q32, q32.shape[0], k, c, _code(dt), dwx, _ws(_lib.lib().pps_head_input_ws_bytes(c), dev))
+        dwx = dwx.reshape(wshape).to(wdt)
+    return dtable, dwx
 
 
 def head_input_supported(c):
@@ -209,9 +231,8 @@ class _NeighbourContract(torch.autograd.Function):
         if g.shape != (m, k, 16):
             raise ValueError('neighbour_contract: g must be [m, k, 16], got {}'.format(tuple(g.shape)))
         out = torch.empty((m, c * 16), device=x.device, dtype=x.dtype)
-        _lib.call('pps_neighbour_contract_fwd', x, idx, g, m, k, c, _code(x.dtype) if low else 0, out)
+        _lib.call('pps_neighbour_contract_fwd', x, idx, g, m, k, c, _code(x.dtype), out)
         ctx.save_for_backward(x, idx, g)
-        ctx.low = low
         return out
 
     @staticmethod
@@ -221,14 +242,14 @@ class _NeighbourContract(torch.autograd.Function):
         n, c = x.shape
         dout = dout.to(x.dtype).contiguous()
         need_x, _, need_g = ctx.needs_input_grad
-        dxg = torch.empty((m * k, c), device=x.device, dtype=torch.float32) if need_x else None
-        dg = torch.empty((m, k, 16), device=x.device, dtype=torch.float32) if need_g else None
+        dxg = _empty32(x.device, m * k, c) if need_x else None
+        dg = _empty32(x.device, m, k, 16) if need_g else None
         if need_x or need_g:
-            _lib.call('pps_neighbour_contract_bwd', x, idx, g, dout, m, k, c, _code(x.dtype) if ctx.low else 0, dxg if need_x else None, dg if need_g else None)
+            _lib.call('pps_neighbour_contract_bwd', x, idx, g, dout, m, k, c, _code(x.dtype), dxg if need_x else None, dg if need_g else None)
         dx = None
         if need_x:
             order, offsets = csr(idx.view(-1), n)
-            dx = torch.empty((n, c), device=x.device, dtype=torch.float32)
+            dx = _empty32(x.device, n, c)
             _lib.call('pps_segment_sum_rows_f32', dxg, order, offsets, n, c, dx)
         return dx, None, dg
 
@@ -247,9 +268,8 @@ class _FkaGeometry(torch.autograd.Function):
             raise ValueError('fka_geometry: inconsistent sizes')
         # the kernel moves entry 0 (norm_radius) in place: on a copy, unless the caller hands over a vector nobody else reads (pack_geo's)
         geo_w = geo.detach() if owned and geo.is_contiguous() and geo.dtype == torch.float32 else geo.detach().clone().contiguous()
-        g = torch.empty((b * m, k, 16), device=pts.device, dtype=torch.float32)
-        stat = torch.empty((2, b, 32), device=pts.device, dtype=torch.float32)
-        ws = torch.empty((_lib.lib().pps_fka_train_ws_bytes(b, m, k),), device=pts.device, dtype=torch.uint8)
+        g, stat = _empty32(pts.device, b * m, k, 16), _empty32(pts.device, 2, b, 32)
+        ws = _ws(_lib.lib().pps_fka_train_ws_bytes(b, m, k), pts.device)
         _lib.call('pps_fka_geometry_fwd_f32', pts, sup, idx, b, m, k, geo_w, float(momentum), g, stat, ws)
         ctx.save_for_backward(pts, sup, idx, geo_w, stat)
         ctx.dims = (b, m, k)
@@ -266,8 +286,8 @@ class _FkaGeometry(torch.autograd.Function):
         pts, sup, idx, geo_w, stat = ctx.saved_tensors
         b, m, k = ctx.dims
         dg = dg.contiguous().float()
-        dgeo = torch.empty((GEO_FLOATS,), device=dg.device, dtype=torch.float32)
-        ws = torch.empty((_lib.lib().pps_fka_train_ws_bytes(b, m, k),), device=dg.device, dtype=torch.uint8)
+        dgeo = _empty32(dg.device, GEO_FLOATS)
+        ws = _ws(_lib.lib().pps_fka_train_ws_bytes(b, m, k), dg.device)
         _lib.call('pps_fka_geometry_bwd_f32', pts, sup, idx, b, m, k, geo_w, stat, dg, dgeo, ws)
         return dgeo, None, None, None, None, None, None, None
 
@@ -280,22 +300,35 @@ def fka_geometry(geo, pts, sup, idx, b, m, momentum, owned=False):
     return _FkaGeometry.apply(geo, pts, sup, idx, b, m, momentum, owned)
 
 
+def _bn_fwd_args(op, x, weight, bias):
+    """What the two BatchNorm nodes prepare alike -> (x fp32 or 16-bit and contiguous, w32, b32, y, save [2, c], workspace); `op` names the node in
+    the error for a shape the reduction does not take."""
+    if x.dtype not in (torch.float32,) + LOW:
+        x = x.float()
+    x = x.contiguous()
+    rows, c = x.shape
+    w32, b32 = _f32(weight), _f32(bias)
+    y = torch.empty_like(x)
+    save = _empty32(x.device, 2, c)
+    nbytes = _lib.lib().pps_bn_train_ws_bytes(rows, c)
+    if nbytes == 0 and rows > 0:
+        raise ValueError('{}: unsupported shape [{}, {}]'.format(op, rows, c))
+    return x, w32, b32, y, save, _ws(nbytes, x.device, 1)
+
+
+def _bn_bwd_args(x, dy):
+    """-> (dy in x's type, dx, dgamma, dbeta, workspace) of the two BatchNorm nodes' backward."""
+    rows, c = x.shape
+    return (dy.to(x.dtype).contiguous(), torch.empty_like(x), _empty32(x.device, c), _empty32(x.device, c),
+            _ws(_lib.lib().pps_bn_train_ws_bytes(rows, c), x.device, 1))
+
+
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu):
         _lib.need_device('train_ops', x, weight, bias)
-        if x.dtype not in (torch.float32,) + LOW:
-            x = x.float()
-        x = x.contiguous()
-        rows, c = x.shape
-        w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-        y = torch.empty_like(x)
-        save = torch.empty((2, c), device=x.device, dtype=torch.float32)
-        nbytes = _lib.lib().pps_bn_train_ws_bytes(rows, c)
-        if nbytes == 0 and rows > 0:
-            raise ValueError('bn_act: unsupported shape [{}, {}]'.format(rows, c))
-        ws = torch.empty((max(nbytes, 1),), device=x.device, dtype=torch.uint8)
-        _lib.call('pps_bn_train_fwd', x, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, running_mean, running_var, float(momentum), float(eps),
+        x, w32, b32, y, save, ws = _bn_fwd_args('bn_act', x, weight, bias)
+        _lib.call('pps_bn_train_fwd', x, x.shape[0], x.shape[1], _code(x.dtype), w32, b32, running_mean, running_var, float(momentum), float(eps),
                   int(bool(relu)), y, save, ws)
         ctx.save_for_backward(x, w32, b32, save)
         ctx.relu = bool(relu)
@@ -305,13 +338,8 @@ class _BnAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w32, b32, save = ctx.saved_tensors
-        rows, c = x.shape
-        dy = dy.to(x.dtype).contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.empty((c,), device=x.device, dtype=torch.float32)
-        dbeta = torch.empty((c,), device=x.device, dtype=torch.float32)
-        ws = torch.empty((max(_lib.lib().pps_bn_train_ws_bytes(rows, c), 1),), device=x.device, dtype=torch.uint8)
-        _lib.call('pps_bn_train_bwd', x, dy, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, save, int(ctx.relu), dx, dgamma, dbeta, ws)
+        dy, dx, dgamma, dbeta, ws = _bn_bwd_args(x, dy)
+        _lib.call('pps_bn_train_bwd', x, dy, x.shape[0], x.shape[1], _code(x.dtype), w32, b32, save, int(ctx.relu), dx, dgamma, dbeta, ws)
         return dx, dgamma.to(ctx.dtypes[0]), dbeta.to(ctx.dtypes[1]), None, None, None, None, None
 
 
@@ -321,19 +349,9 @@ class _BnAddRelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, running_mean, running_var, momentum, eps):
         _lib.need_device('train_ops', x, res, weight, bias)
-        if x.dtype not in (torch.float32,) + LOW:
-            x = x.float()
-        x = x.contiguous()
+        x, w32, b32, y, save, ws = _bn_fwd_args('bn_add_relu', x, weight, bias)
         res = res.to(x.dtype).contiguous()
-        rows, c = x.shape
-        w32, b32 = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-        y = torch.empty_like(x)
-        save = torch.empty((2, c), device=x.device, dtype=torch.float32)
-        nbytes = _lib.lib().pps_bn_train_ws_bytes(rows, c)
-        if nbytes == 0 and rows > 0:
-            raise ValueError('bn_add_relu: unsupported shape [{}, {}]'.format(rows, c))
-        ws = torch.empty((max(nbytes, 1),), device=x.device, dtype=torch.uint8)
-        _lib.call('pps_bn_add_relu_fwd', x, res, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, running_mean, running_var, float(momentum),
+        _lib.call('pps_bn_add_relu_fwd', x, res, x.shape[0], x.shape[1], _code(x.dtype), w32, b32, running_mean, running_var, float(momentum),
                   float(eps), y, save, ws)
         ctx.save_for_backward(x, res, w32, b32, save)
         ctx.dtypes = (weight.dtype, bias.dtype)
@@ -342,13 +360,9 @@ class _BnAddRelu(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, res, w32, b32, save = ctx.saved_tensors
-        rows, c = x.shape
-        dy = dy.to(x.dtype).contiguous()
-        dx, dres = torch.empty_like(x), torch.empty_like(x)
-        dgamma = torch.empty((c,), device=x.device, dtype=torch.float32)
-        dbeta = torch.empty((c,), device=x.device, dtype=torch.float32)
-        ws = torch.empty((max(_lib.lib().pps_bn_train_ws_bytes(rows, c), 1),), device=x.device, dtype=torch.uint8)
-        _lib.call('pps_bn_add_relu_bwd', x, res, dy, rows, c, _code(x.dtype) if x.dtype in LOW else 0, w32, b32, save, dx, dres, dgamma, dbeta, ws)
+        dy, dx, dgamma, dbeta, ws = _bn_bwd_args(x, dy)
+        dres = torch.empty_like(x)
+        _lib.call('pps_bn_add_relu_bwd', x, res, dy, x.shape[0], x.shape[1], _code(x.dtype), w32, b32, save, dx, dres, dgamma, dbeta, ws)
         return dx, dres, dgamma.to(ctx.dtypes[0]), dbeta.to(ctx.dtypes[1]), None, None, None, None
 
 
@@ -370,9 +384,8 @@ def col_sum(x):
     nbytes = _lib.lib().pps_bn_train_ws_bytes(rows, c)
     if nbytes == 0:
         return None
-    out = torch.empty((c,), device=x.device, dtype=torch.float32)
-    ws = torch.empty((nbytes,), device=x.device, dtype=torch.uint8)
-    _lib.call('pps_col_sum_strided', x, rows, c, ld, _code(x.dtype) if x.dtype in LOW else 0, out, ws)
+    out = _empty32(x.device, c)
+    _lib.call('pps_col_sum_strided', x, rows, c, ld, _code(x.dtype), out, _ws(nbytes, x.device))
     return out
 
 
@@ -433,19 +446,21 @@ def gemm_supported(x, k):
     return x.is_cuda and x.dtype in LOW and k % 8 == 0 and k >= 8
 
 
+def _gemm_operand(t):
+    """t [rows, cols] as the dense-layer kernels read it: unit column stride, a row pitch that is a multiple of 8 elements and a 16-byte aligned
+    address (a block of columns of a wider tensor is read where it lies); copied only when it is not like that."""
+    return t.contiguous() if t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16 else t
+
+
 def gemm_nt(x, w, bias=None, out_f32=False):
     """x [M, K] @ w [N, K]^T (+ bias [N] fp32) -> [M, N] in x's 16-bit type (or fp32): pps_gemm_nt_16.  No autograd (called from autograd functions)."""
     _lib.need_device('train_ops', x, w)
     assert x.dim() == 2 and w.dim() == 2 and x.shape[1] == w.shape[1] and x.dtype == w.dtype and x.dtype in LOW
-    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
-        x = x.contiguous()
-    if w.stride(1) != 1 or w.stride(0) % 8 or w.data_ptr() % 16:
-        w = w.contiguous()
+    x, w = _gemm_operand(x), _gemm_operand(w)
     m, k = x.shape
     n = w.shape[0]
     y = torch.empty((m, n), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-    b32 = None if bias is None else bias.detach().float().contiguous()
-    _lib.call('pps_gemm_nt_16', x, x.stride(0), w, w.stride(0), b32, y, n, m, n, k, _code(x.dtype), int(bool(out_f32)))
+    _lib.call('pps_gemm_nt_16', x, x.stride(0), w, w.stride(0), _f32(bias), y, n, m, n, k, _code(x.dtype), int(bool(out_f32)))
     return y
 
 
@@ -453,15 +468,11 @@ def gemm_tn(g, x):
     """g [M, N]^T @ x [M, K] -> fp32 [N, K] (the weight gradient of a row layer: contraction over the rows): pps_gemm_tn_16.  N, K multiples of 8."""
     _lib.need_device('train_ops', g, x)
     assert g.dim() == 2 and x.dim() == 2 and g.shape[0] == x.shape[0] and g.dtype == x.dtype and g.dtype in LOW
-    if g.stride(1) != 1 or g.stride(0) % 8 or g.data_ptr() % 16:
-        g = g.contiguous()
-    if x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
-        x = x.contiguous()
+    g, x = _gemm_operand(g), _gemm_operand(x)
     m, n = g.shape
     k = x.shape[1]
-    L = _lib.lib()
-    dw = torch.empty((n, k), device=g.device, dtype=torch.float32)
-    ws = torch.empty((max(int(L.pps_gemm_tn_ws_bytes(m, n, k)), 16),), device=g.device, dtype=torch.uint8)
+    dw = _empty32(g.device, n, k)
+    ws = _ws(_lib.lib().pps_gemm_tn_ws_bytes(m, n, k), g.device, 16)
     _lib.call('pps_gemm_tn_16', g, g.stride(0), x, x.stride(0), m, n, k, _code(g.dtype), dw, ws)
     return dw
 
@@ -479,7 +490,7 @@ class _AttnPool(torch.autograd.Function):
         q, k, heads = qy.shape
         c = h.shape[2]
         pooled = torch.empty((q, c), device=h.device, dtype=dt)
-        _lib.call('pps_attn_pool_fwd', qy, h, q, k, heads, c, _code(dt) if dt in LOW else 0, ctx.relu_h, pooled)
+        _lib.call('pps_attn_pool_fwd', qy, h, q, k, heads, c, _code(dt), ctx.relu_h, pooled)
         ctx.save_for_backward(qy, h)
         return pooled
 
@@ -490,7 +501,7 @@ class _AttnPool(torch.autograd.Function):
         c = h.shape[2]
         dpooled = dpooled.to(h.dtype).contiguous()
         dqy, dh = torch.empty_like(qy), torch.empty_like(h)
-        _lib.call('pps_attn_pool_bwd', qy, h, dpooled, q, k, heads, c, _code(h.dtype) if h.dtype in LOW else 0, ctx.relu_h, dqy, dh)
+        _lib.call('pps_attn_pool_bwd', qy, h, dpooled, q, k, heads, c, _code(h.dtype), ctx.relu_h, dqy, dh)
         return dqy, dh, None
 
 
@@ -509,6 +520,72 @@ class Act:
         return (torch.relu(z) if self.relu else z).to(self.raw.dtype)
 
 
+def _rows_fwd(x, in_affine, in_relu, w, b, bn=None):
+    """The one caller of pps_rows_layer_fwd: y = act(x) W^T + b with x in its stored form (in_affine [2, cin] or None, in_relu applied on load);
+    bn = (gamma, beta, running_mean, running_var, momentum, eps) takes the batch statistics of y on store (running statistics updated in place), None
+    leaves them.  -> (x, aff, w32, g32, save, y) in the order the nodes save them for _rows_bwd, and out_affine [2, cout] (save, out_affine, g32: None
+    without bn)."""
+    x = _low(x)
+    rows, cin = x.shape
+    cout = w.shape[0]
+    dev = x.device
+    w32, b32, aff = _f32(w), _f32(b), _f32(in_affine)
+    gamma, beta, running_mean, running_var, momentum, eps = bn or (None,) * 6
+    g32, be32 = _f32(gamma), _f32(beta)
+    y = torch.empty((rows, cout), device=dev, dtype=x.dtype)
+    out_affine = _empty32(dev, 2, cout) if bn else None
+    save = _empty32(dev, 2, cout) if bn else None
+    ws = _ws(_lib.lib().pps_rows_layer_ws_bytes(cin, cout), dev)
+    _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
+              b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine,
+              save, ws)
+    return (x, aff, w32, g32, save, y), out_affine
+
+
+def _rows_meta(in_relu, w, b):
+    """What _rows_bwd needs of a layer besides its saved tensors: (in_relu, dtype of w, dtype of b or None)."""
+    return bool(in_relu), w.dtype, None if b is None else b.dtype
+
+
+def _rows_bwd(ctx, entry, grad_args, saved, meta, g_affine):
+    """The one place that allocates the gradients and the workspace of a row layer and calls its backward entry.  `entry` says how the gradient of
+    the raw output y arrives, `grad_args` are that entry's own leading arguments:
+        'rows'    (gy [rows, cout],)                 the gradient as a tensor                          pps_rows_layer_bwd
+        'pooled'  (gval, arg, p)                     one value per (group, channel) in row arg        pps_rows_layer_bwd_pooled
+        'rank2'   (a, dl, dpooled, v, p)             a[q, j] dpooled[q, :] + dl[q, j] v per group     pps_rows_layer_bwd_rank2
+    saved = (x, aff, w32, g32, save, y) of _rows_fwd, meta of _rows_meta, g_affine [2, cout] the gradient of the layer's BatchNorm affine (None
+    without one).  ctx.needs_input_grad[0 / 1] must be those of x / in_affine.  -> the gradients of the first seven arguments every row-layer
+    forward has: (dx, d_in_affine, None, dw, db, dgamma, dbeta) in the parameters' types."""
+    x, aff, w32, g32, save, y = saved
+    in_relu, wdt, bdt = meta
+    rows, cin = x.shape
+    cout = w32.shape[0]
+    dev = x.device
+    bn = g32 is not None
+    need_dx, need_daff = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and aff is not None
+    dx = torch.empty_like(x) if (need_dx or need_daff) else None
+    d_in = _empty32(dev, 2, cin) if need_daff else None
+    dw = _empty32(dev, cout, cin)
+    db = _empty32(dev, cout) if bdt is not None else None
+    dgamma = _empty32(dev, cout) if bn else None
+    dbeta = _empty32(dev, cout) if bn else None
+    ws = _ws(_lib.lib().pps_rows_layer_ws_bytes(cin, cout), dev)
+    code, shift, in_relu, g_affine = _code(x.dtype), _row1(aff, cin), int(in_relu), (g_affine if bn else None)
+    if entry == 'rows':                                      # (spelled out, not starred: tests/test_call_layer_cpu.py counts each site's arguments)
+        gy, = grad_args
+        _lib.call('pps_rows_layer_bwd', x, y, gy, rows, cin, cout, code, aff, shift, in_relu, w32, g32, save, g_affine, dx, None, d_in, dw, db,
+                  dgamma, dbeta, ws)                         # (None: no second gradient of x to add, dx_add)
+    elif entry == 'pooled':
+        gval, arg, p = grad_args
+        _lib.call('pps_rows_layer_bwd_pooled', x, y, gval, arg, p, rows, cin, cout, code, aff, shift, in_relu, w32, g32, save, g_affine, dx, d_in,
+                  dw, db, dgamma, dbeta, ws)
+    else:
+        a, dl, dpooled, v, p = grad_args
+        _lib.call('pps_rows_layer_bwd_rank2', x, y, a, dl, dpooled, v, p, rows, cin, cout, code, aff, shift, in_relu, w32, g32, save, g_affine, dx,
+                  d_in, dw, db, dgamma, dbeta, ws)
+    return dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta
+
+
 class _RowsLayer(torch.autograd.Function):
     """y = act(x) W^T + b over rows with the input's BatchNorm + ReLU applied on load and the output's batch statistics taken on store
     (pps_rows_train.hip).  Returns (y bf16, out_affine [2, cout] or None)."""
@@ -516,49 +593,54 @@ class _RowsLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps):
         _lib.need_device('train_ops', x, w)
-        L = _lib.lib()
-        x = _low(x)
-        rows, cin = x.shape
-        cout = w.shape[0]
-        w32 = w.detach().float().contiguous()
-        b32 = None if b is None else b.detach().float().contiguous()
-        aff = None if in_affine is None else in_affine.detach().float().contiguous()
-        bn = gamma is not None
-        g32 = gamma.detach().float().contiguous() if bn else None
-        be32 = beta.detach().float().contiguous() if bn else None
-        y = torch.empty((rows, cout), device=x.device, dtype=x.dtype)
-        out_affine = torch.empty((2, cout), device=x.device, dtype=torch.float32) if bn else None
-        save = torch.empty((2, cout), device=x.device, dtype=torch.float32) if bn else None
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=x.device, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
-                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine,
-                  save, ws)
-        ctx.save_for_backward(x, aff, w32, g32, save, y)
-        ctx.meta = (bool(in_relu), b is not None, bn, w.dtype, None if b is None else b.dtype)
-        return y, out_affine
+        bn = None if gamma is None else (gamma, beta, running_mean, running_var, momentum, eps)
+        saved, out_affine = _rows_fwd(x, in_affine, in_relu, w, b, bn)
+        ctx.save_for_backward(*saved)
+        ctx.meta = _rows_meta(in_relu, w, b)
+        return saved[5], out_affine
 
     @staticmethod
     def backward(ctx, gy, g_affine):
-        x, aff, w32, g32, save, y = ctx.saved_tensors
-        in_relu, has_b, bn, wdt, bdt = ctx.meta
-        L = _lib.lib()
-        rows, cin = x.shape
-        cout = w32.shape[0]
-        dev = x.device
+        saved = ctx.saved_tensors
+        x, g32 = saved[0], saved[3]
         gy = gy.to(x.dtype).contiguous()
-        if bn:
-            g_affine = torch.zeros((2, cout), device=dev, dtype=torch.float32) if g_affine is None else g_affine.float().contiguous()
-        need_dx, need_daff = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and aff is not None
-        dx = torch.empty_like(x) if (need_dx or need_daff) else None
-        d_in = torch.empty((2, cin), device=dev, dtype=torch.float32) if need_daff else None
-        dw = torch.empty((cout, cin), device=dev, dtype=torch.float32)
-        db = torch.empty((cout,), device=dev, dtype=torch.float32) if has_b else None
-        dgamma = torch.empty((cout,), device=dev, dtype=torch.float32) if bn else None
-        dbeta = torch.empty((cout,), device=dev, dtype=torch.float32) if bn else None
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_bwd', x, y, gy, rows, cin, cout, _code(x.dtype), aff, _row1(aff, cin), int(in_relu),
-                  w32, g32, save, g_affine if bn else None, dx, None, d_in, dw, db, dgamma, dbeta, ws)
-        return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None)
+        if g32 is not None:
+            g_affine = torch.zeros((2, g32.shape[0]), device=x.device, dtype=torch.float32) if g_affine is None else g_affine.float().contiguous()
+        return _rows_bwd(ctx, 'rows', (gy,), saved, ctx.meta, g_affine) + (None, None, None, None)
+
+
+def _extrema_act(raw, affine, relu, groups, p, arg_dtype=torch.int32):
+    """max over the p rows of every group of relu?(raw * scale + shift) from the extrema of the RAW rows (pps_rows_extrema_16): the activation is
+    monotone per channel, so the maximum is taken where scale >= 0 and the minimum elsewhere, and only that value is activated.  affine [2, c] or
+    None (identity).  -> (out [groups, c] fp32, ext the chosen raw extremum, arg (arg_dtype) its row in the group, scale fp32 or None, live = out > 0
+    under relu or None): the last four are what the backward pass needs."""
+    c = raw.shape[1]
+    dev = raw.device
+    mx, mn = torch.empty((groups, c), device=dev), torch.empty((groups, c), device=dev)
+    amx, amn = torch.empty((groups, c), device=dev, dtype=torch.int32), torch.empty((groups, c), device=dev, dtype=torch.int32)
+    _lib.call('pps_rows_extrema_16', raw, groups, p, c, _code(raw.dtype), mx, mn, amx, amn)
+    if affine is None:
+        ext, arg, out = mx, amx, mx
+        scale = None
+    else:
+        scale, shift = affine[0].float(), affine[1].float()
+        up = scale >= 0
+        ext, arg = torch.where(up, mx, mn), torch.where(up, amx, amn).to(arg_dtype)
+        out = ext * scale + shift
+    live = None
+    if relu:
+        live = out > 0
+        out = torch.relu(out)
+    return out, ext, arg, scale, live
+
+
+def _extrema_act_bwd(dout, ext, scale, live, need_daff):
+    """Start of the backward pass of _extrema_act -> (gradient of (scale, shift) [2, c] or None, gradient of the chosen raw value [groups, c] fp32)."""
+    d = dout.float()
+    if live is not None:
+        d = d * live
+    daff = torch.stack([sum_rows(d * ext), sum_rows(d)]) if need_daff else None
+    return daff, (d if scale is None else d * scale)
 
 
 class _RowsLayerMax(torch.autograd.Function):
@@ -570,59 +652,19 @@ class _RowsLayerMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps, relu, groups, p):
         _lib.need_device('train_ops', x, w)
-        L = _lib.lib()
-        x = _low(x)
-        rows, cin = x.shape
-        cout = w.shape[0]
-        dev = x.device
-        w32 = w.detach().float().contiguous()
-        b32 = None if b is None else b.detach().float().contiguous()
-        aff = None if in_affine is None else in_affine.detach().float().contiguous()
-        g32, be32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        y = torch.empty((rows, cout), device=dev, dtype=x.dtype)
-        out_affine = torch.empty((2, cout), device=dev, dtype=torch.float32)
-        save = torch.empty((2, cout), device=dev, dtype=torch.float32)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
-                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine, save, ws)
-        mx, mn = torch.empty((groups, cout), device=dev), torch.empty((groups, cout), device=dev)
-        amx, amn = torch.empty((groups, cout), device=dev, dtype=torch.int32), torch.empty((groups, cout), device=dev, dtype=torch.int32)
-        _lib.call('pps_rows_extrema_16', y, groups, p, cout, _code(y.dtype), mx, mn, amx, amn)
-        scale, shift = out_affine[0], out_affine[1]
-        up = scale >= 0
-        ext, arg = torch.where(up, mx, mn), torch.where(up, amx, amn).to(torch.uint8)
-        out = ext * scale + shift
-        live = None
-        if relu:
-            live = out > 0
-            out = torch.relu(out)
-        ctx.save_for_backward(x, aff, w32, g32, save, y, ext, arg, scale.clone(), live)
-        ctx.meta = (bool(in_relu), b is not None, w.dtype, None if b is None else b.dtype, int(p))
+        saved, out_affine = _rows_fwd(x, in_affine, in_relu, w, b, (gamma, beta, running_mean, running_var, momentum, eps))
+        out, ext, arg, scale, live = _extrema_act(saved[5], out_affine, relu, groups, p, torch.uint8)          # (p <= 255: a byte per winning row)
+        ctx.save_for_backward(*saved, ext, arg, scale.clone(), live)
+        ctx.meta = _rows_meta(in_relu, w, b)
+        ctx.p = int(p)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, aff, w32, g32, save, y, ext, arg, scale, live = ctx.saved_tensors
-        in_relu, has_b, wdt, bdt, p = ctx.meta
-        L = _lib.lib()
-        rows, cin = x.shape
-        cout = w32.shape[0]
-        dev = x.device
-        d = dout.float()
-        if live is not None:
-            d = d * live
-        g_affine = torch.stack([sum_rows(d * ext), sum_rows(d)]).contiguous()        # gradient of (scale, shift) of this layer's BatchNorm
-        gval = (d * scale).to(x.dtype).contiguous()                                    # gradient of the raw output, per (group, channel)
-        need_dx, need_daff = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and aff is not None
-        dx = torch.empty_like(x) if (need_dx or need_daff) else None
-        d_in = torch.empty((2, cin), device=dev, dtype=torch.float32) if need_daff else None
-        dw = torch.empty((cout, cin), device=dev, dtype=torch.float32)
-        db = torch.empty((cout,), device=dev, dtype=torch.float32) if has_b else None
-        dgamma, dbeta = torch.empty((cout,), device=dev, dtype=torch.float32), torch.empty((cout,), device=dev, dtype=torch.float32)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_bwd_pooled', x, y, gval, arg, p, rows, cin, cout, _code(x.dtype), aff, _row1(aff, cin),
-                  int(in_relu), w32, g32, save, g_affine, dx, d_in, dw, db, dgamma, dbeta, ws)
-        return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None, None, None, None)
+        saved, (ext, arg, scale, live) = ctx.saved_tensors[:6], ctx.saved_tensors[6:]
+        g_affine, gval = _extrema_act_bwd(dout, ext, scale, live, True)          # gradient of (scale, shift) of this layer's BatchNorm
+        gval = gval.to(saved[0].dtype).contiguous()                             # gradient of the raw output, per (group, channel)
+        return _rows_bwd(ctx, 'pooled', (gval, arg, ctx.p), saved, ctx.meta, g_affine) + (None,) * 7
 
 
 class _Rows3Layer(torch.autograd.Function):
@@ -631,16 +673,13 @@ class _Rows3Layer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, momentum, eps):
         _lib.need_device('train_ops', x, w)
-        L = _lib.lib()
-        x = x.detach().float().contiguous()
+        x = _f32(x)
         rows = x.shape[0]
-        w32 = w.detach().float().contiguous()
-        b32 = None if b is None else b.detach().float().contiguous()
-        g32, be32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        w32, b32, g32, be32 = _f32(w), _f32(b), _f32(gamma), _f32(beta)
         dt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.bfloat16
         y = torch.empty((rows, 64), device=x.device, dtype=dt if dt in LOW else torch.bfloat16)
-        aff, save = torch.empty((2, 64), device=x.device), torch.empty((2, 64), device=x.device)
-        ws = torch.empty((L.pps_rows3_ws_bytes(),), device=x.device, dtype=torch.uint8)
+        aff, save = _empty32(x.device, 2, 64), _empty32(x.device, 2, 64)
+        ws = _ws(_lib.lib().pps_rows3_ws_bytes(), x.device)
         _lib.call('pps_rows3_fwd', x, rows, w32, b32, _code(y.dtype), y, g32, be32, running_mean, running_var, float(momentum), float(eps), aff,
                   save, ws)
         ctx.save_for_backward(x, y, g32, save)
@@ -651,14 +690,13 @@ class _Rows3Layer(torch.autograd.Function):
     def backward(ctx, gy, g_aff):
         x, y, g32, save = ctx.saved_tensors
         has_b, wdt, bdt = ctx.meta
-        L = _lib.lib()
         dev = x.device
         gy = gy.to(y.dtype).contiguous()
         g_aff = torch.zeros((2, 64), device=dev) if g_aff is None else g_aff.float().contiguous()
-        dw = torch.empty((64, 3), device=dev)
-        db = torch.empty((64,), device=dev) if has_b else None
-        dgamma, dbeta = torch.empty((64,), device=dev), torch.empty((64,), device=dev)
-        ws = torch.empty((L.pps_rows3_ws_bytes(),), device=dev, dtype=torch.uint8)
+        dw = _empty32(dev, 64, 3)
+        db = _empty32(dev, 64) if has_b else None
+        dgamma, dbeta = _empty32(dev, 64), _empty32(dev, 64)
+        ws = _ws(_lib.lib().pps_rows3_ws_bytes(), dev)
         _lib.call('pps_rows3_bwd', x, y, gy, x.shape[0], _code(y.dtype), g32, save, g_aff, dw, db, dgamma, dbeta, ws)
         return None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None
 
@@ -679,7 +717,7 @@ class _PatchTransform(torch.autograd.Function):
         x = _low(x)
         t16 = t.to(x.dtype).contiguous()
         nq = t16.shape[0]
-        aff = None if affine is None else affine.detach().float().contiguous()
+        aff = _f32(affine)
         out = torch.empty_like(x)
         _lib.call('pps_patch_transform_fwd', x, aff, _row1(aff, 64), int(bool(relu)), t16, 1,
                   nq, p, _code(x.dtype), out)
@@ -691,13 +729,12 @@ class _PatchTransform(torch.autograd.Function):
     def backward(ctx, g):
         x, aff, t16 = ctx.saved_tensors
         relu, p, tdt = ctx.meta
-        L = _lib.lib()
         nq = t16.shape[0]
         g = g.to(x.dtype).contiguous()
         dx, dt = torch.empty_like(x), torch.empty_like(t16)
         need_daff = aff is not None and ctx.needs_input_grad[1]
-        daff = torch.empty((2, 64), device=x.device) if need_daff else None
-        ws = torch.empty((L.pps_patch_transform_ws_bytes(),), device=x.device, dtype=torch.uint8)
+        daff = _empty32(x.device, 2, 64) if need_daff else None
+        ws = _ws(_lib.lib().pps_patch_transform_ws_bytes(), x.device)
         _lib.call('pps_patch_transform_bwd', x, aff, _row1(aff, 64), int(relu), t16, 1, g,
                   nq, p, _code(x.dtype), dx, dt, daff, ws)
         return dx, daff, None, dt.to(tdt), None
@@ -723,9 +760,9 @@ class _PatchAttn(torch.autograd.Function):
     def forward(ctx, h, v):
         _lib.need_device('train_ops', h, v)
         h = _low(h)
-        v32 = v.detach().float().contiguous()
+        v32 = _f32(v)
         q, k, c = h.shape
-        pooled = torch.empty((q, c), device=h.device, dtype=torch.float32)
+        pooled = _empty32(h.device, q, c)
         _lib.call('pps_patch_attn_fwd', h, v32, q, k, c, _code(h.dtype), pooled)
         ctx.save_for_backward(h, v32)
         ctx.vdtype = v.dtype
@@ -735,10 +772,9 @@ class _PatchAttn(torch.autograd.Function):
     def backward(ctx, dpooled):
         h, v32 = ctx.saved_tensors
         q, k, c = h.shape
-        L = _lib.lib()
         dpooled = dpooled.float().contiguous()
         dh = torch.empty_like(h)
-        part = torch.empty((L.pps_patch_attn_partials(q), c), device=h.device, dtype=torch.float32)
+        part = _empty32(h.device, _lib.lib().pps_patch_attn_partials(q), c)
         _lib.call('pps_patch_attn_bwd', h, v32, dpooled, q, k, c, _code(h.dtype), dh, part)
         return dh, sum_rows(part).to(ctx.vdtype)
 
@@ -759,36 +795,16 @@ class _ActMax(torch.autograd.Function):
     def forward(ctx, raw, affine, relu, groups, p):
         _lib.need_device('train_ops', raw)
         raw = _low(raw)
-        c = raw.shape[1]
-        dev = raw.device
-        mx, mn = torch.empty((groups, c), device=dev), torch.empty((groups, c), device=dev)
-        amx, amn = torch.empty((groups, c), device=dev, dtype=torch.int32), torch.empty((groups, c), device=dev, dtype=torch.int32)
-        _lib.call('pps_rows_extrema_16', raw, groups, p, c, _code(raw.dtype), mx, mn, amx, amn)
-        if affine is None:
-            ext, arg, out = mx, amx, mx
-            scale = None
-        else:
-            scale, shift = affine[0].float(), affine[1].float()
-            up = scale >= 0
-            ext, arg = torch.where(up, mx, mn), torch.where(up, amx, amn)
-            out = ext * scale + shift
-        live = None
-        if relu:
-            live = out > 0
-            out = torch.relu(out)
+        out, ext, arg, scale, live = _extrema_act(raw, affine, relu, groups, p)
         ctx.save_for_backward(ext, arg, scale, live)
-        ctx.meta = (groups, p, c, affine is not None, raw.dtype)
+        ctx.meta = (groups, p, raw.shape[1], raw.dtype)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         ext, arg, scale, live = ctx.saved_tensors
-        groups, p, c, has_aff, rdt = ctx.meta
-        d = dout.float()
-        if live is not None:
-            d = d * live
-        daff = torch.stack([sum_rows(d * ext), sum_rows(d)]) if has_aff and ctx.needs_input_grad[1] else None
-        dval = d * scale if has_aff else d
+        groups, p, c, rdt = ctx.meta
+        daff, dval = _extrema_act_bwd(dout, ext, scale, live, scale is not None and ctx.needs_input_grad[1])
         draw = torch.zeros((groups, p, c), device=dout.device, dtype=rdt)
         draw.scatter_(1, arg.long().unsqueeze(1), dval.to(rdt).unsqueeze(1))
         return draw.view(groups * p, c), daff, None, None, None
@@ -835,57 +851,34 @@ class _RowsLayerPatchAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, in_affine, in_relu, w, b, gamma, beta, running_mean, running_var, momentum, eps, wq, groups, p):
         _lib.need_device('train_ops', x, w, wq)
-        L = _lib.lib()
-        x = _low(x)
-        rows, cin = x.shape
-        cout = w.shape[0]
-        dev = x.device
-        w32 = w.detach().float().contiguous()
-        b32 = None if b is None else b.detach().float().contiguous()
-        aff = None if in_affine is None else in_affine.detach().float().contiguous()
-        g32, be32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        y = torch.empty((rows, cout), device=dev, dtype=x.dtype)
-        out_affine = torch.empty((2, cout), device=dev, dtype=torch.float32)
-        save = torch.empty((2, cout), device=dev, dtype=torch.float32)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_fwd', x, rows, cin, _code(x.dtype), aff, _row1(aff, cin), int(bool(in_relu)), w32,
-                  b32, cout, y, g32, be32, running_mean, running_var, float(momentum or 0.0), float(eps or 0.0), out_affine, save, ws)
-        wq32 = wq.detach().float().reshape(-1).contiguous()
+        saved, out_affine = _rows_fwd(x, in_affine, in_relu, w, b, (gamma, beta, running_mean, running_var, momentum, eps))
+        y = saved[5]
+        wq32 = _f32(wq).reshape(-1)
         v = wq32 * out_affine[0]                                                     # the logit's weights on the raw output
-        pooled = torch.empty((groups, cout), device=dev, dtype=torch.float32)
-        _lib.call('pps_patch_attn_fwd', y, v, groups, p, cout, _code(y.dtype), pooled)
-        ctx.save_for_backward(x, aff, w32, g32, save, y, v, wq32, out_affine)
-        ctx.meta = (bool(in_relu), b is not None, w.dtype, None if b is None else b.dtype, wq.dtype, tuple(wq.shape), groups, p)
+        pooled = _empty32(y.device, groups, y.shape[1])
+        _lib.call('pps_patch_attn_fwd', y, v, groups, p, y.shape[1], _code(y.dtype), pooled)
+        ctx.save_for_backward(*saved, v, wq32, out_affine)
+        ctx.meta = _rows_meta(in_relu, w, b)
+        ctx.query = (wq.dtype, tuple(wq.shape), groups, p)
         return pooled, out_affine
 
     @staticmethod
     def backward(ctx, dpooled, g_affine):
-        x, aff, w32, g32, save, y, v, wq32, out_affine = ctx.saved_tensors
-        in_relu, has_b, wdt, bdt, qdt, qshape, groups, p = ctx.meta
-        L = _lib.lib()
-        rows, cin = x.shape
-        cout = w32.shape[0]
-        dev = x.device
-        f32e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        saved, (v, wq32, out_affine) = ctx.saved_tensors[:6], ctx.saved_tensors[6:]
+        qdt, qshape, groups, p = ctx.query
+        y = saved[5]
+        rows, cout = y.shape
+        dev = y.device
         dpooled = torch.zeros((groups, cout), device=dev, dtype=torch.float32) if dpooled is None else dpooled.float().contiguous()
-        a, dl = f32e(rows), f32e(rows)
-        part = f32e(L.pps_patch_attn_partials(groups), cout)
+        a, dl = _empty32(dev, rows), _empty32(dev, rows)
+        part = _empty32(dev, _lib.lib().pps_patch_attn_partials(groups), cout)
         _lib.call('pps_patch_attn_bwd_weights', y, v, dpooled, groups, p, cout, _code(y.dtype), a, dl, part)
         dv = sum_rows(part)
         # v = w_q * scale: d w_q = dv * scale, and the scale of the layer's own BatchNorm gets dv * w_q on top of what its consumers hand back
         dwq = (dv * out_affine[0]).reshape(qshape).to(qdt)
         g_affine = torch.zeros((2, cout), device=dev, dtype=torch.float32) if g_affine is None else g_affine.float().clone()
         g_affine[0] += dv * wq32
-        need_dx, need_daff = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and aff is not None
-        dx = torch.empty_like(x) if (need_dx or need_daff) else None
-        d_in = f32e(2, cin) if need_daff else None
-        dw = f32e(cout, cin)
-        db = f32e(cout) if has_b else None
-        dgamma, dbeta = f32e(cout), f32e(cout)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(cin, cout),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_bwd_rank2', x, y, a, dl, dpooled, v, p, rows, cin, cout, _code(x.dtype), aff,
-                  _row1(aff, cin), int(in_relu), w32, g32, save, g_affine, dx, d_in, dw, db, dgamma, dbeta, ws)
-        return (dx if need_dx else None, d_in, None, dw.to(wdt), None if db is None else db.to(bdt), dgamma, dbeta, None, None, None, None, dwq, None, None)
+        return _rows_bwd(ctx, 'rank2', (a, dl, dpooled, v, p), saved, ctx.meta, g_affine) + (None, None, None, None, dwq, None, None)
 
 
 def rows_layer_patch_attn_supported(cin, cout, p, rows):
@@ -910,7 +903,7 @@ def _query_attn_bwd(y3, qy, dpooled, wq32, k, dwq, dbq, ws):
     code = _code(y3.dtype)
     dqy, dy3 = torch.empty_like(qy), torch.empty_like(y3)
     if os.environ.get('PPS_ATTN_GRAD', 'rebuilt') != 'stored' and rows * k < 1 << 32:
-        a = torch.empty((rows,), device=y3.device, dtype=torch.float32)
+        a = _empty32(y3.device, rows)
         _lib.call('pps_attn_pool_bwd_weights', qy, y3, dpooled, rows // k, k, heads, c, code, 1, dqy, a)
         _lib.call('pps_rows_layer_bwd_attn', y3, dqy, rows, c, heads, code, wq32, a, dpooled, k, dy3, dwq, dbq, ws)
         return dy3
@@ -927,15 +920,9 @@ class _QueryAttnPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y3, wq, bq, k):
         _lib.need_device('train_ops', y3, wq)
-        L = _lib.lib()
-        y3 = _low(y3)
+        (y3, _, w32, _, _, qy), _ = _rows_fwd(y3, None, True, wq, bq)
         rows, c = y3.shape
-        heads = wq.shape[0]
-        w32 = wq.detach().float().contiguous()
-        b32 = None if bq is None else bq.detach().float().contiguous()
-        qy = torch.empty((rows, heads), device=y3.device, dtype=y3.dtype)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(c, heads),), device=y3.device, dtype=torch.uint8)
-        _lib.call('pps_rows_layer_fwd', y3, rows, c, _code(y3.dtype), None, None, 1, w32, b32, heads, qy, None, None, None, None, 0.0, 0.0, None, None, ws)
+        heads = w32.shape[0]
         pooled = torch.empty((rows // k, c), device=y3.device, dtype=y3.dtype)
         _lib.call('pps_attn_pool_fwd', qy, y3, rows // k, k, heads, c, _code(y3.dtype), 1, pooled)
         ctx.save_for_backward(y3, w32, qy)
@@ -946,14 +933,13 @@ class _QueryAttnPool(torch.autograd.Function):
     def backward(ctx, dpooled):
         y3, w32, qy = ctx.saved_tensors
         k, has_b, wdt, bdt = ctx.meta
-        L = _lib.lib()
         rows, c = y3.shape
         heads = w32.shape[0]
         dev = y3.device
         dpooled = dpooled.to(y3.dtype).contiguous()
-        dw = torch.empty((heads, c), device=dev, dtype=torch.float32)
-        db = torch.empty((heads,), device=dev, dtype=torch.float32) if has_b else None
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(c, heads),), device=dev, dtype=torch.uint8)
+        dw = _empty32(dev, heads, c)
+        db = _empty32(dev, heads) if has_b else None
+        ws = _ws(_lib.lib().pps_rows_layer_ws_bytes(c, heads), dev)
         dy3 = _query_attn_bwd(y3, qy, dpooled, w32, k, dw, db, ws)
         return dy3, dw.to(wdt), None if db is None else db.to(bdt), None
 
@@ -972,22 +958,13 @@ class _HeadChain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, ids, pts, query, k, wx, w2, b2, w3, b3, wq, bq):
         _lib.need_device('train_ops', table, ids, pts, query, wx, w2, w3, wq)
-        L = _lib.lib()
         table = _low(table)
         ids = ids.contiguous()
-        f32 = lambda t: None if t is None else t.detach().float().contiguous()
-        pts32, q32, wx32, w2_32, w3_32, wq32 = f32(pts), f32(query), f32(wx), f32(w2), f32(w3), f32(wq)
-        b2_32, b3_32, bq32 = f32(b2), f32(b3), f32(bq)
+        pts32, q32, wx32, w2_32, w3_32, wq32 = _f32(pts), _f32(query), _f32(wx), _f32(w2), _f32(w3), _f32(wq)
         nq, c, heads = q32.shape[0], table.shape[1], wq32.shape[0]
-        dev, dt = table.device, table.dtype
-        rows = nq * k
-        pad = (rows + 255) // 256 * 256               # the kernel writes whole 256-row units (unconditional stores): padded storage, views of the rows
-        h1, y2, y3 = (torch.empty((pad, c), device=dev, dtype=dt)[:rows] for _ in range(3))
-        qy = torch.empty((pad, heads), device=dev, dtype=dt)[:rows]
-        ws = torch.empty((L.pps_head_chain_ws_bytes(),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_head_chain_fwd', table, ids, pts32, q32, nq, k, _code(dt), wx32, w2_32, b2_32, w3_32, b3_32, wq32, bq32, h1, y2, y3, qy, ws)
-        pooled = torch.empty((nq, c), device=dev, dtype=dt)
-        _lib.call('pps_attn_pool_fwd', qy, y3, nq, k, heads, c, _code(dt), 1, pooled)
+        h1, y2, y3, qy = _head_chain_fwd(table, ids, pts32, q32, k, wx32, w2_32, _f32(b2), w3_32, _f32(b3), wq32, _f32(bq))
+        pooled = torch.empty((nq, c), device=table.device, dtype=table.dtype)
+        _lib.call('pps_attn_pool_fwd', qy, y3, nq, k, heads, c, _code(table.dtype), 1, pooled)
         ctx.save_for_backward(ids, pts32, q32, w2_32, w3_32, wq32, h1, y2, y3, qy)
         ctx.meta = (table.shape[0], k, wx.dtype, tuple(wx.shape), w2.dtype, w3.dtype, wq.dtype, None if b2 is None else b2.dtype,
                     None if b3 is None else b3.dtype, None if bq is None else bq.dtype)
@@ -997,41 +974,43 @@ class _HeadChain(torch.autograd.Function):
     def backward(ctx, dpooled):
         ids, pts32, q32, w2_32, w3_32, wq32, h1, y2, y3, qy = ctx.saved_tensors
         n, k, wxdt, wxshape, w2dt, w3dt, wqdt, b2dt, b3dt, bqdt = ctx.meta
-        L = _lib.lib()
         rows, c = y3.shape
         heads = wq32.shape[0]
         dev, dt = y3.device, y3.dtype
         code = _code(dt)
         dpooled = dpooled.to(dt).contiguous()
         # attention pooling + fc_query: the two gradients of y3 are summed inside fc_query's input-gradient kernel
-        f32e = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-        dwq, dbq = f32e(heads, c), (f32e(heads) if bqdt is not None else None)
-        ws = torch.empty((L.pps_rows_layer_ws_bytes(c, c),), device=dev, dtype=torch.uint8)        # (the largest of the three layers)
+        dwq, dbq = _empty32(dev, heads, c), (_empty32(dev, heads) if bqdt is not None else None)
+        ws = _ws(_lib.lib().pps_rows_layer_ws_bytes(c, c), dev)        # (the largest of the three layers)
         dy3 = _query_attn_bwd(y3, qy, dpooled, wq32, k, dwq, dbq, ws)
         # fc3
         dy2 = torch.empty_like(y2)
-        dw3, db3 = f32e(c, c), (f32e(c) if b3dt is not None else None)
+        dw3, db3 = _empty32(dev, c, c), (_empty32(dev, c) if b3dt is not None else None)
         _lib.call('pps_rows_layer_bwd', y2, y3, dy3, rows, c, c, code, None, None, 1, w3_32, None, None, None, dy2, None, None, dw3, db3, None, None, ws)
         del dy3
         # fc2
         dh1 = torch.empty_like(h1)
-        dw2, db2 = f32e(c, c), (f32e(c) if b2dt is not None else None)
+        dw2, db2 = _empty32(dev, c, c), (_empty32(dev, c) if b2dt is not None else None)
         _lib.call('pps_rows_layer_bwd', h1, y2, dy2, rows, c, c, code, None, None, 1, w2_32, None, None, None, dh1, None, None, dw2, db2, None, None, ws)
         del dy2
         # head input: d table by the segmented sum of the gather, d wx
-        dtable = dwx = None
-        if ctx.needs_input_grad[0]:
-            order, offsets = csr(ids, n)
-            dt32 = f32e(n, c)
-            _lib.call('pps_segment_sum_rows_16', dh1, order, offsets, n, c, code, dt32)
-            dtable = dt32.to(dt)
-        if ctx.needs_input_grad[5]:
-            dwx = f32e(c, 3)
-            ws2 = torch.empty((L.pps_head_input_ws_bytes(c),), device=dev, dtype=torch.uint8)
-            _lib.call('pps_head_input_dwx', dh1, ids, pts32, q32, q32.shape[0], k, c, code, dwx, ws2)
-            dwx = dwx.reshape(wxshape).to(wxdt)
+        dtable, dwx = _head_input_bwd(dh1, ids, pts32, q32, n, k, wxshape, wxdt, ctx.needs_input_grad[0], ctx.needs_input_grad[5])
         cast = lambda t, d: None if (t is None or d is None) else t.to(d)
         return (dtable, None, None, None, None, dwx, dw2.to(w2dt), cast(db2, b2dt), dw3.to(w3dt), cast(db3, b3dt), dwq.to(wqdt), cast(dbq, bqdt))
+
+
+def _head_chain_fwd(table, ids, pts32, q32, k, wx32, w2_32, b2_32, w3_32, b3_32, wq32, bq32):
+    """The one launch of pps_head_chain_fwd -> (h1, y2, y3 [Q*k, C], qy [Q*k, heads]) in table's type.  The kernel writes whole 256-row units
+    (unconditional stores): padded storage, views of the rows -- the padding is never read, so it is not cleared."""
+    nq, c, heads = q32.shape[0], table.shape[1], wq32.shape[0]
+    dev, dt = table.device, table.dtype
+    rows = nq * k
+    pad = (rows + 255) // 256 * 256
+    h1, y2, y3 = (torch.empty((pad, c), device=dev, dtype=dt)[:rows] for _ in range(3))
+    qy = torch.empty((pad, heads), device=dev, dtype=dt)[:rows]
+    ws = _ws(_lib.lib().pps_head_chain_ws_bytes(), dev)
+    _lib.call('pps_head_chain_fwd', table, ids, pts32, q32, nq, k, _code(dt), wx32, w2_32, b2_32, w3_32, b3_32, wq32, bq32, h1, y2, y3, qy, ws)
+    return h1, y2, y3, qy
 
 
 def head_chain_supported(c, heads, k):
@@ -1062,20 +1041,10 @@ def head_chain_trusted(dtype):
     pts, query = (torch.rand(n, 3, generator=g) - 0.5).to(dev), (torch.rand(nq, 3, generator=g) - 0.5).to(dev)
     wx, w2, w3, wq = r(256, 3, scale=0.5), r(256, 256, scale=1 / 16), r(256, 256, scale=1 / 16), r(64, 256, scale=1 / 8)
     b2, b3, bq = r(256, scale=0.1), r(256, scale=0.1), r(64, scale=0.1)
-    L = _lib.lib()
     rows = nq * k
-    pad = (rows + 255) // 256 * 256
-
-    def chain():
-        h1, y2, y3 = (torch.zeros((pad, 256), device=dev, dtype=dtype) for _ in range(3))
-        qy = torch.zeros((pad, 64), device=dev, dtype=dtype)
-        ws = torch.empty((L.pps_head_chain_ws_bytes(),), device=dev, dtype=torch.uint8)
-        _lib.call('pps_head_chain_fwd', table, ids, pts, query, nq, k, _code(dtype), wx, w2, b2, w3, b3, wq, bq, h1, y2, y3, qy, ws)
-        return h1[:rows], y2[:rows], y3[:rows], qy[:rows]
-
     with torch.no_grad(), torch.autocast('cuda', dtype=dtype):
-        a = chain()
-        b = chain()
+        a = _head_chain_fwd(table, ids, pts, query, k, wx, w2, b2, w3, b3, wq, bq)
+        b = _head_chain_fwd(table, ids, pts, query, k, wx, w2, b2, w3, b3, wq, bq)
         h1 = head_input(table, ids, pts, query, k, wx)
         y2 = rows_layer(Act(h1, None, True), w2, b2, None, True)
         y3 = rows_layer(y2, w3, b3, None, True)

@@ -159,14 +159,18 @@ def test_every_call_site_names_a_declared_entry():
 
 
 def test_every_call_site_passes_as_many_arguments_as_the_entry_declares():
-    checked = 0
+    """(97 sites since train_ops.py calls each rows-layer / head entry from one place, 104 before; a site with a starred argument cannot be
+    counted: there are three, none of them in train_ops.py, and no more may appear)"""
+    checked, starred = 0, []
     for path in sorted(glob.glob(os.path.join(REPO, 'ppsurf_amd', '*.py'))):
         for node in ast.walk(ast.parse(open(path).read())):
             if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'call' and node.args
-                    and isinstance(node.args[0], ast.Constant) and str(node.args[0].value).startswith('pps_')
-                    and not any(isinstance(a, ast.Starred) for a in node.args)):
+                    and isinstance(node.args[0], ast.Constant) and str(node.args[0].value).startswith('pps_')):
+                if any(isinstance(a, ast.Starred) for a in node.args):
+                    starred.append(os.path.basename(path))
+                    continue
                 name = node.args[0].value
                 declared = len(_lib.PARAMS[name]) - (_lib.PARAMS[name][-1:] == ['stream'])
                 assert len(node.args) - 1 == declared, '{}:{}: {} takes {} arguments besides the stream'.format(path, node.lineno, name, declared)
                 checked += 1
-    assert checked > 100
+    assert checked > 90 and len(starred) <= 3 and 'train_ops.py' not in starred

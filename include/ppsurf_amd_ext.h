@@ -302,6 +302,65 @@ int ppsx_decimate_move(const int64_t* win, int64_t nw, const int32_t* src, const
                        int32_t* rename, void* stream);
 int ppsx_decimate_rename(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* rename, int64_t* out, uint8_t* keep, void* stream);
 
+/* ---- orientation: coherent, outward winding per component (csrc/pps_orient.hip) -----------------------------------------------------------
+ * new capability: replaces nothing -- the reference has no such stage and every other stage takes the winding as it comes.  Driven by
+ * ppsurf_amd/orient.py (the pairs and their edge slots by ppsurf_amd/topology.py); the rule and the argument for the labelling with a
+ * parity are written out at the top of csrc/pps_orient.hip and in DESIGN.md section 23.  Pairs: fa, fb int32 [np] the two valid faces on an
+ * edge that exactly two valid faces hold, ea, eb int32 [np] the slot of that edge in each (slot k is corner k -> corner k + 1 mod 3).
+ * word int64 [nf]: (parent << 1) | flip relative to the parent, -1 for an invalid face; word[f] = f << 1 to begin with.  A pair with an entry
+ * outside [0, nf), a slot outside [0, 3) or onto a face with a negative word is skipped, never read through.
+ *   ppsx_orient_pair_sign   sign u8 [np]: 1 when faces[fa][ea] == faces[fb][eb] (both run the edge the same way: one of them must turn),
+ *                           else 0; 0 for a skipped pair.  Every row is written.
+ *                           np or nf < 0 or > 2^31 - 1, or -- with np > 0 -- a NULL fa, fb, ea, eb or sign or a NULL faces with nf > 0:
+ *                           PPS_ERR_ARG, nothing is launched or written.  np == 0: 0, nothing is launched.
+ *   ppsx_orient_hook        one hooking round: a pair walks word from a and from b -- a walk steps from x to its parent p while
+ *                           0 <= p < x and XORs the flips -- to the ends (ra, qa), (rb, qb); when ra != rb:
+ *                           atomicMin(&word[max(ra, rb)], (min(ra, rb) << 1) | (qa ^ qb ^ sign)) and 1 is stored to *changed (int32, device;
+ *                           the caller zeroes it before).  Every word is read by one relaxed device-scope atomic load; no read relies on a
+ *                           write of the same launch; see the .hip file.
+ *                           np or nf < 0 or > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is launched or
+ *                           written.  np == 0 or nf == 0: 0, nothing is launched.
+ *   ppsx_orient_compress    every face f with word[f] >= 0 stores (the end of its walk << 1) | the flip accumulated on it in word[f]; a face
+ *                           with a negative word is not touched.  A walk reads no slot outside [0, f] and takes at most f steps.
+ *                           nf < 0, nf > 2^31 - 1 or a NULL word with nf > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0,
+ *                           nothing is launched.
+ *   ppsx_orient_check       after the fixed point (word[f] = (leader << 1) | flip): a pair with (flip[a] ^ flip[b]) != sign stores 1 to
+ *                           bad[leader of a] (u8 [nf], zeroed by the caller; the same value from every thread).  Which pairs of a
+ *                           non-orientable component fail depends on timing, that one fails does not.
+ *                           np or nf < 0 or > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is launched or
+ *                           written.  np == 0 or nf == 0: 0, nothing is launched.
+ *   ppsx_orient_block_sums  sums f64 [nb]: block i covers count[i] (int32, 1..256) positions of list int32 [nl] from first[i] (int64), faces
+ *                           of one component in ascending index, and lead[i] (int32) is that component's leader.  R = the first corner of
+ *                           face lead[i], q_k = double(P_k) - double(R), the term of a face on its corners as given is
+ *                           ((q0x (q1y q2z - q1z q2y)) + (q0y (q1z q2x - q1x q2z))) + (q0z (q1x q2y - q1y q2x)), negated when flip[f] (u8 [nf])
+ *                           is 1; +0.0 for an absent position, an invalid face or an index out of range.  One wave per block: lane l adds
+ *                           the terms of positions 4 l .. 4 l + 3 in order from +0.0, then S[l] = S[l] + S[l + s] for s = 1, 2, 4, 8, 16, 32,
+ *                           and lane 0 stores.  fp64, every operation rounded on its own.  A block whose first, count or lead is out of
+ *                           range gets +0.0.  Every row is written.
+ *                           nb, nl, nv or nf < 0 or > 2^31 - 1, or -- with nb > 0 -- a NULL first, count, lead or sums, a NULL list with
+ *                           nl > 0, a NULL faces or flip with nf > 0, a NULL verts with nv > 0: PPS_ERR_ARG, nothing is launched or
+ *                           written.  nb == 0: 0, nothing is launched.
+ *   ppsx_orient_comp_sums   vol f64 [nc]: the block sums start[c] .. start[c + 1] - 1 (start int64 [nc + 1]) added in ascending order from
+ *                           +0.0; +0.0 for a row that is not 0 <= start[c] <= start[c + 1] <= nb.  One thread per component.
+ *                           nc or nb < 0 or > 2^31 - 1, or -- with nc > 0 -- a NULL start or vol or a NULL sums with nb > 0: PPS_ERR_ARG,
+ *                           nothing is launched or written.  nc == 0: 0, nothing is launched.
+ *   ppsx_orient_apply       out int64 [nf,3]: face (a, b, c) as (a, c, b) when cid[f] (int32 [nf]) lies in [0, nc) and turn[cid[f]]
+ *                           (u8 [nc]) is 1 with flip[f] == 1 or 2 with flip[f] == 0; every other row is copied as it is.  Every row is written.
+ *                           nf or nc < 0 or > 2^31 - 1, out == faces, or -- with nf > 0 -- a NULL faces, cid, flip or out or a NULL turn with
+ *                           nc > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched. */
+int ppsx_orient_pair_sign(const int64_t* faces, int64_t nf, const int32_t* fa, const int32_t* fb, const int32_t* ea, const int32_t* eb,
+                          int64_t np, uint8_t* sign, void* stream);
+int ppsx_orient_hook(const int32_t* fa, const int32_t* fb, const uint8_t* sign, int64_t np, int64_t* word, int64_t nf, int32_t* changed,
+                     void* stream);
+int ppsx_orient_compress(int64_t* word, int64_t nf, void* stream);
+int ppsx_orient_check(const int32_t* fa, const int32_t* fb, const uint8_t* sign, int64_t np, const int64_t* word, int64_t nf, uint8_t* bad,
+                      void* stream);
+int ppsx_orient_block_sums(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const uint8_t* flip, const int32_t* list,
+                           int64_t nl, const int64_t* first, const int32_t* count, const int32_t* lead, int64_t nb, double* sums, void* stream);
+int ppsx_orient_comp_sums(const double* sums, int64_t nb, const int64_t* start, int64_t nc, double* vol, void* stream);
+int ppsx_orient_apply(const int64_t* faces, int64_t nf, const int32_t* cid, const uint8_t* flip, const uint8_t* turn, int64_t nc, int64_t* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """The topology layer of the mesh stages: faces -> sorted keys -> row tables, and the checks on a mesh argument.
 
-smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19) and pieces.py its
-face pairs (section 21); the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
+smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
+face pairs (section 21) and orient.py the same pairs with their edge slots (section 23); the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
 """
 import torch
@@ -84,23 +84,31 @@ def rim_rows(faces, nv, offsets, nbr, mult):
     return succ, cand, int(keys.shape[0]), int(((leave > 0) | (enter > 0)).sum().item()), int(cand.shape[0])
 
 
-def manifold_pairs(faces, nv):
-    """(fa int32 [np], fb int32 [np], valid bool [nf]) of contiguous device faces: the pairs of valid faces that share an undirected edge
+def manifold_pair_edges(faces, nv):
+    """(fa, fb, ea, eb int32 [np], valid bool [nf]) of contiguous device faces: the pairs of valid faces that share an undirected edge
     which exactly two valid faces hold (an edge with one owner or with three and more gives no pair, a duplicated face
-    is two faces), and which faces are valid.  ppsx_pieces_edge_keys writes 3 keys per face, (min << 32) | max, one sort with indices puts
-    equal edges side by side, and the runs of exactly two give the pairs; the owner of a key is its position // 3.  The pairs are a set:
-    their order, and which owner comes first, follow the sort."""
+    is two faces), the slot of that edge in each face (slot k is corner k -> corner k + 1 mod 3; section 23), and which faces are valid.
+    ppsx_pieces_edge_keys writes 3 keys per face, (min << 32) | max, one sort with indices puts equal edges side by side, and the runs of
+    exactly two give the pairs; the owner of a key is its position // 3 and its slot the position % 3, so two copies of one triangle are
+    three pairs with their own slots.  The pairs are a set: their order, and which owner comes first, follow the sort."""
     nf = int(faces.shape[0])
     keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
     if nf == 0:
-        return keys.to(torch.int32), keys.to(torch.int32), keys.bool()
+        none = keys.to(torch.int32)
+        return none, none, none, none, keys.bool()
     _lib.call('ppsx_pieces_edge_keys', faces, nf, nv, keys)
     valid = keys[0::3] != SENTINEL
     keys, order = torch.sort(keys)
     uniq, counts = torch.unique_consecutive(keys, return_counts=True)
     first = (torch.cumsum(counts, 0) - counts)[(counts == 2) & (uniq != SENTINEL)]
-    owner = order // 3
-    return owner[first].to(torch.int32), owner[first + 1].to(torch.int32), valid
+    one, two = order[first], order[first + 1]
+    return (one // 3).to(torch.int32), (two // 3).to(torch.int32), (one % 3).to(torch.int32), (two % 3).to(torch.int32), valid
+
+
+def manifold_pairs(faces, nv):
+    """(fa int32 [np], fb int32 [np], valid bool [nf]) of contiguous device faces: manifold_pair_edges without the slots."""
+    fa, fb, _, _, valid = manifold_pair_edges(faces, nv)
+    return fa, fb, valid
 
 
 def mesh_adjacency(faces: torch.Tensor, nv: int):

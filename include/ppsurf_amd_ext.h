@@ -361,6 +361,41 @@ int ppsx_orient_comp_sums(const double* sums, int64_t nb, const int64_t* start, 
 int ppsx_orient_apply(const int64_t* faces, int64_t nf, const int32_t* cid, const uint8_t* flip, const uint8_t* turn, int64_t nc, int64_t* out,
                       void* stream);
 
+/* ---- weld: coincident and close vertices become one row (csrc/pps_weld.hip) ---------------------------------------------------------------
+ * new capability: replaces nothing -- the reference has no such stage, and pps_mesh_corner_weld stays the weld of Marching Cubes in its own
+ * grid index space.  Driven by ppsurf_amd/weld.py (the cell lists by trim.SupportGrid: ppsx_trim_cell_slots, a sort, ops.row_offsets); the
+ * rule and the argument for the labelling are written out at the top of csrc/pps_weld.hip and in DESIGN.md section 24.  Rows i != j of
+ * pts f32 [n,3] are linked when ((dx dx + dy dy) + dz dz) <= eps * eps in fp64 on the widened f32, every operation rounded on its own; a
+ * cluster is a connected component of the links and its leader is its smallest row.  lo, hi, h, inv_h, table, capacity, order, offsets are
+ * those of ppsx_trim_cell_slots and ppsx_trim_face_support over the same pts; no result depends on them.
+ *   ppsx_weld_hook      one hooking round on label int32 [n] (label[v] = v to begin with): vertex i visits the rows j < i of the cells its
+ *                       box p_i -+ eps (1 + 2^-20), rounded outward to f32, reaches -- of all rows below i when that range holds more cells
+ *                       than n -- and for every linked j walks label from i and from j -- a walk steps from x to label[x] while
+ *                       0 <= label[x] < x -- to the ends ri, rj; when ri != rj: atomicMin(&label[max], min), and 1 is stored to *changed
+ *                       (int32, device; the caller zeroes it before) when that made the label fall.  A vertex with a negative label
+ *                       takes no part: it is skipped as i and as j.  Every label is read by one relaxed device-scope atomic load; no
+ *                       read relies on a write of the same launch; see the .hip file.  A label outside [0, x] ends a walk at x, an order
+ *                       entry outside [0, i) is skipped and a row of offsets that is not 0 <= o0 <= o1 <= n is taken as empty; none is
+ *                       read through.
+ *                       n < 0, n > 2^31 - 1, eps negative or NaN, or -- with n > 0 -- a NULL pointer, a capacity that is no power of two
+ *                       > n or a grid that make_grid of pps_cells.h refuses: PPS_ERR_ARG, nothing is launched or written.  n == 0: 0,
+ *                       nothing is launched.
+ *   ppsx_weld_compress  every vertex v with label[v] >= 0 stores the end of its walk in label[v]; one with a negative label is not touched.  A walk reads no slot outside [0, v] and takes at most v
+ *                       steps.
+ *                       n < 0, n > 2^31 - 1 or a NULL label with n > 0: PPS_ERR_ARG, nothing is launched or written.  n == 0: 0, nothing
+ *                       is launched.
+ *   ppsx_weld_faces     out int64 [nf,3], code u8 [nf] from faces int64 [nf,3] and newrow int64 [nv] (newrow[v] = the output row of v's
+ *                       leader).  code 1: the face is invalid as given -- an index outside [0, nv) or two equal indices -- or one of its
+ *                       newrow entries lies outside [0, nv); code 2: valid as given and two of its new indices are equal; code 0: kept,
+ *                       out = (newrow[a], newrow[b], newrow[c]).  A face with code != 0 gets its row copied as given and an invalid face is
+ *                       never read through.  Every row of both outputs is written.
+ *                       nf or nv < 0 or > 2^31 - 1, out == faces, or -- with nf > 0 -- a NULL faces, out or code or a NULL newrow with
+ *                       nv > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched. */
+int ppsx_weld_hook(const float* pts, int64_t n, const float* lo, const float* hi, float h, float inv_h, const uint64_t* table, int64_t capacity,
+                   const int64_t* order, const int64_t* offsets, double eps, int32_t* label, int32_t* changed, void* stream);
+int ppsx_weld_compress(int32_t* label, int64_t n, void* stream);
+int ppsx_weld_faces(const int64_t* faces, int64_t nf, int64_t nv, const int64_t* newrow, int64_t* out, uint8_t* code, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

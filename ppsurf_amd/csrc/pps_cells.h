@@ -1,5 +1,6 @@
-// The cell grid and its table, shared by the voxel stage of raw scans (pps_cloud.hip, T = float) and the vertex clustering of meshes
-// (pps_simplify.hip, T = double); DESIGN.md section 12.  Restated in numpy by tests/grid_spec.py.
+// The cell grid and its table, shared by the voxel stage of raw scans (pps_cloud.hip, T = float), the vertex clustering of meshes
+// (pps_simplify.hip, T = double) and the cell lists of the trim and the weld (pps_trim.hip, pps_weld.hip, T = float; find_run);
+// DESIGN.md section 12.  Restated in numpy by tests/grid_spec.py.
 //
 // Grid over the box lo..hi with step h (h and inv_h = 1 / h come from the host), every operation in T and rounded on its own
 // (-ffp-contract=off):
@@ -62,6 +63,24 @@ __device__ __forceinline__ u64 find_or_insert(u64* __restrict__ table, u64 mask,
         slot = (slot + 1) & mask;
     }
     return slot;
+}
+
+// Read-only: the run [j, jend) of the caller's `order` that lists the points of the cell `key`, from offsets int64 [capacity + 1] over a
+// table of n points.  The probe ends at the key or at an empty slot, after at most capacity tries; j and jend are left as they are when
+// the cell is not in the table or its offsets are not 0 <= o0 <= o1 <= n.
+__device__ __forceinline__ void find_run(const u64* __restrict__ table, u64 mask, u64 key, const int64_t* __restrict__ offsets, int64_t n,
+                                         int64_t& j, int64_t& jend) {
+    u64 s = mix64(key) & mask;
+    for (u64 tries = 0; tries <= mask; ++tries) {
+        const u64 seen = table[s];
+        if (seen == key) {
+            const int64_t o0 = offsets[s], o1 = offsets[s + 1];
+            if (o0 >= 0 && o0 <= o1 && o1 <= n) { j = o0; jend = o1; }
+            return;
+        }
+        if (seen == EMPTY) return;
+        s = (s + 1) & mask;
+    }
 }
 
 // count += number of lanes of this wave with `flag`; every lane of the wave must call it

@@ -109,18 +109,7 @@ __global__ __launch_bounds__(64 * FACES_PER_BLOCK) void face_support_kernel(cons
             } else if (cell < ncells) {                                                     // open the next cell: a read-only probe
                 const int cx = c0[0] + (int)(cell % cn[0]), cy = c0[1] + (int)((cell / cn[0]) % cn[1]);
                 const int cz = c0[2] + (int)(cell / ((int64_t)cn[0] * cn[1]));
-                const u64 key = cells::key_of(grid, cx, cy, cz);
-                u64 s = cells::mix64(key) & mask;
-                for (u64 tries = 0; tries <= mask; ++tries) {                               // ends at the key or at an empty slot
-                    const u64 seen = table[s];
-                    if (seen == key) {
-                        const int64_t o0 = offsets[s], o1 = offsets[s + 1];
-                        if (o0 >= 0 && o0 <= o1 && o1 <= n) { j = o0; jend = o1; }
-                        break;
-                    }
-                    if (seen == cells::EMPTY) break;
-                    s = (s + 1) & mask;
-                }
+                cells::find_run(table, mask, cells::key_of(grid, cx, cy, cz), offsets, n, j, jend);
                 cell += 64;
             }
             if (__any(hit) || !__any(j < jend || cell < ncells)) break;

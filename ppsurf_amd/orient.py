@@ -11,7 +11,7 @@ closed component is then turned so that its signed volume is positive (`outward`
 component in `majority` mode, keeps the winding of its larger half.  A component that cannot be oriented (a Moebius strip, a Klein
 bottle) comes back byte for byte and is counted.  The volume is summed in fp64 in a fixed order, so the result is a pure function of
 (verts, faces, mode).  The models have no switch for this stage: run the command on the PLY that `pps.py rec` wrote.  Vertices are never
-welded: a soup of unconnected triangles is one component per face and comes back unchanged.
+welded here: a soup of unconnected triangles is one component per face and comes back unchanged; run `python -m ppsurf_amd.weld` first.
 """
 import json
 import sys

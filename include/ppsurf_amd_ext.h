@@ -213,7 +213,8 @@ int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, 
  *                          np < 0, nf < 0, np or nf > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is
  *                          launched or written.  np == 0 or nf == 0: 0, nothing is launched.
  *   ppsx_pieces_compress   every face f with label[f] >= 0 stores the end of its walk in label[f]; a face with a negative label is not
- *                          touched.  A walk reads no slot outside [0, f] and takes at most f steps.
+ *                          touched.  A walk reads no slot outside [0, f] and takes at most f steps.  The entry is generic over int32
+ *                          labels of this kind: ppsurf_amd/manifold.py runs it on the 3 nf corner labels of section 25.
  *                          nf < 0, nf > 2^31 - 1 or a NULL label with nf > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0,
  *                          nothing is launched.
  *   ppsx_pieces_stats      count int64 [nc], lo, hi f32 [nc,3]: per component c the number of its faces and the box of their corners over
@@ -395,6 +396,37 @@ int ppsx_weld_hook(const float* pts, int64_t n, const float* lo, const float* hi
                    const int64_t* order, const int64_t* offsets, double eps, int32_t* label, int32_t* changed, void* stream);
 int ppsx_weld_compress(int32_t* label, int64_t n, void* stream);
 int ppsx_weld_faces(const int64_t* faces, int64_t nf, int64_t nv, const int64_t* newrow, int64_t* out, uint8_t* code, void* stream);
+
+/* ---- manifold split: many-owner edges and pinched vertices are cut apart by duplicating vertices (csrc/pps_manifold.hip) ------------------
+ * new capability: replaces nothing -- the reference has no such stage.  Driven by ppsurf_amd/manifold.py (the pairs and their edge slots
+ * by ppsurf_amd/topology.py); the rule, the argument for the labelling and the argument that the result is manifold are written out at the
+ * top of csrc/pps_manifold.hip and in DESIGN.md section 25.  Corner c = 3 f + k of a valid face f names the vertex faces[f][k]; label
+ * int32 [3 nf] holds one entry per corner, label[c] = c to begin with and -1 for a corner of an invalid face.  The compress launch between
+ * two hooks is ppsx_pieces_compress(label, 3 nf).
+ *   ppsx_manifold_hook   one hooking round over the pairs fa, fb, ea, eb int32 [np] (the two valid faces on an edge that exactly two valid
+ *                        faces hold and the slot of that edge in each; slot k is corner k -> corner k + 1 mod 3).  One thread per pair reads
+ *                        the four corners of the two slots from faces int64 [nf,3]: when both slots name the same two vertices, the corner
+ *                        of fa and the corner of fb that name one end are joined, and likewise for the other end -- slot to slot when both
+ *                        faces run the edge the same way, crossed when they run it in opposite ways.  Joining x and y: walk label from x
+ *                        and from y -- a walk steps from x to label[x] while 0 <= label[x] < x -- to the ends rx, ry; when rx != ry:
+ *                        atomicMin(&label[max], min), and 1 is stored to *changed (int32, device; the caller zeroes it before) when that
+ *                        made the label fall.  A pair with a face outside [0, nf), a slot outside [0, 3), a corner vertex outside [0, nv)
+ *                        or slots that name no common edge is skipped; a join onto a corner with a negative label is skipped; none is
+ *                        read through.  Every label is read by one relaxed device-scope atomic load; no read relies on a write of the
+ *                        same launch; see the .hip file.
+ *                        nf, nv or np < 0 or > 2^31 - 1, 3 nf > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG,
+ *                        nothing is launched or written.  np == 0 or nf == 0: 0, nothing is launched.
+ *   ppsx_manifold_faces  out int64 [nf,3] from faces int64 [nf,3], label int32 [3 nf] and newrow int64 [3 nf] (newrow[l] = the output row
+ *                        of the fan whose leader is corner l): corner c of a face that is valid as given with label[c] >= 0 becomes
+ *                        newrow[label[c]], one with a negative label keeps its entry.  A face that is invalid as given -- an index outside
+ *                        [0, nv) or two equal indices -- is copied as given and not read through, and so is a face with a label >= 3 nf or
+ *                        with a new entry outside [0, nv_out).  Every row of out is written.
+ *                        nf, nv or nv_out < 0 or > 2^31 - 1, 3 nf > 2^31 - 1, out == faces, or -- with nf > 0 -- a NULL pointer:
+ *                        PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched. */
+int ppsx_manifold_hook(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* fa, const int32_t* fb, const int32_t* ea, const int32_t* eb,
+                       int64_t np, int32_t* label, int32_t* changed, void* stream);
+int ppsx_manifold_faces(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* label, const int64_t* newrow, int64_t nv_out, int64_t* out,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,7 @@
 
 #include "pps_common.h"
 #include "pps_faces.h"
+#include "pps_labels.h"
 #include "../../include/ppsurf_amd_ext.h"
 
 namespace {
@@ -75,19 +76,6 @@ __device__ __forceinline__ int image_of(float x) {
 }
 
 __device__ __forceinline__ float float_of(int image) { return __int_as_float(image >= 0 ? image : image ^ 0x7FFFFFFF); }
-
-__device__ __forceinline__ int load_label(const int32_t* label, int64_t x) {
-    return __hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the end of the walk from x (0 <= x < nf, by the caller): it steps to label[x] while 0 <= label[x] < x
-__device__ __forceinline__ int walk_end(const int32_t* label, int x) {
-    for (;;) {
-        const int p = load_label(label, x);
-        if (p < 0 || p >= x) return x;
-        x = p;
-    }
-}
 
 __global__ __launch_bounds__(256) void edge_keys_kernel(const int64_t* __restrict__ faces, int64_t nf, int64_t nv, int64_t* __restrict__ keys) {
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;

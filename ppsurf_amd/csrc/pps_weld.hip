@@ -55,25 +55,13 @@
 
 #include "pps_cells.h"
 #include "pps_faces.h"
+#include "pps_labels.h"
 #include "../../include/ppsurf_amd_ext.h"
 
 namespace {
 
 using cells::u64;
 typedef cells::Grid<float> Grid;
-
-__device__ __forceinline__ int load_label(const int32_t* label, int64_t x) {
-    return __hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the end of the walk from x (0 <= x < n, by the caller): it steps to label[x] while 0 <= label[x] < x
-__device__ __forceinline__ int walk_end(const int32_t* label, int x) {
-    for (;;) {
-        const int p = load_label(label, x);
-        if (p < 0 || p >= x) return x;
-        x = p;
-    }
-}
 
 struct Query {
     double x, y, z, eps2;

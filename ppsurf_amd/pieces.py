@@ -49,6 +49,12 @@ def _checked_rules(min_faces, min_diag_frac, keep_largest):
     return min_faces, min_diag_frac, keep_largest
 
 
+def compress_labels(label, n):
+    """Every slot of label int32 [n] with a label >= 0 gets the end of its descending walk (ppsx_pieces_compress): the step between two
+    hooking rounds, here on face labels and in manifold.py on corner labels."""
+    _lib.call('ppsx_pieces_compress', label, n)
+
+
 def _labels(f, nv):
     """(label int32 [nf], valid bool [nf], rounds) of contiguous device faces: hooking and compressing until a hook launch changes nothing.
     The rounds depend on the face order and on timing; the labels do not."""
@@ -65,7 +71,7 @@ def _labels(f, nv):
             rounds += 1
             if int(changed.item()) == 0:
                 break
-            _lib.call('ppsx_pieces_compress', label, nf)
+            compress_labels(label, nf)
     return label, valid, rounds
 
 

@@ -1,7 +1,8 @@
 """The topology layer of the mesh stages: faces -> sorted keys -> row tables, and the checks on a mesh argument.
 
 smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
-face pairs (section 21) and orient.py the same pairs with their edge slots (section 23); the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
+face pairs (section 21), orient.py the same pairs with their edge slots (section 23) and manifold.py those pairs and slots once more,
+with the owner count of every edge (section 25); the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
 """
 import torch
@@ -91,16 +92,30 @@ def manifold_pair_edges(faces, nv):
     ppsx_pieces_edge_keys writes 3 keys per face, (min << 32) | max, one sort with indices puts equal edges side by side, and the runs of
     exactly two give the pairs; the owner of a key is its position // 3 and its slot the position % 3, so two copies of one triangle are
     three pairs with their own slots.  The pairs are a set: their order, and which owner comes first, follow the sort."""
+    return pairs_of_runs(*edge_runs(faces, nv))
+
+
+def edge_runs(faces, nv):
+    """(order int64 [3 nf], first int64 [ne], owners int64 [ne], valid bool [nf]) of contiguous device faces: the ne distinct undirected
+    edges of the valid faces in ascending key.  ppsx_pieces_edge_keys writes 3 keys per face, (min << 32) | max, and one sort with indices
+    puts equal edges side by side: edge e is the sorted positions first[e] .. first[e] + owners[e] - 1, and order gives the unsorted
+    position of each, whose owner is position // 3 and whose slot is position % 3.  owners == 1 is a border edge, 2 a manifold one, 3 and
+    more a non-manifold one (section 25 counts them).  Where there are invalid faces their SENTINEL keys form one more run at the end,
+    with owners 0, so that no compaction (and no synchronisation) is spent on it here."""
     nf = int(faces.shape[0])
     keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
     if nf == 0:
-        none = keys.to(torch.int32)
-        return none, none, none, none, keys.bool()
+        return keys, keys, keys, keys.bool()
     _lib.call('ppsx_pieces_edge_keys', faces, nf, nv, keys)
     valid = keys[0::3] != SENTINEL
     keys, order = torch.sort(keys)
     uniq, counts = torch.unique_consecutive(keys, return_counts=True)
-    first = (torch.cumsum(counts, 0) - counts)[(counts == 2) & (uniq != SENTINEL)]
+    return order, torch.cumsum(counts, 0) - counts, torch.where(uniq != SENTINEL, counts, torch.zeros_like(counts)), valid
+
+
+def pairs_of_runs(order, first, owners, valid):
+    """manifold_pair_edges from the edge_runs of the same faces: the runs of exactly two."""
+    first = first[owners == 2]
     one, two = order[first], order[first + 1]
     return (one // 3).to(torch.int32), (two // 3).to(torch.int32), (one % 3).to(torch.int32), (two % 3).to(torch.int32), valid
 

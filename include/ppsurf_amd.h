@@ -207,7 +207,9 @@ int pps_decode_tail_f32(const float* pooled, const float* xbar, int64_t q, const
  * feat_rows (wpack, bias), tail (wpack, bias) -- layouts as documented at the single entry points;
  * logits out [q,2]; occ out [q] or NULL; ws: pps_decode_ws_bytes(q) bytes of device scratch, ZEROED once by the caller before its first use
  * (its first 64 bytes hold the range-guard words of pps_decode_fwd_mixed_f32: int32 [0] = flag of the chunk in flight, [1] = number of chunks
- * recomputed in fp32 so far). */
+ * recomputed in fp32 so far; [2..15] are the tile-claim words of include/ppsurf_amd_ext.h.  ALL 64 bytes must be zero before the first call;
+ * the kernels return words 2..15 to zero and nothing re-zeroes them at entry, so they must never be written by the caller or copied from a
+ * workspace that has a call in flight: non-zero claim words make a call skip queries.  One workspace serves one stream at a time). */
 size_t pps_decode_ws_bytes(int64_t q);
 int pps_decode_fwd_f32(const float* table, const float* pts, const float* query, const int64_t* idx, int64_t q, int k,
                        const float* patches, int p, const float* const* weights, float* logits, float* occ, void* ws, void* stream);

@@ -428,6 +428,24 @@ int ppsx_manifold_hook(const int64_t* faces, int64_t nf, int64_t nv, const int32
 int ppsx_manifold_faces(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* label, const int64_t* newrow, int64_t nv_out, int64_t* out,
                         void* stream);
 
+/* ---- tile claims of the split-precision decoder (csrc/pps_decode.hip, csrc/pps_common.h) ---------------------------------------------------------
+ * changes no entry: inside pps_decode_fwd_mixed_f32 the persistent split-precision kernels take their next unit of work from counters in the
+ * head of the workspace `ws` instead of walking a fixed share of the units.  int32 words of that head: [0] range flag, [1] fall-back count (as
+ * before), [2] workgroups of the kernel in flight that are done, [3..10] the interpolation kernel's counters (one per XCD range), [11] STN rows,
+ * [12] STN head, [13] fc3 + feature rows, [14] tail.  The caller zeroes the head once, as before; every kernel leaves words 2..14 at zero.  The
+ * single entries (pps_interp_pool_f16x3, pps_pointnet_f16x3, pps_decode_tail_f16x3) keep the fixed share.  A query's results do not depend on
+ * the unit or the workgroup that evaluates it.  Environment, read per call: PPS_TILE_CLAIMS=0 keeps the fixed share everywhere; a number selects
+ * kernels by bit (1 interpolation, 2 STN rows, 4 STN head, 8 fc3 + feature rows, 16 tail).
+ *   ppsx_decode_units  HOST function, launches nothing; units, count are HOST pointers.  Lists the units of kernel 0 interp_pool_f16x3,
+ *                      1 pointnet_stn_rows (split precision, one launch), 2 pointnet_stn_head_h, 3 pointnet_fc3_feat_rows, 4 decode_tail_h for
+ *                      q queries with patches of p points on a chip that holds wgs workgroups of that kernel, in the order the counters hand
+ *                      them out, computed by the functions the kernels call: units int64 [capacity,3] = (first query, query count, mode);
+ *                      mode is patch_packing's for STN rows (1: packed wave groups, only among the queries below the split point, which is
+ *                      the whole rounds over wgs workgroups; 2: the packed arithmetic, one query per wave; 0: padded tiles) and 0 elsewhere.
+ *                      *count = the number of units; at most `capacity` of them are written.
+ *                      kernel outside 0..4, q < 0, p < 1, wgs < 1, capacity < 0, count NULL, or units NULL with capacity > 0: PPS_ERR_ARG. */
+int ppsx_decode_units(int kernel, int64_t q, int p, int wgs, int64_t* units, int64_t capacity, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,9 +50,12 @@ _entries = None        # name -> (function, takes a stream): what `call` needs o
 _ext_entries = {}      # the same for the extension entries, filled by lib(): empty while something else installs _entries directly
 
 
-def _bind(handle, signatures, params):
+def _bind(handle, signatures, params, optional=False):
+    """optional: an entry the library does not export is left out instead of raised (a PPS_LIB_VARIANT library built from an older tree)"""
     entries = {}
     for name, (res, args) in signatures.items():
+        if optional and not hasattr(handle, name):
+            continue
         fn = getattr(handle, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -73,7 +76,9 @@ def lib():
                            'There is no CPU fallback.'.format(LIB_PATH))
         handle = ctypes.CDLL(LIB_PATH)
         _entries = bind(handle)
-        _ext_entries = _bind(handle, EXT_SIGNATURES, EXT_PARAMS)
+        # a variant library (development aid, e.g. `--variant parent` built in a checkout of the parent commit and copied here for an A/B run)
+        # may predate an extension entry: calling that entry then fails as undeclared; the product library must export every one
+        _ext_entries = _bind(handle, EXT_SIGNATURES, EXT_PARAMS, optional=bool(os.environ.get('PPS_LIB_VARIANT')))
         _lib = handle
     return _lib
 

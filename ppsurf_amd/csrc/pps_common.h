@@ -480,4 +480,56 @@ __device__ __forceinline__ void xcd_tile_range(int ntiles, int& first, int& coun
     count = (hi - lo > slot) ? (hi - lo - slot + per - 1) / per : 0;
 }
 
+// ---- tile claims: a persistent workgroup takes its next tile from a counter in global memory instead of walking a fixed share ----------------
+// A fixed share makes the slowest workgroup the kernel's time, and a workgroup that starts late (the other chunk lane still holds its CU) runs a
+// full share behind everyone else.  With claims a workgroup takes tiles for as long as it runs.  The protocol, the same in every kernel:
+//   * the first tile of a workgroup is the one its fixed share starts with: no claim, so a launch does not open with one atomic per workgroup on one
+//     word (kernels of 30 us notice).  A counter therefore stands for the tiles BEHIND those first ones: what it returns is offset by their number;
+//   * thread 0 of the workgroup issues atomicAdd(counter, 1) at the HEAD of a trip for the trip after it, so the latency lies under the trip;
+//   * it stores the tile it got into one LDS word before a barrier the trip has anyway (not the first barrier of the trip: a slow wave may still
+//     be reading the word), and every wave reads the word behind that barrier.  Tile and exit condition are therefore the same value for all
+//     waves of the workgroup -- the loops hold workgroup barriers, a wave must never leave alone;
+//   * the counters live in the head of the decoder workspace (PPS_CLAIM_* words) and are zero between launches: every workgroup counts itself
+//     out when it leaves the loop (claim_finish), the last one clears the kernel's counters and the count.  All claims of the launch have returned
+//     by then, and the next kernel on the stream starts behind this one.
+// Head of the decoder workspace, int32 words: 0 range flag, 1 fall-back count (decode_fwd), then
+#define PPS_CLAIM_DONE 2           // workgroups of the kernel in flight that have left their loop
+#define PPS_CLAIM_INTERP 3         // .. 10: interp_pool_f16x3_kernel, one counter per XCD range
+#define PPS_CLAIM_STN_ROWS 11
+#define PPS_CLAIM_STN_HEAD 12
+#define PPS_CLAIM_FC3_FEAT 13
+#define PPS_CLAIM_TAIL 14
+
+// The cut of xcd_tile_range: `nwg` workgroups walk tile_ranges(nwg) contiguous ranges, range r = [lo, hi) of the ntiles tiles
+__host__ __device__ inline int tile_ranges(int nwg) { return ((nwg & 7) != 0 || nwg < 8) ? 1 : 8; }
+__host__ __device__ inline void tile_range_bounds(int ntiles, int nranges, int r, int& lo, int& hi) {
+    // (nranges is 1 or 8: no division -- thread 0 runs this inside a trip, with the other waves of the workgroup on their way to a barrier)
+    lo = nranges == 8 ? (int)(((int64_t)ntiles * r) >> 3) : 0;
+    hi = nranges == 8 ? (int)(((int64_t)ntiles * (r + 1)) >> 3) : ntiles;
+}
+
+// Thread 0's state of a ranged claim: the range it takes from (its XCD's first) and how many ranges it has not yet seen empty
+struct RangeClaim { int r, left; };
+// t = what atomicAdd(counters + rc.r, 1) returned; per = workgroups per range, each with the first tile lo + (its place in the range) unclaimed.
+// The tile t stands for; when the range is used up, the next range that still has one (a counter only grows, so a range seen empty stays empty:
+// at most nranges moves per workgroup); -1 when every range is used up.
+__device__ __forceinline__ int range_claim_resolve(int* counters, int ntiles, int nranges, int per, RangeClaim& rc, int t) {
+    for (;;) {
+        int lo, hi;
+        tile_range_bounds(ntiles, nranges, rc.r, lo, hi);
+        if (per + t < hi - lo) return lo + per + t;
+        if (--rc.left <= 0) return -1;
+        rc.r = (rc.r + 1 == nranges) ? 0 : rc.r + 1;
+        t = atomicAdd(counters + rc.r, 1);
+    }
+}
+
+// Behind the loop, all threads of the workgroup: see above
+__device__ __forceinline__ void claim_finish(int* done, int* counters, int ncounters) {
+    if (threadIdx.x == 0 && atomicAdd(done, 1) == (int)gridDim.x - 1) {
+        for (int i = 0; i < ncounters; ++i) atomicExch(counters + i, 0);
+        atomicExch(done, 0);
+    }
+}
+
 }  // namespace pps

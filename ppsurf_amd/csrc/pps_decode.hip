@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include "pps_common.h"
 #include "../../include/ppsurf_amd.h"
+#include "../../include/ppsurf_amd_ext.h"
 
 using namespace pps;
 
@@ -313,12 +314,16 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 static_assert(IH_OB == 2, "the weight pointer of the kernel's layer step wraps behind the step that fetches the last chunk: right for two output blocks per chunk only");
 #define IH_LDS_BYTES (2 * IH_CH4 * 16 + (IP_W_XYZ + IP_NBIAS + IH_NW * 64 * 3 + IH_NW * 256) * 4)
 
+// CLAIM: tiles are claimed (pps_common.h) from the words head[PPS_CLAIM_INTERP ..] of the decoder workspace instead of walked as a fixed share.
+// Every XCD keeps its contiguous query range (the G gather lives on that L2) with a counter of its own; a workgroup whose range is used up takes
+// from the next XCD's.  !CLAIM (head unused): the fixed share of xcd_tile_range.
+template <bool CLAIM>
 PPS_PLAIN_F32
 __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float* __restrict__ G, const float* __restrict__ pts,
                                                                      const float* __restrict__ query, const int64_t* __restrict__ idx,
                                                                      int64_t Q, int k, const float* __restrict__ wxyz,
                                                                      const f32x4* __restrict__ w16, const float* __restrict__ bias,
-                                                                     float* __restrict__ pooled, int* __restrict__ range) {
+                                                                     float* __restrict__ pooled, int* __restrict__ range, int* __restrict__ head) {
     float amax = 0.f;
     float* xyz_l = (float*)((f32x4*)pps_smem + 2 * IH_CH4);
     float* bias_l = xyz_l + IP_W_XYZ;
@@ -332,8 +337,28 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
 
     lds_fill(xyz_l, wxyz, IP_W_XYZ);
     lds_fill(bias_l, bias, IP_NBIAS);
+    // claims: thread 0 takes the first tile ahead of the barrier of stream_begin, which publishes it
+    int* slot = nullptr;              // LDS: [0] the tile of the next trip (-1: none left), [1], [2] thread 0's RangeClaim
+    int tile = 0, pend = 0;
+    if constexpr (CLAIM) {
+        __shared__ int claim_l[3];
+        slot = claim_l;
+        if (threadIdx.x == 0) {
+            // the first tile is the fixed share's (place b >> 3 in the range of XCD b & 7); a range with fewer tiles than workgroups: claim elsewhere
+            const int nt = (int)((Q + IH_NW / 4 - 1) / (IH_NW / 4)), nr = tile_ranges(gridDim.x), per = gridDim.x / nr;
+            const int place = nr == 1 ? (int)blockIdx.x : (int)(blockIdx.x >> 3);
+            RangeClaim rc = {nr == 1 ? 0 : (int)(blockIdx.x & 7), nr};
+            int lo, hi;
+            tile_range_bounds(nt, nr, rc.r, lo, hi);
+            slot[0] = place < hi - lo ? lo + place
+                                      : range_claim_resolve(head + PPS_CLAIM_INTERP, nt, nr, per, rc, atomicAdd(head + PPS_CLAIM_INTERP + rc.r, 1));
+            slot[1] = rc.r;
+            slot[2] = rc.left;
+        }
+    }
     f32x4 *cur, *nxt;
     stream_begin<IH_CH4, IH_CH4, IH_NT>(wg, cur, nxt);
+    if constexpr (CLAIM) tile = __builtin_amdgcn_readfirstlane(slot[0]);
     // the weight stream: one SGPR pointer to the chunk being fetched (advanced after every step, back to the first chunk after the last one) and
     // one VGPR byte offset per piece -- no vector instruction and no spilled pointer per piece (pps_common.h, chunk_copy_piece_at)
     unsigned voff[IH_CH4 / IH_NT];
@@ -348,8 +373,13 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
     // Static priority instead of a flip around the MFMA phase of every pass: the second-dispatched half of the workgroup (waves 4-7, the second query)
     // loses the issue arbitration to its older SIMD partner on every phase; raised once, it takes the partner's timing (profiles/NOTES_unpacked_valu.md)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-    for (int it = 0; it < count; ++it) {
-        const int64_t qi = (int64_t)(first + it * stride) * (IH_NW / 4) + (wave >> 2);
+    for (int it = 0; CLAIM ? tile >= 0 : it < count; ++it) {
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_INTERP + slot[1], 1);      // for the trip after this one
+        } else {
+            tile = first + it * stride;
+        }
+        const int64_t qi = (int64_t)tile * (IH_NW / 4) + (wave >> 2);
         const bool qv = qi < Q;
         const int64_t qc = qv ? qi : Q - 1;
         const int row = wq * 16 + n;
@@ -449,7 +479,17 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
         }
         rows16_sum_transposed(a, lane);
         ((f32x4*)(part + wave * 256))[4 * n + g] = a[0];
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) {
+                RangeClaim rc = {slot[1], slot[2]};
+                const int nr = tile_ranges(gridDim.x);
+                slot[0] = range_claim_resolve(head + PPS_CLAIM_INTERP, ntiles, nr, gridDim.x / nr, rc, pend);
+                slot[1] = rc.r;
+                slot[2] = rc.left;
+            }
+        }
         wg_barrier();
+        if constexpr (CLAIM) tile = __builtin_amdgcn_readfirstlane(slot[0]);
         if (wq == 0 && qv) {
             f32x4 s = ((const f32x4*)(part + (wbase + 0) * 256))[lane];
             s += ((const f32x4*)(part + (wbase + 1) * 256))[lane];
@@ -458,6 +498,7 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
             ((f32x4*)(pooled + qi * 256))[lane] = s;
         }
     }
+    if constexpr (CLAIM) claim_finish(head + PPS_CLAIM_DONE, head + PPS_CLAIM_INTERP, 8);
     range_commit(amax, range);
 }
 
@@ -641,6 +682,57 @@ __host__ __device__ inline PatchPacking patch_packing(int P, int mode = 1) {
     return k;
 }
 
+// ---- units of the persistent split-precision kernels: what a workgroup takes per trip, by claim (pps_common.h) or as its fixed share -----------
+// One arithmetic for the kernels, the launchers and the host-side enumerator ppsx_decode_units (include/ppsurf_amd_ext.h).
+// kernel 0 interp_pool_f16x3 (2 queries), 1 pointnet_stn_rows<true>, 2 pointnet_stn_head_h (64), 3 pointnet_fc3_feat_rows (16), 4 decode_tail_h (64)
+struct DecodeUnit { int64_t first; int count, mode; };      // queries [first, first + count); mode: patch_packing's for STN rows, else 0
+#define PPS_UNIT_KERNELS 5
+__host__ __device__ inline int decode_unit_queries(int kernel) { return kernel == 0 ? 2 : kernel == 3 ? 16 : 64; }
+// STN rows: queries [0, q_packed) go in packed units of PNW wave groups x qg queries (mode 1), the rest in units of one query per wave (mode 2;
+// mode 0 where the patch size does not pack).  q_packed = the full rounds over the `wgs` workgroups the chip holds.
+__host__ __device__ inline int64_t stn_rows_q_packed(int64_t Q, int P, int wgs) {
+    const PatchPacking pk = patch_packing(P);
+    const int64_t per_round = (int64_t)wgs * PNW * pk.qg;
+    return pk.packed ? (Q / per_round) * per_round : 0;
+}
+__host__ __device__ inline int64_t stn_rows_packed_units(int P, int64_t q_packed) {
+    const int64_t uq = (int64_t)PNW * patch_packing(P).qg;
+    return (q_packed + uq - 1) / uq;
+}
+__host__ __device__ inline int64_t stn_rows_units(int64_t Q, int P, int64_t q_packed) {
+    return stn_rows_packed_units(P, q_packed) + (Q - q_packed + PNW - 1) / PNW;
+}
+__host__ __device__ inline DecodeUnit stn_rows_unit(int64_t Q, int P, int64_t q_packed, int64_t u) {
+    const PatchPacking pk = patch_packing(P);
+    const int64_t npk = stn_rows_packed_units(P, q_packed), uq = (int64_t)PNW * pk.qg;
+    DecodeUnit d;
+    if (u < npk) {
+        d.first = u * uq;
+        d.count = (int)(q_packed - d.first < uq ? q_packed - d.first : uq);
+        d.mode = 1;
+    } else {
+        d.first = q_packed + (u - npk) * PNW;
+        d.count = (int)(Q - d.first < PNW ? Q - d.first : PNW);
+        d.mode = pk.packed ? 2 : 0;
+    }
+    return d;
+}
+__host__ __device__ inline int64_t decode_units(int kernel, int64_t Q, int P, int wgs) {
+    if (kernel == 1) return stn_rows_units(Q, P, stn_rows_q_packed(Q, P, wgs));
+    const int uq = decode_unit_queries(kernel);
+    return (Q + uq - 1) / uq;
+}
+// unit u in ascending order; the interpolation kernel claims in that order inside each range of tile_range_bounds (pps_common.h)
+__host__ __device__ inline DecodeUnit decode_unit(int kernel, int64_t Q, int P, int wgs, int64_t u) {
+    if (kernel == 1) return stn_rows_unit(Q, P, stn_rows_q_packed(Q, P, wgs), u);
+    const int uq = decode_unit_queries(kernel);
+    DecodeUnit d;
+    d.first = u * uq;
+    d.count = (int)(Q - d.first < uq ? Q - d.first : uq);
+    d.mode = 0;
+    return d;
+}
+
 // conv0a .. stn.conv3 on one 16-row tile; z = 256 channels
 __device__ __forceinline__ void stn_chain(float coord, f32x4 (&z)[16], const float* xyz_l, const f32x4* bias4, const f32x4* wg,
                                           f32x4*& cur, f32x4*& nxt, int lane) {
@@ -670,10 +762,12 @@ __device__ __forceinline__ void stn_chain(float coord, f32x4 (&z)[16], const flo
 // of A-fragment reads serve T x 16 rows.  conv3's output blocks are handed to zsink(tile, first_block, o0, o1) as they leave the matrix pipe (the
 // callers reduce them at once: a tile's 256 channels are never held).  conv0a stays an fp32 MFMA (K = 3), the four dense layers run as three f16
 // products each; `wg` -> pps_pack_dense_f16x3 images of c0b, s1, s2, s3 (same byte sizes and chunk boundaries as fp32).  Per tile the arithmetic does
-// not depend on T: results do not depend on how tiles are grouped.
-template <int T, class ZSink>
+// not depend on T: results do not depend on how tiles are grouped.  `publish` runs ahead of the chain's last chunk barrier (tile claims: the barrier
+// hands what it stored in LDS to the other waves).
+struct NoPublish { __device__ __forceinline__ void operator()() const {} };
+template <int T, class ZSink, class Publish = NoPublish>
 __device__ __forceinline__ void stn_chain_h_tiles(const float (&coord)[T], const float* xyz_l, const f32x4* bias4, const f32x4* wg,
-                                                  f32x4*& cur, f32x4*& nxt, int lane, float& amax, ZSink&& zsink) {
+                                                  f32x4*& cur, f32x4*& nxt, int lane, float& amax, ZSink&& zsink, Publish&& publish = Publish{}) {
     const int g = lane >> 4;
     HiLo a[T][2], b[T][2], y[T][4];
 #pragma unroll
@@ -701,6 +795,7 @@ __device__ __forceinline__ void stn_chain_h_tiles(const float (&coord)[T], const
         stream_step<PCH4, PNT>(wg + 4096 + (c + 1) * PCH4, cur, nxt, [&](const f32x4* w) {
             dense_blocks_f16x3_tiles<T, 4, PN_C3OB, 1>(y, (const half8*)w, bias4 + 80 + 4 * PN_C3OB * c, lane,
                                                       [&](int t, int i, const f32x4& o0, const f32x4& o1) { zsink(t, PN_C3OB * c + 2 * i, o0, o1); }); });
+    publish();
     stream_step<1024, PNT>(wg, cur, nxt, [&](const f32x4* w) {
         dense_blocks_f16x3_tiles<T, 4, PN_C3OB, 1>(y, (const half8*)w, bias4 + 80 + 4 * PN_C3OB * (PN_C3N - 1), lane,
                                                   [&](int t, int i, const f32x4& o0, const f32x4& o1) { zsink(t, PN_C3OB * (PN_C3N - 1) + 2 * i, o0, o1); }); });
@@ -711,9 +806,9 @@ __device__ __forceinline__ void stn_chain_h_tiles(const float (&coord)[T], const
 // copies of a pair of conv3 output blocks leave the matrix pipe together, are reduced over the tiles and with the query's parked left-over row
 // `prow` (-inf where the patch is not packed), then over the 16 rows, and stored.  The maximum is the same set of values as in the pass-by-pass
 // schedule, so g has the same bits.
-template <int T>
+template <int T, class Publish>
 __device__ __forceinline__ void stn_query_tiles(const float* __restrict__ qpatch, int P, const float* prow, float* gq, bool store, const float* xyz_l,
-                                                const f32x4* bias4, const f32x4* wg, f32x4*& cur, f32x4*& nxt, int lane, float& amax) {
+                                                const f32x4* bias4, const f32x4* wg, f32x4*& cur, f32x4*& nxt, int lane, float& amax, Publish&& publish) {
     const int n = lane & 15, g = lane >> 4;
     float coord[T];
 #pragma unroll
@@ -747,16 +842,21 @@ __device__ __forceinline__ void stn_query_tiles(const float* __restrict__ qpatch
             ((f32x4*)gq)[4 * bb + g] = f32x4{p[0], p[1], p[2], p[3]};
             ((f32x4*)gq)[4 * (bb + 1) + g] = f32x4{s[0], s[1], s[2], s[3]};
         }
-    });
+    }, publish);
 }
 
 // H = false: fp32 (wdense = wpack + 256 floats of the same image); H = true: split precision (wdense = the f16x3 image).
 // tmax (H only): 3 -- a query with at most three full tiles takes them through the chain in one pass (stn_query_tiles); 2 -- two tiles at a time
 // with a running maximum for every patch size (what fb > 3 always does).
-template <bool H>
+// CLAIM (H only): ONE launch for all Q queries instead of a packed and a remainder launch.  Units are claimed (pps_common.h) in ascending order from
+// head[PPS_CLAIM_STN_ROWS]: the packed units of queries [0, q_packed) first, then the remainder in units of one query per wave (stn_rows_unit) --
+// whoever is free takes them, no workgroup waits for a second launch.  `pack` is not used: the mode comes with the unit.
+template <bool H, bool CLAIM>
 __device__ __forceinline__ void pointnet_stn_rows_body(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
                                                        const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
-                                                       const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
+                                                       const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag,
+                                                       int64_t q_packed, int* __restrict__ head) {
+    static_assert(H || !CLAIM, "tile claims: split precision only");
     // flag: H -- where the range guard of the split reports (pps_common.h); !H -- gate of the fp32 fallback (may be null)
     if (!H && gate_closed(flag)) return;
     float amax = 0.f;
@@ -770,49 +870,72 @@ __device__ __forceinline__ void pointnet_stn_rows_body(const float* __restrict__
 
     lds_fill(xyz_l, wpack, PA_W_XYZ);
     lds_fill(bias_l, bias, PA_NBIAS);
+    int* slot = nullptr;              // claims: LDS word with the unit of the next trip, handed over by a chunk barrier
+    int unit = 0, pend = 0;
+    if constexpr (CLAIM) {
+        __shared__ int claim_l;
+        slot = &claim_l;
+        unit = blockIdx.x;            // the first unit is not claimed: the counter stands for the units behind the grid's first ones
+    }
     f32x4 *cur, *nxt;
     stream_begin<PCH4, 1024, PNT>(wg, cur, nxt);
+    auto publish = [&]() {
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) *slot = (int)gridDim.x + pend;
+        }
+    };
 
-    const PatchPacking pk = patch_packing(P, pack);
+    const PatchPacking pk = patch_packing(P, CLAIM ? 1 : pack);
     const int64_t ngroups = (Q + pk.qg - 1) / pk.qg;
-    const int ntiles = (int)((ngroups + PNW - 1) / PNW);
+    const int ntiles = CLAIM ? (int)stn_rows_units(Q, P, q_packed) : (int)((ngroups + PNW - 1) / PNW);
     const bool one_pass = H && tmax >= 3 && pk.fb <= 3;
     if (one_pass && !pk.packed)                                // no left-over rows: the wave's parked row (read by this wave alone) is the identity of max
         for (int i = lane; i < PN_ROWF; i += 64) mypark[i] = -INFINITY;
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
-    for (int it = 0; it < count; ++it) {
-        const int64_t q0 = ((int64_t)(first + it * stride) * PNW + wave) * pk.qg;
+    for (int it = 0; CLAIM ? unit < ntiles : it < count; ++it) {
+        // this trip: qg queries per wave group from q0 on, of the queries [0, Ql)
+        int qg = pk.qg;
+        int64_t Ql = Q, q0;
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_STN_ROWS, 1);      // for the trip after this one
+            const DecodeUnit du = stn_rows_unit(Q, P, q_packed, unit);
+            qg = du.mode == 1 ? pk.qg : 1;
+            Ql = du.mode == 1 ? q_packed : Q;
+            q0 = du.first + (int64_t)wave * qg;
+        } else {
+            q0 = ((int64_t)(first + it * stride) * PNW + wave) * pk.qg;
+        }
         if constexpr (H) {
             // ---- split-precision schedule: conv3's blocks are reduced as they are produced, and the full tiles of a query go through the chain all
             // at once (at most three: one_pass) or two at a time
             if (pk.packed) {
                 const int ql = n / pk.lo;
-                const int64_t qq = (q0 + ql < Q) ? q0 + ql : Q - 1;
+                const int64_t qq = (q0 + ql < Ql) ? q0 + ql : Ql - 1;
                 const float coord[1] = {(g < 3) ? patches[(qq * P + pk.fb * 16 + (n % pk.lo)) * 3 + g] : 0.f};
                 stn_chain_h_tiles<1>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, [&](int, int bb, const f32x4& o0, const f32x4& o1) {
                     f32x4 m0, m1;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { m0[r] = group_max(o0[r], pk.lo); m1[r] = group_max(o1[r], pk.lo); }
                     if ((n % pk.lo) == 0) { ((f32x4*)(mypark + ql * PN_ROWF))[4 * bb + g] = m0; ((f32x4*)(mypark + ql * PN_ROWF))[4 * (bb + 1) + g] = m1; }
-                });
+                }, publish);
             }
             if (one_pass) {
-                for (int qi = 0; qi < pk.qg; ++qi) {
+                for (int qi = 0; qi < qg; ++qi) {
                     const int64_t q = q0 + qi;
-                    const bool qv = q < Q;
-                    const float* qpatch = patches + (qv ? q : Q - 1) * P * 3;
+                    const bool qv = q < Ql;
+                    const float* qpatch = patches + (qv ? q : Ql - 1) * P * 3;
                     const float* prow = mypark + qi * PN_ROWF;
                     float* gq = gout + (qv ? q : 0) * 256;
-                    if (pk.fb == 3) stn_query_tiles<3>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
-                    else if (pk.fb == 2) stn_query_tiles<2>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
-                    else stn_query_tiles<1>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax);
+                    if (pk.fb == 3) stn_query_tiles<3>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax, publish);
+                    else if (pk.fb == 2) stn_query_tiles<2>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax, publish);
+                    else stn_query_tiles<1>(qpatch, P, prow, gq, qv, xyz_l, bias4, wg, cur, nxt, lane, amax, publish);
                 }
             } else {
-                for (int qi = 0; qi < pk.qg; ++qi) {
+                for (int qi = 0; qi < qg; ++qi) {
                     const int64_t q = q0 + qi;
-                    const bool qv = q < Q;
-                    const int64_t qc = qv ? q : Q - 1;
+                    const bool qv = q < Ql;
+                    const int64_t qc = qv ? q : Ql - 1;
                     f32x4 rmax[16];
 #pragma unroll
                     for (int bb = 0; bb < 16; ++bb)
@@ -829,11 +952,11 @@ __device__ __forceinline__ void pointnet_stn_rows_body(const float* __restrict__
                     int rb = 0;
                     for (; rb + 1 < pk.fb; rb += 2) {
                         const float coord[2] = {row_coord(rb), row_coord(rb + 1)};
-                        stn_chain_h_tiles<2>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
+                        stn_chain_h_tiles<2>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax, publish);
                     }
                     if (rb < pk.fb) {
                         const float coord[1] = {row_coord(rb)};
-                        stn_chain_h_tiles<1>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax);
+                        stn_chain_h_tiles<1>(coord, xyz_l, bias4, wg, cur, nxt, lane, amax, zmax, publish);
                     }
 #pragma unroll
                     for (int bb = 0; bb < 16; ++bb) {
@@ -887,7 +1010,9 @@ __device__ __forceinline__ void pointnet_stn_rows_body(const float* __restrict__
                 }
             }
         }
+        if constexpr (CLAIM) unit = __builtin_amdgcn_readfirstlane(*slot);      // published ahead of the last chunk barrier of the trip's first chain
     }
+    if constexpr (CLAIM) claim_finish(head + PPS_CLAIM_DONE, head + PPS_CLAIM_STN_ROWS, 1);
     if (H) range_commit(amax, flag);
 }
 // the kernel proper; the split-precision instantiation alone is compiled without packed fp32 VALU (PPS_PLAIN_F32, pps_common.h)
@@ -895,14 +1020,22 @@ template <bool H>
 __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
                                                                    const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
                                                                    const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
-    pointnet_stn_rows_body<H>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag);
+    pointnet_stn_rows_body<H, false>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag, 0, nullptr);
 }
 template <>
 PPS_PLAIN_F32
 __global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_kernel<true>(const float* __restrict__ patches, int64_t Q, int P, int pack, int tmax,
                                                                          const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
                                                                          const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag) {
-    pointnet_stn_rows_body<true>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag);
+    pointnet_stn_rows_body<true, false>(patches, Q, P, pack, tmax, wpack, wdense, bias, gout, flag, 0, nullptr);
+}
+// split precision, all queries in one launch of claimed units
+PPS_PLAIN_F32
+__global__ __launch_bounds__(PNT, 2) void pointnet_stn_rows_claim_kernel(const float* __restrict__ patches, int64_t Q, int P, int64_t q_packed, int tmax,
+                                                                         const float* __restrict__ wpack, const f32x4* __restrict__ wdense,
+                                                                         const float* __restrict__ bias, float* __restrict__ gout, int* __restrict__ flag,
+                                                                         int* __restrict__ head) {
+    pointnet_stn_rows_body<true, true>(patches, Q, P, 1, tmax, wpack, wdense, bias, gout, flag, q_packed, head);
 }
 
 // =====================================================================================================
@@ -962,9 +1095,11 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_fc_kernel(const float* __r
 }
 
 // The STN head in split precision, shared by the two kernels below: one row g[256] per lane (n, .) -> fc1(128, ReLU) -> fc2(64, ReLU) = u, every
-// layer input split (and range-tracked) on the way.  Weight chunks 0..4 of the fc image; `after` = the chunk fetched behind fc2.
+// layer input split (and range-tracked) on the way.  Weight chunks 0..4 of the fc image; `after` = the chunk fetched behind fc2.  `publish` runs
+// ahead of the last chunk barrier (tile claims, as in stn_chain_h_tiles).
+template <class Publish = NoPublish>
 __device__ __forceinline__ void stn_head_h(const float* __restrict__ grow, const f32x4* wg, const f32x4* after, const f32x4* __restrict__ bias_g,
-                                           f32x4*& cur, f32x4*& nxt, int lane, float& amax, HiLo (&u)[2]) {
+                                           f32x4*& cur, f32x4*& nxt, int lane, float& amax, HiLo (&u)[2], Publish&& publish = Publish{}) {
     HiLo ah[8], h[4];
     {
         f32x4 a[16];
@@ -978,6 +1113,7 @@ __device__ __forceinline__ void stn_head_h(const float* __restrict__ grow, const
     for (int c = 0; c < 4; ++c)
         stream_step<CH4>(wg + (c + 1) * CH4, cur, nxt, [&](const f32x4* w) {
             dense_blocks_f16x3<8, 2, 1>(ah, (const half8*)w, bias_g + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { h[c] = split_f16_r(amax, o0, o1); }); });
+    publish();
     stream_step<CH4>(after, cur, nxt, [&](const f32x4* w) {
         dense_blocks_f16x3<4, 4, 1>(h, (const half8*)w, bias_g + 32, lane, [&](int i, const f32x4& o0, const f32x4& o1) { u[i] = split_f16_r(amax, o0, o1); }); });
 }
@@ -1225,27 +1361,48 @@ __global__ __launch_bounds__(PNT, 2) void pointnet_feat_rows_kernel<true>(const 
 // (256 B per query; lane (query n, g) of the reader takes half8 (2 kb + part) * 4 + g).  Weight chunks 0..4 of the fc image, streamed as in
 // pointnet_stn_fc_h_kernel; the same values are split (and range-tracked) as there.
 #define PH_LDS_BYTES (2 * CH4 * 16)
+// CLAIM: tiles claimed in ascending order from head[PPS_CLAIM_STN_HEAD] (pps_common.h); !CLAIM (head unused): the fixed share
+template <bool CLAIM>
 __global__ __launch_bounds__(NT, 2) void pointnet_stn_head_h_kernel(const float* __restrict__ gin, int64_t Q, const f32x4* __restrict__ w16,
-                                                                    const float* __restrict__ bias, half8* __restrict__ uh, int* __restrict__ range) {
+                                                                    const float* __restrict__ bias, half8* __restrict__ uh, int* __restrict__ range,
+                                                                    int* __restrict__ head) {
     float amax = 0.f;
     const f32x4* wg = w16;
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
     const f32x4* bias_g = (const f32x4*)bias;                  // biases of the two layers: [128][64] floats
+    int* slot = nullptr;              // claims: LDS word with the tile of the next trip, handed over by a chunk barrier
+    int tile = 0, pend = 0;
+    if constexpr (CLAIM) {
+        __shared__ int claim_l;
+        slot = &claim_l;
+        tile = blockIdx.x;            // the first tile is not claimed: the counter stands for the tiles behind the grid's first ones
+    }
     f32x4 *cur, *nxt;
     stream_begin<CH4>(wg, cur, nxt);
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
-    for (int it = 0; it < count; ++it) {
-        const TileRow q = tile_row(first + it * stride, wave, n, Q);
+    for (int it = 0; CLAIM ? tile < ntiles : it < count; ++it) {
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_STN_HEAD, 1);      // for the trip after this one
+        } else {
+            tile = first + it * stride;
+        }
+        const TileRow q = tile_row(tile, wave, n, Q);
         HiLo u[2];
-        stn_head_h(gin + q.c * 256, wg, wg, bias_g, cur, nxt, lane, amax, u);
+        stn_head_h(gin + q.c * 256, wg, wg, bias_g, cur, nxt, lane, amax, u, [&]() {
+            if constexpr (CLAIM) {
+                if (threadIdx.x == 0) *slot = (int)gridDim.x + pend;
+            }
+        });
+        if constexpr (CLAIM) tile = __builtin_amdgcn_readfirstlane(*slot);
         if (q.valid) {
             half8* dst = uh + q.c * 16 + g;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) { dst[(2 * kb) * 4] = u[kb].hi; dst[(2 * kb + 1) * 4] = u[kb].lo; }
         }
     }
+    if constexpr (CLAIM) claim_finish(head + PPS_CLAIM_DONE, head + PPS_CLAIM_STN_HEAD, 1);
     range_commit(amax, range);
 }
 
@@ -1264,12 +1421,14 @@ __global__ __launch_bounds__(NT, 2) void pointnet_stn_head_h_kernel(const float*
 #define PF_QSTRIDE 257                 // half8 per query of an exchange buffer: 4 KiB + 16 B
 #define PF_BUF (8 * PF_QSTRIDE)        // half8 per buffer of 8 queries
 #define PF_LDS_BYTES (PC_LDS_BYTES + 3 * PF_BUF * 16)
+// CLAIM: passes claimed in ascending order from head[PPS_CLAIM_FC3_FEAT] (pps_common.h); !CLAIM (head unused): the fixed share
+template <bool CLAIM>
 PPS_PLAIN_F32
 __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const float* __restrict__ patches, const half8* __restrict__ uh,
                                                                           int64_t Q, int P, const f32x4* __restrict__ wfc,
                                                                           const float* __restrict__ bias_fc, const float* __restrict__ wpack,
                                                                           const f32x4* __restrict__ wdense, const float* __restrict__ bias,
-                                                                          float* __restrict__ xbar, int* __restrict__ flag) {
+                                                                          float* __restrict__ xbar, int* __restrict__ flag, int* __restrict__ head) {
     float amax = 0.f;
     half8* ex = (half8*)(pps_smem + PC_LDS_BYTES);       // the exchange buffers, behind phase C's resident arrays
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;
@@ -1288,8 +1447,22 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
     const f32x4 tf[4][4] = {};                           // the fp32 matrix of feat_rows_query: not used in split precision
-    for (int it = 0; it < count; ++it) {
-        const int64_t q0 = (int64_t)(first + it * stride) * 16;
+    // claims: the first pass is not claimed (the counter stands for the passes behind the grid's first ones); the pass after a pass is published ahead
+    // of the second barrier of slice 3 and read behind it (seven barriers lie between that read and the next store to the word)
+    int* slot = nullptr;
+    int tile = 0, next = 0, pend = 0;
+    if constexpr (CLAIM) {
+        __shared__ int claim_l;
+        slot = &claim_l;
+        tile = blockIdx.x;
+    }
+    for (int it = 0; CLAIM ? tile < ntiles : it < count; ++it) {
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_FC3_FEAT, 1);      // for the pass after this one
+        } else {
+            tile = first + it * stride;
+        }
+        const int64_t q0 = (int64_t)tile * 16;
         half8 th[4][2], tl[4][2], th2[2][2], tl2[2][2];
         {
             const int64_t qc = q0 + n < Q ? q0 + n : Q - 1;
@@ -1309,7 +1482,13 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
                     d[0] = v.hi;
                     d[64] = v.lo;
                 });
+                if constexpr (CLAIM) {
+                    if (ob == 3 && threadIdx.x == 0) *slot = (int)gridDim.x + pend;
+                }
                 wg_barrier();
+                if constexpr (CLAIM) {
+                    if (ob == 3) next = __builtin_amdgcn_readfirstlane(*slot);
+                }
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb) {
                     th[ob][kb] = ex_r[(2 * kb) * 64];
@@ -1335,7 +1514,9 @@ __global__ __launch_bounds__(PF_NT, 2) void pointnet_fc3_feat_rows_kernel(const 
             }
             feat_rows_query<true>(patches, q0 + wave + 8, P, ntile_rows, th, tl, tf, pc, s0, amax, lane, xbar);
         }
+        if constexpr (CLAIM) tile = next;
     }
+    if constexpr (CLAIM) claim_finish(head + PPS_CLAIM_DONE, head + PPS_CLAIM_FC3_FEAT, 1);
     range_commit(amax, flag);
 }
 
@@ -1398,10 +1579,13 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_kernel(const float* __restr
 // two 256 -> 256 halves ([pooled | xbar] are two tensors), the second starts from the fp32 accumulators of the first.
 // w16 (half8 fragments): pps_pack_dense_f16x3 images, 32 KiB chunks (two output blocks each): Wa and Wb ALTERNATING chunk by chunk (the pair of
 // output blocks 2c, 2c+1 is finished before the next one starts: two live accumulator blocks instead of sixteen), then [L2][L3].
+// CLAIM: tiles claimed in ascending order from head[PPS_CLAIM_TAIL] (pps_common.h); !CLAIM (head unused): the fixed share
+template <bool CLAIM>
 PPS_PLAIN_F32
 __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __restrict__ pooled, const float* __restrict__ xbar, int64_t Q,
                                                               const f32x4* __restrict__ w16, const float* __restrict__ bias,
-                                                              float* __restrict__ logits, float* __restrict__ occ, int* __restrict__ range) {
+                                                              float* __restrict__ logits, float* __restrict__ occ, int* __restrict__ range,
+                                                              int* __restrict__ head) {
     float amax = 0.f;
     float* bias_l = (float*)((f32x4*)pps_smem + 2 * CH4);
     const f32x4* bias4 = (const f32x4*)bias_l;
@@ -1409,14 +1593,26 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __res
     const int lane = lane_id(), wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
 
     lds_fill(bias_l, bias, TL_NBIAS);
+    int* slot = nullptr;              // claims: LDS word with the tile of the next trip, handed over by a chunk barrier
+    int tile = 0, pend = 0;
+    if constexpr (CLAIM) {
+        __shared__ int claim_l;
+        slot = &claim_l;
+        tile = blockIdx.x;            // the first tile is not claimed: the counter stands for the tiles behind the grid's first ones
+    }
     f32x4 *cur, *nxt;
     stream_begin<CH4>(wg, cur, nxt);
 
     const int ntiles = (int)((Q + NW * 16 - 1) / (NW * 16));
     int first, count, stride;
     xcd_tile_range(ntiles, first, count, stride);
-    for (int it = 0; it < count; ++it) {
-        const TileRow q = tile_row(first + it * stride, wave, n, Q);
+    for (int it = 0; CLAIM ? tile < ntiles : it < count; ++it) {
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_TAIL, 1);      // for the trip after this one
+        } else {
+            tile = first + it * stride;
+        }
+        const TileRow q = tile_row(tile, wave, n, Q);
         HiLo p[8], x[4];
         {
             const f32x4* sp = (const f32x4*)(pooled + q.c * 256) + g;
@@ -1441,16 +1637,22 @@ __global__ __launch_bounds__(NT, 2) void decode_tail_h_kernel(const float* __res
             stream_step<CH4>(wg + 24576 + (c + 1) * 2048, cur, nxt, [&](const f32x4* w) {
                 dense_blocks_f16x3<8, 2, 1>(y, (const half8*)w, bias4 + 64 + 8 * c, lane, [&](int, const f32x4& o0, const f32x4& o1) { p[c] = split_f16_r(amax, o0, o1); }); });
         f32x4 o[2];
+        if constexpr (CLAIM) {
+            if (threadIdx.x == 0) *slot = (int)gridDim.x + pend;      // handed over by the barrier of the trip's last chunk step
+        }
         stream_step<CH4>(wg, cur, nxt, [&](const f32x4* w) {
             dense_blocks_f16x3<8, 2, 0>(p, (const half8*)w, bias4 + 128, lane, [&](int, const f32x4& o0, const f32x4& o1) { o[0] = o0; o[1] = o1; }); });
+        if constexpr (CLAIM) tile = __builtin_amdgcn_readfirstlane(*slot);
         store_logits(o[0], q, g, logits, occ);
     }
+    if constexpr (CLAIM) claim_finish(head + PPS_CLAIM_DONE, head + PPS_CLAIM_TAIL, 1);
     range_commit(amax, range);
 }
 
 // =====================================================================================================
 // host side
 // =====================================================================================================
+static_assert(IH_NW / 4 == 2 && NW * 16 == 64, "decode_unit_queries: queries per tile of the interpolation kernel, of the STN head and of the tail");
 static int g_cu_count = 0;
 static int cu_count() {
     if (g_cu_count == 0) {
@@ -1492,8 +1694,7 @@ static PnSplit pn_split(int64_t q, int p) {
     const PatchPacking pk = patch_packing(p);
     PnSplit sp;
     const int wgs = chip_wgs(PN_WG_PER_CU);
-    const int64_t per_round = (int64_t)wgs * PNW * pk.qg;
-    sp.q_packed = pk.packed ? (q / per_round) * per_round : 0;
+    sp.q_packed = stn_rows_q_packed(q, p, wgs);
     if (pk.packed && getenv("PPS_PN_FORCE_PACK")) sp.q_packed = q;      // test hook: packed path for any query count
     sp.grid_packed = wgs;
     sp.rest_mode = pk.packed ? 2 : 0;                // the remainder in the packed arithmetic, one query per wave group: same bits as a packed round
@@ -1501,15 +1702,34 @@ static PnSplit pn_split(int64_t q, int p) {
     return sp;
 }
 
+// Tile claims inside pps_decode_fwd*: which split-precision kernels take their tiles from the workspace counters (pps_common.h).  PPS_TILE_CLAIMS,
+// read per call (tests and A/B runs switch it): unset = the product's set, 0 = none (fixed shares everywhere), else a mask of the bits below.
+enum { CLAIM_INTERP = 1, CLAIM_STN_ROWS = 2, CLAIM_STN_HEAD = 4, CLAIM_FC3_FEAT = 8, CLAIM_TAIL = 16 };
+#ifndef PPS_CLAIM_DEFAULT
+// the product's set: the two kernels where claiming measured faster (profiles/NOTES_tile_claims.md: STN rows -2.6 %, fc3 + feature -2.8 %; the
+// interpolation kernel +0.8 %, the STN head +1.3 us and the tail +6.4 us keep the fixed share)
+#define PPS_CLAIM_DEFAULT (CLAIM_STN_ROWS | CLAIM_FC3_FEAT)
+#endif
+static int claim_mask() {
+    const char* e = getenv("PPS_TILE_CLAIMS");
+    return (e && *e) ? (atoi(e) & 31) : PPS_CLAIM_DEFAULT;
+}
+
+// head (split precision only): the claim words of the decoder workspace -- one launch of claimed units; null -- the two launches of pn_split
 template <bool H>
 static int launch_stn_rows(const float* patches, int64_t q, int p, const float* wpack, const void* wdense, const float* bias, float* g,
-                           int* flag, void* stream) {
+                           int* flag, void* stream, int* head = nullptr) {
     const PnSplit sp = pn_split(q, p);
     // split precision: the full tiles of a query in one pass where there are at most three; PPS_STN_TILES=2 (read per call: a test switches it) keeps
     // the two-at-a-time schedule, same bits
     const char* tiles_env = getenv("PPS_STN_TILES");
     const int tmax = (tiles_env && atoi(tiles_env) == 2) ? 2 : 3;
     int rc = PPS_OK;
+    if constexpr (H) {
+        if (head != nullptr)
+            return launch<pointnet_stn_rows_claim_kernel>(grid_for(stn_rows_units(q, p, sp.q_packed), sp.grid_packed), PNT, PA_LDS_BYTES, stream, patches, q,
+                                                          p, sp.q_packed, tmax, wpack, (const f32x4*)wdense, bias, g, flag, head);
+    }
     if (sp.q_packed > 0)
         rc = launch<pointnet_stn_rows_kernel<H>>(sp.grid_packed, PNT, PA_LDS_BYTES, stream, patches, sp.q_packed, p, 1, tmax, wpack,
                                                  (const f32x4*)wdense, bias, g, flag);
@@ -1554,6 +1774,65 @@ static int decode_tail_f32_impl(const float* pooled, const float* xbar, int64_t 
                                       gate);
 }
 
+// head: the claim words of the decoder workspace, or null for the fixed share (so for the two split-precision launchers below)
+static int interp_pool_f16x3_impl(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k, const float* wxyz,
+                                  const void* w16, const float* bias, float* pooled, int32_t* range_flag, int* head, void* stream) {
+    if (q < 0 || k < 1 || k > 64) return PPS_ERR_ARG;
+    if (q == 0) return PPS_OK;
+    if (!G || !pts || !query || !idx || !wxyz || !w16 || !bias || !pooled) return PPS_ERR_ARG;
+    const int grid = grid_for((q + IH_NW / 4 - 1) / (IH_NW / 4), chip_wgs(IH_WG_PER_CU));      // one 8-wave workgroup per CU (IH_NT = 512)
+    if (head != nullptr)
+        return launch<interp_pool_f16x3_kernel<true>>(grid, IH_NT, IH_LDS_BYTES, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled,
+                                                      (int*)range_flag, head);
+    return launch<interp_pool_f16x3_kernel<false>>(grid, IH_NT, IH_LDS_BYTES, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled,
+                                                   (int*)range_flag, (int*)nullptr);
+}
+
+static int decode_tail_f16x3_impl(const float* pooled, const float* xbar, int64_t q, const void* w16, const float* bias, float* logits, float* occ,
+                                  int32_t* range_flag, int* head, void* stream) {
+    if (q < 0) return PPS_ERR_ARG;
+    if (q == 0) return PPS_OK;
+    if (!pooled || !xbar || !w16 || !bias || !logits) return PPS_ERR_ARG;
+    const int grid = grid_for((q + NW * 16 - 1) / (NW * 16));
+    if (head != nullptr)
+        return launch<decode_tail_h_kernel<true>>(grid, NT, TL_LDS_BYTES, stream, pooled, xbar, q, (const f32x4*)w16, bias, logits, occ, (int*)range_flag, head);
+    return launch<decode_tail_h_kernel<false>>(grid, NT, TL_LDS_BYTES, stream, pooled, xbar, q, (const f32x4*)w16, bias, logits, occ, (int*)range_flag, head);
+}
+
+// head, claims: the claim words of the decoder workspace and which kernels use them (CLAIM_* bits); null = fixed shares
+static int pointnet_f16x3_impl(const float* patches, int64_t q, int p, const float* const* weights, const void* const* w16, float* g, float* trans2,
+                               float* xbar, int32_t* range_flag, void* const* events, int* head, int claims, void* stream) {
+    if (q < 0 || p < 1) return PPS_ERR_ARG;
+    if (q == 0) return PPS_OK;
+    if (!patches || !weights || !w16 || !w16[0] || !w16[1] || !w16[2] || !g || !trans2 || !xbar) return PPS_ERR_ARG;
+    int* range = (int*)range_flag;
+    auto mark = [&](int i) { if (events && events[i]) hipEventRecord((hipEvent_t)events[i], (hipStream_t)stream); };
+    int rc = launch_stn_rows<true>(patches, q, p, weights[0], w16[0], weights[1], g, range, stream, (head && (claims & CLAIM_STN_ROWS)) ? head : nullptr);
+    mark(0);
+    if (rc != PPS_OK) return rc;
+    const int head_grid = grid_for((q + NW * 16 - 1) / (NW * 16));
+    // Default: M never leaves the CU.  The head writes u (256 B per query, already split) into the start of the trans2 slot, and one kernel runs
+    // fc3 and phase C (pointnet_fc3_feat_rows_kernel).  PPS_PN_FUSED=0 (read per call: a test switches it) keeps the two kernels with M in trans2.
+    const char* fused_env = getenv("PPS_PN_FUSED");
+    const bool fused = !(fused_env && fused_env[0] == '0' && fused_env[1] == 0);
+    int* const head_c = (head && (claims & CLAIM_STN_HEAD)) ? head : nullptr;
+    int* const feat_c = (head && (claims & CLAIM_FC3_FEAT)) ? head : nullptr;
+    const f32x4* wfc = (const f32x4*)w16[1];
+    if (!fused) rc = launch<pointnet_stn_fc_h_kernel>(head_grid, NT, PB_LDS_BYTES, stream, g, q, wfc, weights[3], (half8*)trans2, range);
+    else if (head_c) rc = launch<pointnet_stn_head_h_kernel<true>>(head_grid, NT, PH_LDS_BYTES, stream, g, q, wfc, weights[3], (half8*)trans2, range, head_c);
+    else rc = launch<pointnet_stn_head_h_kernel<false>>(head_grid, NT, PH_LDS_BYTES, stream, g, q, wfc, weights[3], (half8*)trans2, range, head_c);
+    mark(1);
+    if (rc != PPS_OK) return rc;
+    const int feat_grid = grid_for((q + 15) / 16, chip_wgs(1));
+    if (!fused) rc = launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
+    else if (feat_c) rc = launch<pointnet_fc3_feat_rows_kernel<true>>(feat_grid, PF_NT, PF_LDS_BYTES, stream, patches, (const half8*)trans2, q, p, wfc, weights[3],
+                                                                      weights[4], (const f32x4*)w16[2], weights[5], xbar, range, feat_c);
+    else rc = launch<pointnet_fc3_feat_rows_kernel<false>>(feat_grid, PF_NT, PF_LDS_BYTES, stream, patches, (const half8*)trans2, q, p, wfc, weights[3],
+                                                           weights[4], (const f32x4*)w16[2], weights[5], xbar, range, feat_c);
+    mark(2);
+    return rc;
+}
+
 extern "C" {
 
 int pps_abi_version(void) { return 2; }
@@ -1576,12 +1855,7 @@ int pps_interp_pool_f32(const float* G, const float* pts, const float* query, co
 
 int pps_interp_pool_f16x3(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k,
                           const float* wxyz, const void* w16, const float* bias, float* pooled, int32_t* range_flag, void* stream) {
-    if (q < 0 || k < 1 || k > 64) return PPS_ERR_ARG;
-    if (q == 0) return PPS_OK;
-    if (!G || !pts || !query || !idx || !wxyz || !w16 || !bias || !pooled) return PPS_ERR_ARG;
-    const int grid = grid_for((q + IH_NW / 4 - 1) / (IH_NW / 4), chip_wgs(IH_WG_PER_CU));      // one 8-wave workgroup per CU (IH_NT = 512)
-    return launch<interp_pool_f16x3_kernel>(grid, IH_NT, IH_LDS_BYTES, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled,
-                                            (int*)range_flag);
+    return interp_pool_f16x3_impl(G, pts, query, idx, q, k, wxyz, w16, bias, pooled, range_flag, nullptr, stream);
 }
 
 int pps_interp_small_f32(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k, int c,
@@ -1640,30 +1914,8 @@ int pps_pointnet_feat_rows_f32(const float* patches, const float* trans2, int64_
  * the kernels; with PPS_PN_FUSED=0 all of it holds the pre-split fragments of the per-query matrix. */
 int pps_pointnet_f16x3(const float* patches, int64_t q, int p, const float* const* weights /* [2..7] of the decode array */,
                        const void* const* w16, float* g, float* trans2, float* xbar, int32_t* range_flag, void* const* events, void* stream) {
-    if (q < 0 || p < 1) return PPS_ERR_ARG;
-    if (q == 0) return PPS_OK;
-    if (!patches || !weights || !w16 || !w16[0] || !w16[1] || !w16[2] || !g || !trans2 || !xbar) return PPS_ERR_ARG;
-    int* range = (int*)range_flag;
-    auto mark = [&](int i) { if (events && events[i]) hipEventRecord((hipEvent_t)events[i], (hipStream_t)stream); };
-    int rc = launch_stn_rows<true>(patches, q, p, weights[0], w16[0], weights[1], g, range, stream);
-    mark(0);
-    if (rc != PPS_OK) return rc;
-    const int head_grid = grid_for((q + NW * 16 - 1) / (NW * 16));
-    // Default: M never leaves the CU.  The head writes u (256 B per query, already split) into the start of the trans2 slot, and one kernel runs
-    // fc3 and phase C (pointnet_fc3_feat_rows_kernel).  PPS_PN_FUSED=0 (read per call: a test switches it) keeps the two kernels with M in trans2.
-    const char* fused_env = getenv("PPS_PN_FUSED");
-    const bool fused = !(fused_env && fused_env[0] == '0' && fused_env[1] == 0);
-    rc = fused ? launch<pointnet_stn_head_h_kernel>(head_grid, NT, PH_LDS_BYTES, stream, g, q, (const f32x4*)w16[1], weights[3], (half8*)trans2, range)
-               : launch<pointnet_stn_fc_h_kernel>(head_grid, NT, PB_LDS_BYTES, stream, g, q, (const f32x4*)w16[1], weights[3], (half8*)trans2, range);
-    mark(1);
-    if (rc != PPS_OK) return rc;
-    rc = fused ? launch<pointnet_fc3_feat_rows_kernel>(grid_for((q + 15) / 16, chip_wgs(1)), PF_NT, PF_LDS_BYTES, stream, patches, (const half8*)trans2,
-                                                       q, p, (const f32x4*)w16[1], weights[3], weights[4], (const f32x4*)w16[2], weights[5], xbar, range)
-               : launch_feat_rows<true>(patches, trans2, q, p, weights[4], w16[2], weights[5], xbar, range, stream);
-    mark(2);
-    return rc;
+    return pointnet_f16x3_impl(patches, q, p, weights, w16, g, trans2, xbar, range_flag, events, nullptr, 0, stream);
 }
-
 int pps_decode_tail_f32(const float* pooled, const float* xbar, int64_t q, const float* wpack, const float* bias,
                         float* logits, float* occ, void* stream) {
     return decode_tail_f32_impl(pooled, xbar, q, wpack, bias, logits, occ, nullptr, stream);
@@ -1671,11 +1923,7 @@ int pps_decode_tail_f32(const float* pooled, const float* xbar, int64_t q, const
 
 int pps_decode_tail_f16x3(const float* pooled, const float* xbar, int64_t q, const void* w16, const float* bias, float* logits, float* occ,
                           int32_t* range_flag, void* stream) {
-    if (q < 0) return PPS_ERR_ARG;
-    if (q == 0) return PPS_OK;
-    if (!pooled || !xbar || !w16 || !bias || !logits) return PPS_ERR_ARG;
-    return launch<decode_tail_h_kernel>(grid_for((q + NW * 16 - 1) / (NW * 16)), NT, TL_LDS_BYTES, stream, pooled, xbar, q, (const f32x4*)w16, bias,
-                                        logits, occ, (int*)range_flag);
+    return decode_tail_f16x3_impl(pooled, xbar, q, w16, bias, logits, occ, range_flag, nullptr, stream);
 }
 
 /* The whole decoder of one query chunk in one call: the five launches above on `stream`, intermediates in caller scratch (the first 64 bytes of it
@@ -1704,11 +1952,13 @@ static int decode_fwd(const float* table, const float* pts, const float* query, 
     if (split && hipMemsetAsync(guard, 0, sizeof(int), st) != hipSuccess) return PPS_ERR_LAUNCH;
 #define PPS_MARK(i) do { if (events && events[i] && hipEventRecord((hipEvent_t)events[i], st) != hipSuccess) return PPS_ERR_LAUNCH; } while (0)
     PPS_MARK(0);
-    int rc = interp_w16 ? pps_interp_pool_f16x3(table, pts, query, idx, q, k, weights[0], interp_w16, weights[1], pooled, guard, stream)
+    const int claims = claim_mask();
+    int rc = interp_w16 ? interp_pool_f16x3_impl(table, pts, query, idx, q, k, weights[0], interp_w16, weights[1], pooled, guard,
+                                                 (claims & CLAIM_INTERP) ? guard : nullptr, stream)
                         : pps_interp_pool_f32(table, pts, query, idx, q, k, weights[0], weights[1], pooled, stream);
     PPS_MARK(1);
     if (pn16) {
-        if (rc == PPS_OK) rc = pps_pointnet_f16x3(patches, q, p, weights + 2, w16 + 1, g, trans2, xbar, guard, events ? events + 2 : nullptr, stream);
+        if (rc == PPS_OK) rc = pointnet_f16x3_impl(patches, q, p, weights + 2, w16 + 1, g, trans2, xbar, guard, events ? events + 2 : nullptr, guard, claims, stream);
     } else {
         if (rc == PPS_OK) rc = pps_pointnet_stn_rows_f32(patches, q, p, weights[2], weights[3], g, stream);
         PPS_MARK(2);
@@ -1718,7 +1968,7 @@ static int decode_fwd(const float* table, const float* pts, const float* query, 
         PPS_MARK(4);
     }
     if (rc == PPS_OK)
-        rc = (w16 && w16[4]) ? pps_decode_tail_f16x3(pooled, xbar, q, w16[4], weights[9], logits, occ, guard, stream)
+        rc = (w16 && w16[4]) ? decode_tail_f16x3_impl(pooled, xbar, q, w16[4], weights[9], logits, occ, guard, (claims & CLAIM_TAIL) ? guard : nullptr, stream)
                              : pps_decode_tail_f32(pooled, xbar, q, weights[8], weights[9], logits, occ, stream);
     PPS_MARK(5);
 #undef PPS_MARK
@@ -1751,6 +2001,28 @@ int pps_decode_fwd_mixed_f32(const float* table, const float* pts, const float* 
                              void* ws, void* const* events, void* stream) {
     if (!w16) return PPS_ERR_ARG;
     return decode_fwd(table, pts, query, idx, q, k, patches, p, weights, logits, occ, ws, events, stream, w16);
+}
+
+/* include/ppsurf_amd_ext.h: the units of a persistent split-precision kernel, on the host, from the arithmetic the kernels use */
+int ppsx_decode_units(int kernel, int64_t q, int p, int wgs, int64_t* units, int64_t capacity, int64_t* count) {
+    if (kernel < 0 || kernel >= PPS_UNIT_KERNELS || q < 0 || p < 1 || wgs < 1 || capacity < 0 || !count || (capacity > 0 && !units)) return PPS_ERR_ARG;
+    const int ntiles = (int)decode_units(kernel, q, p, wgs);
+    // the interpolation kernel claims range by range of the workgroups' XCDs, every other kernel from one counter: ascending either way
+    const int nranges = kernel == 0 ? tile_ranges(wgs) : 1;
+    int64_t n = 0;
+    for (int r = 0; r < nranges; ++r) {
+        int lo, hi;
+        tile_range_bounds(ntiles, nranges, r, lo, hi);
+        for (int u = lo; u < hi; ++u, ++n) {
+            if (n >= capacity) continue;
+            const DecodeUnit d = decode_unit(kernel, q, p, wgs, u);
+            units[3 * n] = d.first;
+            units[3 * n + 1] = d.count;
+            units[3 * n + 2] = d.mode;
+        }
+    }
+    *count = n;
+    return PPS_OK;
 }
 
 }  // extern "C"

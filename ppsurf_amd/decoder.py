@@ -192,7 +192,7 @@ class DecoderPlan:
             t = torch.empty(max(n, 1), dtype=dtype, device=self.device)
             t[:16].zero_()                                     # head of the decoder workspace: range-guard words (include/ppsurf_amd.h)
             if old is not None and old.dtype == dtype and old.numel() >= 16 and t.numel() >= 16:
-                t[:16].copy_(old[:16])                         # the fall-back counter survives a growing workspace
+                t[1:2].copy_(old[1:2])                         # the fall-back counter survives a growing workspace; the claim words start at zero
             self._scratch[name] = t
         return t[:n].view(shape)
 

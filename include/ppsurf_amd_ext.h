@@ -194,10 +194,21 @@ int ppsx_denoise_filter_pass(const int64_t* faces, int64_t nf, int64_t nv, const
 int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, int64_t nf, const double* normals, const int64_t* offsets,
                              const int32_t* inc, int64_t ni, double* out, void* stream);
 
+/* ---- the labelling layer: the compress step of every stage that keeps int32 labels (csrc/pps_labels.hip, csrc/pps_labels.h) -------------
+ * Driven by ppsurf_amd/labels.py, whose fixed_point repeats { flag = 0; a stage's hook; flag down -> done; compress }; the argument (I1,
+ * I2, stale reads, the fixed point, progress, the bounds of a walk) is written out once, in csrc/pps_labels.h, and in DESIGN.md section 26.
+ *   ppsx_labels_compress  every slot x of label int32 [n] with label[x] >= 0 stores the end of its walk in label[x] -- a walk steps from x
+ *                         to label[x] while 0 <= label[x] < x, reads no slot outside [0, x] and takes at most x steps; a slot with a
+ *                         negative label is not touched.  Runs on the face labels of section 21, the vertex labels of section 24 and the
+ *                         3 nf corner labels of section 25.  256 threads, (n + 255) / 256 blocks.
+ *                         n < 0, n > 2^31 - 1 or a NULL label with n > 0: PPS_ERR_ARG, nothing is launched or written.  n == 0: 0,
+ *                         nothing is launched. */
+int ppsx_labels_compress(int32_t* label, int64_t n, void* stream);
+
 /* ---- isolated pieces: face components, a table per component, the rules that drop components (csrc/pps_pieces.hip) -----------------------
  * new capability: replaces nothing -- the reference's rule, remove_small_connected_components(num_faces = 6), stays with
- * pps_mesh_small_components.  Driven by ppsurf_amd/pieces.py (the keys by ppsurf_amd/topology.py); the rule and the argument for the
- * labelling are written out at the top of csrc/pps_pieces.hip and in DESIGN.md section 21.  A face is valid when its three indices lie in
+ * pps_mesh_small_components.  Driven by ppsurf_amd/pieces.py (the keys by ppsurf_amd/topology.py, the loop by ppsurf_amd/labels.py); the
+ * rule is written out at the top of csrc/pps_pieces.hip and in DESIGN.md section 21, the argument for the labelling in csrc/pps_labels.h.  A face is valid when its three indices lie in
  * [0, nv) and are pairwise distinct; two valid faces are adjacent when they share an undirected edge that exactly two valid faces hold; a
  * component's leader is its smallest face index.
  *   ppsx_pieces_edge_keys  keys int64 [3 nf]: per valid face (a, b, c) of faces int64 [nf,3] the keys of the undirected edges ab, bc, ca in
@@ -212,11 +223,6 @@ int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, 
  *                          with a negative label is skipped.  No read relies on a write of the same launch; see the .hip file.
  *                          np < 0, nf < 0, np or nf > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is
  *                          launched or written.  np == 0 or nf == 0: 0, nothing is launched.
- *   ppsx_pieces_compress   every face f with label[f] >= 0 stores the end of its walk in label[f]; a face with a negative label is not
- *                          touched.  A walk reads no slot outside [0, f] and takes at most f steps.  The entry is generic over int32
- *                          labels of this kind: ppsurf_amd/manifold.py runs it on the 3 nf corner labels of section 25.
- *                          nf < 0, nf > 2^31 - 1 or a NULL label with nf > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0,
- *                          nothing is launched.
  *   ppsx_pieces_stats      count int64 [nc], lo, hi f32 [nc,3]: per component c the number of its faces and the box of their corners over
  *                          verts f32 [nv,3], every coordinate taken as x + 0.0f.  Face f belongs to cid[f] (int32 [nf]); a face with
  *                          label[f] < 0, an invalid face and a face with cid[f] outside [0, nc) are skipped and not read through.  A
@@ -235,7 +241,6 @@ int ppsx_denoise_vertex_pass(const double* x, int64_t nv, const int64_t* faces, 
  *                          launched or written.  nc == 0: 0, nothing is launched. */
 int ppsx_pieces_edge_keys(const int64_t* faces, int64_t nf, int64_t nv, int64_t* keys, void* stream);
 int ppsx_pieces_hook(const int32_t* fa, const int32_t* fb, int64_t np, int32_t* label, int64_t nf, int32_t* changed, void* stream);
-int ppsx_pieces_compress(int32_t* label, int64_t nf, void* stream);
 int ppsx_pieces_stats(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int32_t* label, const int32_t* cid, int64_t nc,
                       int64_t* count, float* lo, float* hi, void* stream);
 int ppsx_pieces_select(const int64_t* count, const float* lo, const float* hi, const int64_t* rank, int64_t nc, int has_min_faces,
@@ -305,8 +310,8 @@ int ppsx_decimate_rename(const int64_t* faces, int64_t nf, int64_t nv, const int
 
 /* ---- orientation: coherent, outward winding per component (csrc/pps_orient.hip) -----------------------------------------------------------
  * new capability: replaces nothing -- the reference has no such stage and every other stage takes the winding as it comes.  Driven by
- * ppsurf_amd/orient.py (the pairs and their edge slots by ppsurf_amd/topology.py); the rule and the argument for the labelling with a
- * parity are written out at the top of csrc/pps_orient.hip and in DESIGN.md section 23.  Pairs: fa, fb int32 [np] the two valid faces on an
+ * ppsurf_amd/orient.py (the pairs and their edge slots by ppsurf_amd/topology.py); the rule and what the parity adds to the labelling argument of
+ * csrc/pps_labels.h are written out at the top of csrc/pps_orient.hip and in DESIGN.md section 23.  Pairs: fa, fb int32 [np] the two valid faces on an
  * edge that exactly two valid faces hold, ea, eb int32 [np] the slot of that edge in each (slot k is corner k -> corner k + 1 mod 3).
  * word int64 [nf]: (parent << 1) | flip relative to the parent, -1 for an invalid face; word[f] = f << 1 to begin with.  A pair with an entry
  * outside [0, nf), a slot outside [0, 3) or onto a face with a negative word is skipped, never read through.
@@ -364,8 +369,9 @@ int ppsx_orient_apply(const int64_t* faces, int64_t nf, const int32_t* cid, cons
 
 /* ---- weld: coincident and close vertices become one row (csrc/pps_weld.hip) ---------------------------------------------------------------
  * new capability: replaces nothing -- the reference has no such stage, and pps_mesh_corner_weld stays the weld of Marching Cubes in its own
- * grid index space.  Driven by ppsurf_amd/weld.py (the cell lists by trim.SupportGrid: ppsx_trim_cell_slots, a sort, ops.row_offsets); the
- * rule and the argument for the labelling are written out at the top of csrc/pps_weld.hip and in DESIGN.md section 24.  Rows i != j of
+ * grid index space.  Driven by ppsurf_amd/weld.py (the cell lists by trim.SupportGrid: ppsx_trim_cell_slots, a sort, ops.row_offsets; the loop by
+ * ppsurf_amd/labels.py); the rule is written out at the top of csrc/pps_weld.hip and in DESIGN.md section 24, the argument for the
+ * labelling in csrc/pps_labels.h.  Rows i != j of
  * pts f32 [n,3] are linked when ((dx dx + dy dy) + dz dz) <= eps * eps in fp64 on the widened f32, every operation rounded on its own; a
  * cluster is a connected component of the links and its leader is its smallest row.  lo, hi, h, inv_h, table, capacity, order, offsets are
  * those of ppsx_trim_cell_slots and ppsx_trim_face_support over the same pts; no result depends on them.
@@ -381,10 +387,6 @@ int ppsx_orient_apply(const int64_t* faces, int64_t nf, const int32_t* cid, cons
  *                       n < 0, n > 2^31 - 1, eps negative or NaN, or -- with n > 0 -- a NULL pointer, a capacity that is no power of two
  *                       > n or a grid that make_grid of pps_cells.h refuses: PPS_ERR_ARG, nothing is launched or written.  n == 0: 0,
  *                       nothing is launched.
- *   ppsx_weld_compress  every vertex v with label[v] >= 0 stores the end of its walk in label[v]; one with a negative label is not touched.  A walk reads no slot outside [0, v] and takes at most v
- *                       steps.
- *                       n < 0, n > 2^31 - 1 or a NULL label with n > 0: PPS_ERR_ARG, nothing is launched or written.  n == 0: 0, nothing
- *                       is launched.
  *   ppsx_weld_faces     out int64 [nf,3], code u8 [nf] from faces int64 [nf,3] and newrow int64 [nv] (newrow[v] = the output row of v's
  *                       leader).  code 1: the face is invalid as given -- an index outside [0, nv) or two equal indices -- or one of its
  *                       newrow entries lies outside [0, nv); code 2: valid as given and two of its new indices are equal; code 0: kept,
@@ -394,15 +396,14 @@ int ppsx_orient_apply(const int64_t* faces, int64_t nf, const int32_t* cid, cons
  *                       nv > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched. */
 int ppsx_weld_hook(const float* pts, int64_t n, const float* lo, const float* hi, float h, float inv_h, const uint64_t* table, int64_t capacity,
                    const int64_t* order, const int64_t* offsets, double eps, int32_t* label, int32_t* changed, void* stream);
-int ppsx_weld_compress(int32_t* label, int64_t n, void* stream);
 int ppsx_weld_faces(const int64_t* faces, int64_t nf, int64_t nv, const int64_t* newrow, int64_t* out, uint8_t* code, void* stream);
 
 /* ---- manifold split: many-owner edges and pinched vertices are cut apart by duplicating vertices (csrc/pps_manifold.hip) ------------------
  * new capability: replaces nothing -- the reference has no such stage.  Driven by ppsurf_amd/manifold.py (the pairs and their edge slots
- * by ppsurf_amd/topology.py); the rule, the argument for the labelling and the argument that the result is manifold are written out at the
- * top of csrc/pps_manifold.hip and in DESIGN.md section 25.  Corner c = 3 f + k of a valid face f names the vertex faces[f][k]; label
+ * by ppsurf_amd/topology.py, the loop by ppsurf_amd/labels.py); the rule and the argument that the result is manifold are written out at the
+ * top of csrc/pps_manifold.hip and in DESIGN.md section 25, the argument for the labelling in csrc/pps_labels.h.  Corner c = 3 f + k of a valid face f names the vertex faces[f][k]; label
  * int32 [3 nf] holds one entry per corner, label[c] = c to begin with and -1 for a corner of an invalid face.  The compress launch between
- * two hooks is ppsx_pieces_compress(label, 3 nf).
+ * two hooks is ppsx_labels_compress(label, 3 nf).
  *   ppsx_manifold_hook   one hooking round over the pairs fa, fb, ea, eb int32 [np] (the two valid faces on an edge that exactly two valid
  *                        faces hold and the slot of that edge in each; slot k is corner k -> corner k + 1 mod 3).  One thread per pair reads
  *                        the four corners of the two slots from faces int64 [nf,3]: when both slots name the same two vertices, the corner

@@ -1,11 +1,33 @@
-// The walk over int32 labels that the hooking and compressing stages share: the face components (pps_pieces.hip), the
-// vertex clusters of the weld (pps_weld.hip, section 24) and the corner fans (pps_manifold.hip, section 25).  pps_orient.hip walks 64-bit
-// words that carry a parity and keeps its own.
+// The labelling layer: connected components by hooking and compressing over int32 labels.  The face components
+// (pps_pieces.hip, section 21), the vertex clusters of the weld (pps_weld.hip, section 24) and the corner fans (pps_manifold.hip, section 25)
+// share the walk, the join and the one compress entry (pps_labels.hip); the host loop is ppsurf_amd/labels.py.  pps_orient.hip walks 64-bit
+// words that carry a parity (a different state), keeps its own walk, hook and compress, and adds I3 to the argument below.
 //
-// label[x] <= x for every slot that takes part and labels only fall, so a walk descends and ends.  Every label is read by ONE relaxed
-// device-scope atomic load: the range check and the use see the same value, and the value is the one the slot has or an earlier one -- the
-// L2s of the XCDs are not coherent for plain loads, and no kernel relies on seeing another workgroup's write inside its launch (the
-// argument is written out at the top of pps_pieces.hip).
+// The argument, once.  A NODE is a slot of label int32 [n] (a face, a vertex, a corner); a LINK joins two nodes (a stage says what its links
+// are); a component is a class of the transitive closure of the links and its leader is its smallest node.  label[x] starts as x, or as a
+// negative value for a node that takes no part: such a node is skipped wherever it turns up and never touched.  The host repeats
+// { flag = 0; hook; flag down -> done; compress } (labels.fixed_point).
+//   hook      every link (x, y) walks label from x and from y to the ends rx, ry; when rx != ry: atomicMin(&label[max(rx, ry)], min(rx, ry)).
+//   compress  every node walks label to the end of its walk and stores it in its own slot.
+//   I1  label[x] <= x.                        It starts as x; a hook stores a min below the slot's index, compress an end of a descending walk.
+//   I2  label[x] lies in x's component.       A hook joins the ends of the walks of two linked nodes; every node of a walk is a label of the
+//                                             node before it, so by induction it lies in the component of the node the walk began at.
+//   Labels only fall: atomicMin, and compress stores the end of a walk that began at the slot's own value.
+//   Stale reads.  No kernel relies on seeing another workgroup's write inside its launch (the L2s of the XCDs are not coherent for plain
+//   loads).  Every label is read by ONE relaxed device-scope atomic load, so the range check and the use see the same value, and the
+//   value is the one the slot has or an earlier one.  An earlier one satisfies I1 and I2 as well, so a stale read can only end a walk early,
+//   at a node that is a root no longer.  The atomicMin onto it is harmless (I1, I2 hold, the label cannot rise) and the flag it may raise
+//   costs one more round, never the result.
+//   The fixed point is decided by what a fresh launch reads: a hook launch that leaves the flag down has written nothing that changed a
+//   label (under either flag rule below), so every read in it saw the memory as the launches before left it, and in that memory both ends
+//   of every link have the same root.  Then every component has one root, by I1 no node of it lies below its root, and the compress before
+//   made every label a root: label[x] is the leader.
+//   Progress: in a launch that starts away from the fixed point the first atomicMin in time comes from a thread that read the starting
+//   state only; its larger end is a true root there and falls strictly.  Labels are bounded below, so the rounds end on any input.
+//   Bounds of a walk: it steps from x to label[x] only when 0 <= label[x] < x, so it descends, takes at most x steps and reads no slot
+//   outside [0, x]; a label outside [0, x] ends it at x like a root.
+//   The flag rule is the stage's: join_ends below raises the flag only when a label fell (weld, manifold: a launch raises it exactly when it
+//   changed a label); the hook of pps_pieces.hip raises it whenever the two ends differ.  Both are down at the fixed point and only there.
 #pragma once
 #include <stdint.h>
 
@@ -20,4 +42,15 @@ __device__ __forceinline__ int walk_end(const int32_t* label, int x) {
         if (p < 0 || p >= x) return x;
         x = p;
     }
+}
+
+// the nodes x, y (0 <= x, y < n and both taking part, by the caller) are linked: their ends are joined, and the flag goes up only when a
+// label fell (the value the atomic returns: when another thread had lowered the slot as far already, that thread raised the flag).
+// pps_pieces.hip's hook keeps its own body (an atomicMin without a return, the flag up whenever the ends differ): the cost of the
+// returning form on its first round is unmeasured.
+__device__ __forceinline__ void join_ends(int32_t* label, int x, int y, int32_t* changed) {
+    const int rx = walk_end(label, x), ry = walk_end(label, y);
+    if (rx == ry) return;
+    const int low = rx > ry ? ry : rx;
+    if (atomicMin(label + (rx > ry ? rx : ry), low) > low) *changed = 1;
 }

@@ -2,8 +2,8 @@
 // vertices.
 //
 // new capability: replaces nothing -- the reference has no such stage, and the stages of sections 19 to 23 step around non-manifold geometry
-// without repairing it.  Driven by ppsurf_amd/manifold.py (the pairs and their edge slots by ppsurf_amd/topology.py, the compress launch
-// is ppsx_pieces_compress of pps_pieces.hip, which is generic); restated in numpy by tests/manifold_spec.py (a plain union-find over
+// without repairing it.  Driven by ppsurf_amd/manifold.py (the pairs and their edge slots by ppsurf_amd/topology.py, the loop and the compress
+// launch by ppsurf_amd/labels.py); restated in numpy by tests/manifold_spec.py (a plain union-find over
 // corners), which the kernels match byte for byte.
 //
 // The rule: vertices V [nv,3], faces F int64 [nf,3], nv, nf <= 2^31 - 1, 3 nf <= 2^31 - 1.  A pure function of the ordered mesh.
@@ -29,28 +29,13 @@
 // a path of one fan into a cycle, so a second run finds one fan per vertex: the stage is idempotent.  The cut closes nothing: the faces of a
 // many-owner edge that the fans do not pair become borders.
 //
-// Labelling (hook_kernel, and compress_kernel of pps_pieces.hip on the 3 nf corner labels), section 21's on corners with the links found on
-// the fly: label[c] starts as c, -1 for a corner of an invalid face.  The host repeats { flag = 0; hook; flag down -> done; compress }.
-//   hook      one thread per pair; both of its unions are done in that thread, so no link list is materialised.  A union of the corners
-//             x, y walks label from x and from y to the ends rx, ry and, when rx != ry, does atomicMin(&label[max(rx, ry)], min(rx, ry));
-//             the flag goes up when that made the label fall (the value the atomic returns: when another thread had lowered the slot as far
-//             already, that thread raised the flag).  This is section 24's rule: a launch raises the flag exactly when it changed a label,
-//             labels only fall and are bounded below, and the host loop ends on any input.
-//   compress  every corner walks label to the end of its walk and stores it in its own slot.
-//   A corner with a negative label takes no part: a union onto it is skipped and it is never touched.
-//   I1  label[c] <= c.                       It starts as c; a hook stores a min below the slot's index, compress an end of a descending walk.
-//   I2  label[c] lies in c's fan.            A hook joins the ends of the walks of two linked corners; every node of a walk is a label of the
-//                                            node before it, so by induction it lies in the fan of the corner the walk began at.
-//   Labels only fall.  No kernel relies on seeing another workgroup's write inside its launch (the L2s of the XCDs are not coherent for
-//   plain loads): every label is read by ONE relaxed device-scope atomic load (pps_labels.h), which returns the value a slot has or an
-//   earlier one, and an earlier one satisfies I1 and I2 as well, so a stale read can only end a walk early.  The atomicMin onto such an end
-//   is harmless and the flag it raises costs one more round, never the result.  The end is decided by what a fresh launch reads: a hook
-//   launch that leaves the flag down has changed nothing, so every read in it saw the memory as the launches before left it, and in that
-//   memory both ends of every link have the same root.  Then every fan has one root, by I1 no corner of it lies below its root, and the
-//   compress before made every label a root: label[c] is the leader.  Progress: as in pps_pieces.hip, the first atomicMin in time of a
-//   launch that starts away from the fixed point lowers a true root strictly, and labels are bounded below.
-//   A walk steps from x to label[x] only when 0 <= label[x] < x: it descends, takes at most x steps and reads no slot outside [0, x]; a
-//   label outside [0, x] ends it at x like a root.
+// Labelling (hook_kernel here, the compress of pps_labels.hip on the 3 nf corner labels; the argument is written out in pps_labels.h).  A
+// node is a corner, a link as above, found on the fly: label[c] starts as c, -1 for a corner of an invalid face.
+//   hook      one thread per pair; both of its unions are done in that thread, so no link list is materialised.  A union joins the ends of
+//             its two corners (join_ends of pps_labels.h): the flag goes up only when a label fell, so a launch raises it exactly when it
+//             changed a label.
+//   skipped   a union onto a corner with a negative label; a pair with a face, a slot or a corner vertex out of range or without a common
+//             edge.
 //
 // Shape: hook_kernel one thread per pair; faces_kernel one thread per face.  Plain vector loads and stores, integer atomics only, no LDS,
 // no scratch.  Everything read is range-checked before it becomes an address: the face indices and the slots of a pair, the vertex indices
@@ -65,10 +50,7 @@ namespace {
 // the corners x, y (0 <= x, y < 3 nf, by the caller) are linked: their ends are joined
 __device__ __forceinline__ void join(int32_t* label, int x, int y, int32_t* changed) {
     if (load_label(label, x) < 0 || load_label(label, y) < 0) return;                       // a corner that takes no part
-    const int rx = walk_end(label, x), ry = walk_end(label, y);
-    if (rx == ry) return;
-    const int low = rx > ry ? ry : rx;
-    if (atomicMin(label + (rx > ry ? rx : ry), low) > low) *changed = 1;                    // the flag goes up only when a label fell
+    join_ends(label, x, y, changed);
 }
 
 __global__ __launch_bounds__(256) void hook_kernel(const int64_t* __restrict__ faces, int64_t nf, int64_t nv, const int32_t* __restrict__ fa,

@@ -26,34 +26,25 @@
 // A pure function of (V, F, mode): no dependence on the launch shape or on timing.
 //
 // Labelling with a parity (hook_kernel, compress_kernel) over the pairs fa, fb, s.  word[f] = (parent << 1) | flip of f relative to that
-// parent, one int64 per face; it starts as f << 1 and is -1 for an invalid face, which is never touched.  The host repeats
-// { flag = 0; hook; flag down -> done; compress }, as pieces._labels does.
+// parent, one int64 per face; it starts as f << 1 and is -1 for an invalid face, which is never touched.  The loop is the labelling
+// layer's (labels.fixed_point) and the argument is that of pps_labels.h with the parent part of a word as the label; the walk, the hook
+// and the compress are this file's own because the state is a different word.  What the parity adds:
 //   hook      a pair (a, b, s) walks from a and from b to the ends (ra, qa), (rb, qb): a walk steps from x to its parent p while
 //             0 <= p < x and XORs the flips it passes.  When ra != rb: atomicMin(&word[max(ra, rb)], (min(ra, rb) << 1) | (qa ^ qb ^ s))
-//             and the flag goes up.
+//             and the flag goes up (whenever the ends differ, as in pps_pieces.hip).
 //   compress  every face stores (the end of its walk << 1) | the parity of that walk in its own slot.
-//   Hook launches only issue atomicMins, compress launches only store into the thread's own slot.
-//   I1  parent(f) <= f.                       The word starts as f << 1; a hook stores a parent below the slot's index -- a root's word
-//                                             is x << 1 and (min << 1) | 1 < max << 1 -- and compress the end of a descending walk.
-//   I2  parent(f) lies in f's component.      As I2 of pps_pieces.hip.
+//   skipped   a pair entry outside [0, nf) or onto a face with a negative word.
+//   I1  holds for the packed words too: a root's word is x << 1 and (min << 1) | 1 < max << 1, so a hook stores a parent below the slot.
 //   I3  in an orientable component the flip of word[f] is flip[f] ^ flip[parent(f)].   It holds at the start (0 to itself).  A walk XORs
 //                                             such relations, so its parity is flip[start] ^ flip[end]; the hook's value states
 //                                             flip[max] ^ flip[min] = qa ^ qb ^ s because flip[a] ^ flip[b] = s; compress stores a walk's.
 //   The parent parts order the packed words (the flip is the lowest bit), so they evolve exactly as the labels of pps_pieces.hip: an
 //   atomicMin lowers the parent when the new one is smaller, and between two values with one parent it keeps the flip 0 -- by I3 both
 //   flips are equal in an orientable component, and in a non-orientable one no flip is used.  The fixed point therefore has the leaders of
-//   face_components.
-//   No kernel relies on seeing another workgroup's write inside its launch (the L2s of the XCDs are not coherent for plain loads).  Every
-//   word is read by ONE relaxed device-scope atomic load of 8 bytes, so parent and flip come from the same snapshot and the range check
-//   and the use see the same value.  A stale read returns an earlier word, and by I1 - I3 an earlier word states a true relation as well:
-//   it can only end a walk early, at a node that is a root no longer.  The atomicMin onto it is harmless (the invariants hold, the parent
-//   cannot rise) and the flag it raises costs one more round, never the result.
-//   The end is decided by what a fresh launch reads: a hook launch that leaves the flag down has written nothing, so every read in it saw
-//   the memory as the launches before left it, and there both faces of every pair have the same root.  Then every component has one root,
-//   the compress before made every word (root << 1) | parity of the walk to it, and by I3 that parity is flip[f] ^ flip[leader] = flip[f].
-//   Progress and the bound on a walk are those of pps_pieces.hip: the first atomicMin in time of a launch away from the fixed point
-//   lowers a true root; a walk descends, ends after at most f steps and reads no slot outside [0, f]; a parent outside [0, x) ends it
-//   at x like a root.  The rounds are those of the labels without a parity: the parity rides on the same words and adds no dependency.
+//   face_components, and the rounds are those of the labels without a parity: the parity adds no dependency.
+//   Every word is read by ONE relaxed device-scope atomic load of 8 bytes, so parent and flip come from the same snapshot; a stale read
+//   returns an earlier word, which by I1 - I3 states a true relation as well.  At the fixed point the compress before made every word
+//   (root << 1) | parity of the walk to it, and by I3 that parity is flip[f] ^ flip[leader] = flip[f].
 //   In a non-orientable component the flips depend on the path and so on timing; check_kernel only establishes that some pair fails.
 //
 // Shape: pair_sign, hook and check one thread per pair; compress and apply one thread per face; block_sums one wave per block of 256

@@ -23,26 +23,12 @@
 //   output        the kept faces in their given order; the vertices no kept face references dropped, order kept, faces re-indexed (host).
 // A pure function of (V, F, rules): no dependence on the launch shape or on timing.
 //
-// Labelling (hook_kernel, compress_kernel) over the pair list fa, fb int32 [np] (the edges with exactly two owners).  label[f] starts as f,
-// -1 for an invalid face, which is never touched.  The host repeats { flag = 0; hook; flag down -> done; compress }.
+// Labelling (hook_kernel here, the compress of pps_labels.hip; the argument is written out in pps_labels.h).  A node is a face, a link a
+// pair of the list fa, fb int32 [np] (the edges with exactly two owners); label[f] starts as f, -1 for an invalid face.
 //   hook      a pair (a, b) walks label from a and from b to the ends ra, rb; when ra != rb: atomicMin(&label[max(ra, rb)], min(ra, rb)) and
-//             the flag goes up.
-//   compress  every face walks label to the end of its walk and stores it in its own slot.
-//   I1  label[f] <= f.                        It starts as f; a hook stores a min below the slot's index, compress an end of a descending walk.
-//   I2  label[f] lies in f's component.       A hook joins the ends of the walks of two adjacent faces; every node of a walk is a label of the
-//                                             node before it, so by induction it lies in the component of the face the walk began at.
-//   Labels only fall: atomicMin, and compress stores the end of a walk that began at the slot's own value.  No kernel relies on seeing
-//   another workgroup's write inside its launch (the L2s of the XCDs are not coherent for plain loads): a read returns the value a slot
-//   has or an earlier one, and an earlier one satisfies I1 and I2 as well, so a stale read can only end a walk early, at a node that is a
-//   root no longer.  The atomicMin onto it is harmless (I1, I2 hold, the label cannot rise) and the flag it raises costs one more round.
-//   Every value is read by ONE relaxed device-scope atomic load, so the range check and the use see the same value.
-//   The end is decided by what a fresh launch reads: a hook launch that leaves the flag down has written nothing, so every read in it saw the
-//   memory as the launches before left it, and in that memory both faces of every pair have the same root.  Then every component has one
-//   root, by I1 no face of it lies below its root, and the compress before made every label a root: label[f] is the leader.  Progress: in a
-//   launch that starts away from the fixed point the first atomicMin in time comes from a thread that read the starting state only, its
-//   larger end is a true root there and falls strictly; labels are bounded below, so the rounds end.
-//   A walk steps from x to label[x] only when 0 <= label[x] < x, so it descends, ends after at most f steps and reads no slot outside
-//   [0, f]; a label outside [0, x] ends it at x like a root.  A pair entry outside [0, nf) or onto a face with a negative label is skipped.
+//             the flag goes up -- whenever the ends differ, not only when the label fell: a launch that leaves the flag down has issued no
+//             atomic at all.
+//   skipped   a pair entry outside [0, nf) or onto a face with a negative label.
 //
 // Statistics (stats_kernel): count, lo and hi by integer atomics -- exact in any order -- after combining on chip.  One destination per
 // face would send 7 atomics per face of a one-component sphere to seven addresses.  Per wave: the lanes that share the component of the
@@ -53,7 +39,7 @@
 // init_kernel writes the images of +inf / -inf and zero counts before, decode_kernel turns the images back into floats after.
 //
 // Shape: edge_keys_kernel one thread per face, three 8-byte stores (as half_edges_kernel of pps_smooth.hip); hook_kernel one thread per pair;
-// compress_kernel one thread per face; stats_kernel 1024 threads, one per face, 576 bytes of LDS (a component number and a box per wave); select_kernel one thread per component.
+// stats_kernel 1024 threads, one per face, 576 bytes of LDS (a component number and a box per wave); select_kernel one thread per component.
 // Every index is range-checked before it becomes an address.  The atomics are ordinary device-scope vector atomics.
 #include <math.h>
 
@@ -99,13 +85,6 @@ __global__ __launch_bounds__(256) void hook_kernel(const int32_t* __restrict__ f
     if (ra == rb) return;
     atomicMin(label + (ra > rb ? ra : rb), ra > rb ? rb : ra);
     *changed = 1;
-}
-
-__global__ __launch_bounds__(256) void compress_kernel(int32_t* label, int64_t nf) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf) return;
-    if (load_label(label, f) < 0) return;                   // an invalid face is never touched
-    label[f] = walk_end(label, (int)f);
 }
 
 __global__ __launch_bounds__(256) void stats_init_kernel(int64_t* __restrict__ count, int* __restrict__ lo, int* __restrict__ hi, int64_t nc) {
@@ -269,14 +248,6 @@ int ppsx_pieces_hook(const int32_t* fa, const int32_t* fb, int64_t np, int32_t* 
     if (np == 0 || nf == 0) return PPS_OK;
     if (!fa || !fb || !label || !changed) return PPS_ERR_ARG;
     hipLaunchKernelGGL(hook_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fa, fb, np, label, nf, changed);
-    return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
-}
-
-int ppsx_pieces_compress(int32_t* label, int64_t nf, void* stream) {
-    if (nf < 0 || too_many(nf)) return PPS_ERR_ARG;
-    if (nf == 0) return PPS_OK;
-    if (!label) return PPS_ERR_ARG;
-    hipLaunchKernelGGL(compress_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (hipStream_t)stream, label, nf);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 

@@ -16,28 +16,12 @@
 //              one cluster; code 0: kept, its corners renumbered, its winding as given.
 // A pure function of (V, F, eps): no dependence on the cell grid, the table capacity, the launch shape or on timing.
 //
-// Labelling (hook_kernel, compress_kernel), section 21's on vertices with the links found on the fly: label[v] starts as v.  The host
-// repeats { flag = 0; hook; flag down -> done; compress }.
-//   hook      vertex i visits every j < i it is linked to, walks label from i and from j to the ends ri, rj and, when ri != rj, does
-//             atomicMin(&label[max(ri, rj)], min(ri, rj)); the flag goes up when that made the label fall (the value the atomic returns:
-//             when another thread had lowered the slot as far already, that thread raised the flag).  So a launch raises the flag exactly
-//             when it changed a label, labels only fall and are bounded below, and the host loop ends on any input.  No pair list is kept:
-//             k copies of one point are k k / 2 pairs.
-//   compress  every vertex walks label to the end of its walk and stores it in its own slot.
-//   A vertex with a negative label takes no part, like an invalid face of section 21: it is skipped as i and as j and never touched.
-//   I1  label[v] <= v.                       It starts as v; a hook stores a min below the slot's index, compress an end of a descending walk.
-//   I2  label[v] lies in v's cluster.        A hook joins the ends of the walks of two linked vertices; every node of a walk is a label of the
-//                                            node before it, so by induction it lies in the cluster of the vertex the walk began at.
-//   Labels only fall.  No kernel relies on seeing another workgroup's write inside its launch (the L2s of the XCDs are not coherent for
-//   plain loads): every label is read by ONE relaxed device-scope atomic load, which returns the value a slot has or an earlier one, and an
-//   earlier one satisfies I1 and I2 as well, so a stale read can only end a walk early.  The atomicMin onto such an end is harmless and the
-//   flag it raises costs one more round, never the result.  The end is decided by what a fresh launch reads: a hook launch that leaves the
-//   flag down has changed nothing, so every read in it saw the memory as the launches before left it, and in that memory both ends of every
-//   link have the same root.  Then every cluster has one root, by I1 no vertex of it lies below its root, and the compress before made
-//   every label a root: label[v] is the leader.  Progress: as in pps_pieces.hip, the first atomicMin in time of a launch that starts away
-//   from the fixed point lowers a true root strictly, and labels are bounded below.
-//   A walk steps from x to label[x] only when 0 <= label[x] < x: it descends, takes at most x steps and reads no slot outside [0, x]; a
-//   label outside [0, x] ends it at x like a root.
+// Labelling (hook_kernel here, the compress of pps_labels.hip; the argument is written out in pps_labels.h).  A node is a vertex, a link
+// a pair of rows within eps, found on the fly: label[v] starts as v.
+//   hook      vertex i visits every j < i it is linked to and joins their ends (join_ends of pps_labels.h): the flag goes up only when a
+//             label fell, so a launch raises it exactly when it changed a label.  No pair list is kept: k copies of one point are
+//             k k / 2 pairs.
+//   skipped   a vertex with a negative label, as i and as j; an order entry outside [0, i).
 //
 // Candidates of vertex i (the point query of section 15's argument): per axis the interval p_i -+ R, R = eps (1 + 2^-20), computed in fp64
 // and rounded OUTWARD to f32; the cell range is cell_of(lower) .. cell_of(upper) with the cell_of that placed the points, which is monotone,
@@ -49,8 +33,8 @@
 // The cell edge only sets the work: no result depends on it.
 //
 // Shape: hook_kernel one thread per vertex, a serial walk over its cells (at most 27 to 64 with a cell edge >= eps) and their runs of
-// `order`; compress_kernel one thread per vertex; faces_kernel one thread per face.  Plain vector loads and stores, integer atomics only, no
-// LDS.  Every index read from order, offsets, label, faces or newrow is range-checked before it becomes an address.
+// `order`; faces_kernel one thread per face.  Plain vector loads and stores, integer atomics only, no LDS.  Every index read
+// from order, offsets, label, faces or newrow is range-checked before it becomes an address.
 #include <math.h>
 
 #include "pps_cells.h"
@@ -73,10 +57,7 @@ __device__ __forceinline__ void visit(const float* __restrict__ pts, const Query
     const double dx = q.x - (double)pts[3 * (int64_t)j], dy = q.y - (double)pts[3 * (int64_t)j + 1], dz = q.z - (double)pts[3 * (int64_t)j + 2];
     if (!(((dx * dx + dy * dy) + dz * dz) <= q.eps2)) return;
     if (load_label(label, j) < 0) return;                                                   // a vertex that takes no part
-    const int ri = walk_end(label, q.i), rj = walk_end(label, j);
-    if (ri == rj) return;
-    const int low = ri > rj ? rj : ri;
-    if (atomicMin(label + (ri > rj ? ri : rj), low) > low) *changed = 1;                    // the flag goes up only when a label fell
+    join_ends(label, q.i, j, changed);
 }
 
 __global__ __launch_bounds__(256) void hook_kernel(const float* __restrict__ pts, int64_t n, Grid grid, const u64* __restrict__ table, u64 mask,
@@ -108,12 +89,6 @@ __global__ __launch_bounds__(256) void hook_kernel(const float* __restrict__ pts
                     if (j >= 0 && j < i) visit(pts, q, (int)j, label, changed);
                 }
             }
-}
-
-__global__ __launch_bounds__(256) void compress_kernel(int32_t* label, int64_t n) {
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n || load_label(label, v) < 0) return;           // a vertex with a negative label is never touched
-    label[v] = walk_end(label, (int)v);
 }
 
 __global__ __launch_bounds__(256) void faces_kernel(const int64_t* __restrict__ faces, int64_t nf, int64_t nv, const int64_t* __restrict__ newrow,
@@ -151,14 +126,6 @@ int ppsx_weld_hook(const float* pts, int64_t n, const float* lo, const float* hi
     const double eps2 = eps * eps;
     hipLaunchKernelGGL(hook_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pts, n, grid, (const u64*)table,
                        (u64)(capacity - 1), order, offsets, eps, eps2, label, changed);
-    return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
-}
-
-int ppsx_weld_compress(int32_t* label, int64_t n, void* stream) {
-    if (n < 0 || too_many(n)) return PPS_ERR_ARG;
-    if (n == 0) return PPS_OK;
-    if (!label) return PPS_ERR_ARG;
-    hipLaunchKernelGGL(compress_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, label, n);
     return hipGetLastError() == hipSuccess ? PPS_OK : PPS_ERR_LAUNCH;
 }
 

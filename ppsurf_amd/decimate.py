@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -160,27 +160,18 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.decimate')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    local32 = meshio.centred_f32(verts, centre)
-    local, f = torch.from_numpy(local32).to(dev), torch.from_numpy(faces).to(dev)
-    if local.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT:
-        raise SystemExit('{} has more than 2^31 - 1 vertices or faces'.format(args.mesh))
-    kept, out_v, out_f, info = _decimate_rows(local, f, max_faces, max_rounds)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.decimate')
+    kept, out_v, out_f, info = _decimate_rows(*mesh.to_device(limit='faces'), max_faces, max_rounds)
     if kept is None:
-        meshio.write_ply_mesh(args.out_file, verts, faces, double=double, colors_u8=colors)
+        mesh.write_as_read(args.out_file)
     else:
         # a vertex that never moved is written as read; a moved one from its float32 position
         kept, out_v = kept.cpu().numpy(), out_v.cpu().numpy()
-        moved = (out_v.view(np.int32) != local32[kept].view(np.int32)).any(axis=1)
-        pos = np.asarray(verts, dtype=np.float64)[kept]
-        pos[moved] = out_v[moved].astype(np.float64) + centre[None]
-        meshio.write_ply_mesh(args.out_file, pos, out_f.cpu().numpy(), double=double, colors_u8=None if colors is None else np.asarray(colors)[kept])
+        moved = (out_v.view(np.int32) != mesh.local32[kept].view(np.int32)).any(axis=1)
+        pos = np.asarray(mesh.verts, dtype=np.float64)[kept]
+        pos[moved] = out_v[moved].astype(np.float64) + mesh.centre[None]
+        meshio.write_ply_mesh(args.out_file, pos, out_f.cpu().numpy(), double=mesh.double,
+                              colors_u8=None if mesh.colors is None else np.asarray(mesh.colors)[kept])
     print(json.dumps(info))
     return info
 

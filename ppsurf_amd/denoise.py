@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_ITERS = 1000
@@ -109,17 +109,9 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.denoise')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
-    out_v, _, info = denoise_mesh(local, torch.from_numpy(np.asarray(faces, dtype=np.int64).reshape(-1, 3)).to(dev), threshold, normal_iters,
-                                  vertex_iters)
-    out_v = out_v.cpu().numpy().astype(np.float64) + centre[None]
-    meshio.write_ply_mesh(args.out_file, out_v, faces, double=double, colors_u8=colors)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.denoise')
+    out_v, _, info = denoise_mesh(*mesh.to_device(), threshold, normal_iters, vertex_iters)
+    mesh.write_moved(args.out_file, out_v)
     print(json.dumps(info))
     return info
 

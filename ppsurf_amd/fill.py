@@ -15,7 +15,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here like from the siblings)
 
 MAX_EDGES = 4096
@@ -98,21 +98,15 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.fill')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    nv = int(verts.shape[0])
-    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
-    out_v, out_f, info = fill_holes(local, torch.from_numpy(np.asarray(faces, dtype=np.int64).reshape(-1, 3)).to(dev), max_edges)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.fill')
+    nv, colors = int(mesh.verts.shape[0]), mesh.colors
+    out_v, out_f, info = fill_holes(*mesh.to_device(), max_edges)
     out_f = out_f.cpu().numpy()
     # the old vertices keep the file's own values; only the new ones come back from the centred float32 frame
-    out_v = np.concatenate([verts, out_v[nv:].cpu().numpy().astype(np.float64) + centre[None]])
+    out_v = np.concatenate([mesh.verts, out_v[nv:].cpu().numpy().astype(np.float64) + mesh.centre[None]])
     if colors is not None:
-        colors = np.concatenate([colors, loop_colors(colors, out_f[faces.shape[0]:], nv)])
-    meshio.write_ply_mesh(args.out_file, out_v, out_f, double=double, colors_u8=colors)
+        colors = np.concatenate([colors, loop_colors(colors, out_f[mesh.faces.shape[0]:], nv)])
+    meshio.write_ply_mesh(args.out_file, out_v, out_f, double=mesh.double, colors_u8=colors)
     print(json.dumps(info))
     return info
 

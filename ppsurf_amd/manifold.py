@@ -20,10 +20,9 @@ switch for this stage: run the command on the PLY that `pps.py rec` or another s
 import json
 import sys
 
-import numpy as np
 import torch
 
-from . import _lib, meshio, pieces, topology
+from . import _lib, labels, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -44,14 +43,8 @@ def _fans(f, nv, fa, fb, ea, eb, valid):
     label = torch.where(valid.repeat_interleave(3), own, torch.full_like(own, -1))
     pairs, rounds = int(fa.shape[0]), 0
     if pairs > 0:
-        changed = torch.zeros(1, dtype=torch.int32, device=f.device)
-        while True:
-            changed.zero_()
-            _lib.call('ppsx_manifold_hook', f, nf, nv, fa, fb, ea, eb, pairs, label, changed)
-            rounds += 1
-            if int(changed.item()) == 0:
-                break
-            pieces.compress_labels(label, 3 * nf)
+        rounds = labels.fixed_point(lambda changed: _lib.call('ppsx_manifold_hook', f, nf, nv, fa, fb, ea, eb, pairs, label, changed),
+                                    lambda: labels.compress(label, 3 * nf), f.device)
     return label, rounds
 
 
@@ -61,7 +54,7 @@ def _rows(f, nv, label):
     identity elsewhere, never read), source is the given row of every output row and fans the number of fans at every given vertex.
     Integer work on small tables in torch."""
     nc, dev = int(label.shape[0]), f.device
-    leader = torch.nonzero(label == torch.arange(nc, dtype=torch.int32, device=dev)).reshape(-1)          # ascending
+    leader = torch.nonzero(label == torch.arange(nc, dtype=torch.int32, device=dev)).reshape(-1)   # ascending (no numbers: not labels.leaders)
     at = f.reshape(-1)[leader]                                                                         # the vertex every fan names
     first = torch.full((nv,), nc, dtype=torch.int64, device=dev).scatter_reduce_(0, at, leader, 'amin')
     extra = first[at] != leader
@@ -147,24 +140,12 @@ def main(argv=None):
     ap.add_argument('out_file', help='PLY mesh with the split vertices appended')
     args = ap.parse_args(argv)
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.manifold')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    local, f = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev), torch.from_numpy(faces).to(dev)
-    if local.shape[0] > MAX_COUNT or 3 * f.shape[0] > MAX_COUNT:
-        raise SystemExit('{} has more than 2^31 - 1 vertices or corners'.format(args.mesh))
-    # the vertices (and colours) are written as read, gathered through the source rows: the stage works on row numbers
-    source, out, info = _split_rows(local, f)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.manifold')
+    source, out, info = _split_rows(*mesh.to_device(limit='corners'))
     if out is None:
-        meshio.write_ply_mesh(args.out_file, verts, faces, double=double, colors_u8=colors)
+        mesh.write_as_read(args.out_file)
     else:
-        source = source.cpu().numpy()
-        meshio.write_ply_mesh(args.out_file, verts[source], out.cpu().numpy(), double=double,
-                              colors_u8=None if colors is None else np.asarray(colors)[source])
+        mesh.write_rows(args.out_file, source, out)
     print(json.dumps(info))
     return info
 

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, ops, topology
+from . import _lib, mesh_cli, meshio, ops, topology
 from .topology import CpuTensorError, vertex_incidence  # noqa: F401  (their home is topology.py; the names stay importable from here)
 
 MAX_K = 256
@@ -114,25 +114,19 @@ def main(argv=None):
     if (args.points is None) != (args.points_out is None):
         ap.error('--points and --points_out go together')
     meshio.need_ply_output(ap, args.out_file, args.points_out, plural=True)
-    _lib.need_gpu('python -m ppsurf_amd.normals')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    local = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev)
-    dev_faces = torch.from_numpy(np.asarray(faces, dtype=np.int64).reshape(-1, 3)).to(dev)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.normals')
+    local, dev_faces = mesh.to_device()
     nrm, info = vertex_normals(local, dev_faces, weight)
-    meshio.write_ply_mesh(args.out_file, verts, faces, double=double, normals=nrm.cpu().numpy(), colors_u8=colors)
+    mesh.write_as_read(args.out_file, normals=nrm)
     if args.points is not None:
         pts = np.asarray(meshio.load_pts(args.points))[:, :3].astype(np.float64)
         if not np.isfinite(pts).all():
             raise SystemExit('{} has non-finite points'.format(args.points))
-        if verts.shape[0] == 0:
+        if mesh.verts.shape[0] == 0:
             raise SystemExit('{} has no vertices to take normals from'.format(args.mesh))
         pts_double = os.path.splitext(args.points)[1].lower() == '.las' or (
             os.path.splitext(args.points)[1].lower() == '.ply' and meshio.ply_stores_doubles(args.points))
-        scan = torch.from_numpy(meshio.centred_f32(pts, centre)).to(dev)                   # the scan on the mesh's centre: one frame
+        scan = torch.from_numpy(meshio.centred_f32(pts, mesh.centre)).to(local.device)                 # the scan on the mesh's centre: one frame
         pn, pinfo = point_normals(scan, local, dev_faces, k=k, weight=weight)
         meshio.write_ply_points_normals(args.points_out, pts, pn.cpu().numpy(), double=pts_double)
         info = dict(info, points=pinfo['points'], k=pinfo['k'], zero_point_normals=pinfo['zero_normals'])

@@ -16,10 +16,9 @@ welded here: a soup of unconnected triangles is one component per face and comes
 import json
 import sys
 
-import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, labels, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -51,14 +50,8 @@ def _parity_labels(f, fa, fb, ea, eb, valid):
     if pairs > 0:
         sign = torch.empty(pairs, dtype=torch.uint8, device=dev)
         _lib.call('ppsx_orient_pair_sign', f, nf, fa, fb, ea, eb, pairs, sign)
-        changed = torch.zeros(1, dtype=torch.int32, device=dev)
-        while True:
-            changed.zero_()
-            _lib.call('ppsx_orient_hook', fa, fb, sign, pairs, word, nf, changed)
-            rounds += 1
-            if int(changed.item()) == 0:
-                break
-            _lib.call('ppsx_orient_compress', word, nf)
+        rounds = labels.fixed_point(lambda changed: _lib.call('ppsx_orient_hook', fa, fb, sign, pairs, word, nf, changed),
+                                    lambda: _lib.call('ppsx_orient_compress', word, nf), dev)
         _lib.call('ppsx_orient_check', fa, fb, sign, pairs, word, nf, bad)
     label = torch.where(valid, word >> 1, word).to(torch.int32)
     flip = (word & 1).to(torch.uint8) * valid
@@ -92,17 +85,15 @@ def _volumes(v, f, flip, cid, leader, need, faces_c):
 
 def _oriented(v, f, mode):
     """(faces or None, info) of a checked device mesh and a checked mode; None when nothing turns."""
-    nv, nf, dev = int(v.shape[0]), int(f.shape[0]), f.device
+    nv, nf = int(v.shape[0]), int(f.shape[0])
     label, flip, bad, valid, fa, _ = _flips(f, nv)
-    leads = valid & (label == torch.arange(nf, dtype=torch.int32, device=dev))
-    leader = torch.nonzero(leads).reshape(-1)
+    _, leader, number = labels.leaders(label, live=valid)
     nc = int(leader.shape[0])
     info = {'faces_in': nf, 'faces_valid': int(valid.sum().item()), 'faces_flipped': 0, 'components': nc, 'components_closed': 0,
             'components_open': 0, 'components_non_orientable': 0, 'faces_non_orientable': 0, 'components_flipped': 0, 'zero_volume': 0,
             'mode': mode}
     if nc == 0:
         return None, info
-    number = torch.cumsum(leads, 0) - 1
     cid = torch.where(valid, number[label.clamp(min=0).long()], torch.full_like(number, -1)).to(torch.int32)
     live = cid[valid].long()
     faces_c = torch.bincount(live, minlength=nc)
@@ -172,19 +163,9 @@ def main(argv=None):
                     help='outward / inward: by the signed volume of every closed component; majority: the larger half of every component stays')
     args = ap.parse_args(argv)
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.orient')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    local, f = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev), torch.from_numpy(faces).to(dev)
-    if local.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT:
-        raise SystemExit('{} has more than 2^31 - 1 vertices or faces'.format(args.mesh))
-    # the vertices (and colours) are written as read: the stage works on row numbers and on the centred float32 copy
-    out, info = _oriented(local, f, args.mode)
-    meshio.write_ply_mesh(args.out_file, verts, faces if out is None else out.cpu().numpy(), double=double, colors_u8=colors)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.orient')
+    out, info = _oriented(*mesh.to_device(limit='faces'), args.mode)
+    mesh.write_as_read(args.out_file, faces=out)
     print(json.dumps(info))
     return info
 

@@ -19,7 +19,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, labels, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -49,12 +49,6 @@ def _checked_rules(min_faces, min_diag_frac, keep_largest):
     return min_faces, min_diag_frac, keep_largest
 
 
-def compress_labels(label, n):
-    """Every slot of label int32 [n] with a label >= 0 gets the end of its descending walk (ppsx_pieces_compress): the step between two
-    hooking rounds, here on face labels and in manifold.py on corner labels."""
-    _lib.call('ppsx_pieces_compress', label, n)
-
-
 def _labels(f, nv):
     """(label int32 [nf], valid bool [nf], rounds) of contiguous device faces: hooking and compressing until a hook launch changes nothing.
     The rounds depend on the face order and on timing; the labels do not."""
@@ -64,14 +58,8 @@ def _labels(f, nv):
     label = torch.where(valid, own, torch.full_like(own, -1))
     pairs, rounds = int(fa.shape[0]), 0
     if pairs > 0:
-        changed = torch.zeros(1, dtype=torch.int32, device=f.device)
-        while True:
-            changed.zero_()
-            _lib.call('ppsx_pieces_hook', fa, fb, pairs, label, nf, changed)
-            rounds += 1
-            if int(changed.item()) == 0:
-                break
-            compress_labels(label, nf)
+        rounds = labels.fixed_point(lambda changed: _lib.call('ppsx_pieces_hook', fa, fb, pairs, label, nf, changed),
+                                    lambda: labels.compress(label, nf), f.device)
     return label, valid, rounds
 
 
@@ -86,10 +74,8 @@ def _table(v, f):
     `rounds` next to the entries of `component_table`."""
     nv, nf, dev = int(v.shape[0]), int(f.shape[0]), f.device
     label, valid, rounds = _labels(f, nv)
-    leads = label == torch.arange(nf, dtype=torch.int32, device=dev)
-    leader = torch.nonzero(leads).reshape(-1)
+    _, leader, number = labels.leaders(label)
     nc = int(leader.shape[0])
-    number = torch.cumsum(leads, 0) - 1
     cid = torch.where(valid, number[label.clamp(min=0).long()], torch.full_like(number, -1)).to(torch.int32)
     count = torch.empty(nc, dtype=torch.int64, device=dev)
     lo, hi = torch.empty(nc, 3, dtype=torch.float32, device=dev), torch.empty(nc, 3, dtype=torch.float32, device=dev)
@@ -205,23 +191,12 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.pieces')
-    verts, faces, colors, double = meshio.read_mesh_file(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    local, f = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev), torch.from_numpy(faces).to(dev)
-    if local.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT:
-        raise SystemExit('{} has more than 2^31 - 1 vertices or faces'.format(args.mesh))
-    # the vertices (and colours) are written as read: the removal works on row numbers, not on the float32 copies
-    rows, out_f, info, top = _pieces_rows(local, f, *rules)
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.pieces')
+    rows, out_f, info, top = _pieces_rows(*mesh.to_device(limit='faces'), *rules)
     if rows is None:
-        meshio.write_ply_mesh(args.out_file, verts, faces, double=double, colors_u8=colors)
+        mesh.write_as_read(args.out_file)
     else:
-        rows = rows.cpu().numpy()
-        meshio.write_ply_mesh(args.out_file, verts[rows], out_f.cpu().numpy(), double=double, colors_u8=None if colors is None else np.asarray(colors)[rows])
+        mesh.write_rows(args.out_file, rows, out_f)
     report = dict(info, top=top)
     print(json.dumps(report))
     return report

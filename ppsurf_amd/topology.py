@@ -2,7 +2,8 @@
 
 smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
 face pairs (section 21), orient.py the same pairs with their edge slots (section 23) and manifold.py those pairs and slots once more,
-with the owner count of every edge (section 25); the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
+with the owner count of every edge (section 25); the hooking and compressing loop that runs on those pairs is labels.py (section 26), the
+frame of the commands mesh_cli.py; the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
 """
 import torch

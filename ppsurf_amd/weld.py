@@ -23,7 +23,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, topology
+from . import _lib, labels, mesh_cli, meshio, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 from .trim import SupportGrid, _f32_not_below
 
@@ -51,17 +51,10 @@ def _clusters(v, eps, cell=None, capacity=None):
     grid = SupportGrid(v, capacity)
     # a cell edge of eps, of the box's longest edge when eps is larger than that, and never below the floor or the grid's 2^20 cells per axis
     grid.build(grid.edge_for(max(min(eps, float(grid.ext)), H_FLOOR)) if cell is None else _f32_not_below(cell))
-    changed = torch.zeros(1, dtype=torch.int32, device=v.device)
-    rounds = 0
-    while True:
-        changed.zero_()
+    def hook(changed):
         _lib.call('ppsx_weld_hook', grid.pts, nv, grid._vec3(grid.lo), grid._vec3(grid.hi), float(grid.h), float(grid.inv_h), grid._table,
                   grid.capacity, grid.order, grid.offsets, eps, label, changed)
-        rounds += 1
-        if int(changed.item()) == 0:
-            break
-        _lib.call('ppsx_weld_compress', label, nv)
-    return label, rounds
+    return label, labels.fixed_point(hook, lambda: labels.compress(label, nv), v.device)
 
 
 def _dropped_duplicates(kept):
@@ -82,10 +75,9 @@ def _weld_rows(verts, faces, eps, drop_duplicates, cell=None, capacity=None):
     valid face or every face valid and no duplicate dropped."""
     nv, nf, dev = int(verts.shape[0]), int(faces.shape[0]), faces.device
     leader, _ = _clusters(verts, eps, cell, capacity)
-    leads = leader == torch.arange(nv, dtype=torch.int32, device=dev)
-    rows = torch.nonzero(leads).reshape(-1)
+    _, rows, number = labels.leaders(leader)
     sizes = torch.bincount(leader.long(), minlength=nv)
-    newrow = (torch.cumsum(leads, 0) - 1)[leader.long()].contiguous()
+    newrow = number[leader.long()].contiguous()
     out = torch.empty_like(faces)
     code = torch.empty(nf, dtype=torch.uint8, device=dev)
     _lib.call('ppsx_weld_faces', faces, nf, nv, newrow, out, code)
@@ -162,24 +154,14 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     meshio.need_ply_output(ap, args.out_file)
-    _lib.need_gpu('python -m ppsurf_amd.weld')
-    verts, faces, colors, double = read_input(args.mesh)
-    if not np.isfinite(verts).all():
-        raise SystemExit('{} has non-finite vertices'.format(args.mesh))
-    centre = meshio.box_centre(verts)                              # the mesh's own box
-    dev = torch.device('cuda')
-    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    local, f = torch.from_numpy(meshio.centred_f32(verts, centre)).to(dev), torch.from_numpy(faces).to(dev)
-    if local.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT:
-        raise SystemExit('{} has more than 2^31 - 1 vertices or faces'.format(args.mesh))
+    mesh = mesh_cli.load(args.mesh, 'python -m ppsurf_amd.weld', reader=read_input)
+    local, f = mesh.to_device(limit='faces')
     pairs_in = int(topology.manifold_pair_edges(f, int(local.shape[0]))[0].shape[0])
-    # the vertices (and colours) are written as read: the weld works on row numbers, not on the float32 copies
     rows, out_f, info = _weld_rows(local, f, eps, args.drop_duplicates)
     if rows is None:
-        meshio.write_ply_mesh(args.out_file, verts, faces, double=double, colors_u8=colors)
+        mesh.write_as_read(args.out_file)
     else:
-        rows = rows.cpu().numpy()
-        meshio.write_ply_mesh(args.out_file, verts[rows], out_f.cpu().numpy(), double=double, colors_u8=None if colors is None else np.asarray(colors)[rows])
+        mesh.write_rows(args.out_file, rows, out_f)
     pairs_out = int(topology.manifold_pair_edges(out_f.contiguous(), info['vertices_out'])[0].shape[0])
     report = dict(info, pairs_in=pairs_in, pairs_out=pairs_out, closed=2 * pairs_out == 3 * info['faces_out'])
     print(json.dumps(report))

@@ -78,7 +78,7 @@ def fixed_point(f, nv, pairs, label):
         assert int(changed.item()) in (0, 1)
         if int(changed.item()) == 0:
             return rounds
-        _lib.call('ppsx_pieces_compress', label, int(label.shape[0]))
+        _lib.call('ppsx_labels_compress', label, int(label.shape[0]))
     raise AssertionError('no fixed point')
 
 

@@ -135,7 +135,7 @@ def fixed_point(fa, fb, label, nf):
         assert int(changed.item()) in (0, 1)
         if int(changed.item()) == 0:
             return rounds
-        _lib.call('ppsx_pieces_compress', label, nf)
+        _lib.call('ppsx_labels_compress', label, nf)
     raise AssertionError('no fixed point')
 
 
@@ -152,15 +152,11 @@ def test_hook_and_compress_alone_skip_bad_pairs_and_invalid_faces():
     one = label.cpu().numpy()
     # one round: the labels have only fallen, stay in their component, and the skipped faces are as they were
     assert int(changed.item()) == 1 and one[1] == 0 and one[2] in (0, 1) and one[6] == 5 and one[[0, 3, 4, 5, 7]].tolist() == [0, -1, 4, 5, 7]
-    _lib.call('ppsx_pieces_compress', label, 8)                       # a hook that raised the flag is followed by a compress
+    _lib.call('ppsx_labels_compress', label, 8)                       # a hook that raised the flag is followed by a compress
     fixed_point(fa, fb, label, 8)
     assert label.cpu().numpy().tolist() == [0, 0, 0, -1, 4, 5, 5, 7] and buf[0].item() == -7 and buf[9].item() == -7
     # a fixed point leaves the flag down at once and writes nothing
     assert fixed_point(fa, fb, label, 8) == 1 and label.cpu().numpy().tolist() == [0, 0, 0, -1, 4, 5, 5, 7]
-    # compress alone: chains, an untouched invalid face, and a label above its slot, where a walk ends as at a root
-    buf[1:9] = dev(np.array([0, 0, 1, 2, -1, 7, 5, 3], dtype=np.int32))
-    _lib.call('ppsx_pieces_compress', label, 8)
-    assert label.cpu().numpy().tolist() == [0, 0, 0, 0, -1, 5, 5, 0] and buf[0].item() == -7 and buf[9].item() == -7
     # np = 0: nothing to do
     _lib.call('ppsx_pieces_hook', None, None, 0, label, 8, changed, on=torch.device(DEV))
 
@@ -273,9 +269,6 @@ def test_bad_arguments_are_an_error_return_and_write_nothing():
     def hook(fa=fa, fb=fb, np_=pairs, label=work, nf=nf, changed=changed):
         return run('ppsx_pieces_hook', fa, fb, np_, label, nf, changed)
 
-    def compress(label=work, nf=nf):
-        return run('ppsx_pieces_compress', label, nf)
-
     def stats(verts=verts, nv=nv, faces=faces, nf=nf, label=label, cid=cid, nc=6, count=out_n, lo=out_lo, hi=out_hi):
         return run('ppsx_pieces_stats', verts, nv, faces, nf, label, cid, nc, count, lo, hi)
 
@@ -290,9 +283,6 @@ def test_bad_arguments_are_an_error_return_and_write_nothing():
         assert hook(**kw) == 1, kw
         assert torch.equal(work, label0) and changed.item() == 0, kw
     assert hook(label=None) == 1 and hook(np_=0) == 0 and hook(nf=0) == 0 and hook(np_=0, fa=None, fb=None, label=None, changed=None) == 0
-    for kw in (dict(nf=-1), dict(nf=big), dict(label=None)):
-        assert compress(**kw) == 1, kw
-    assert compress(nf=0) == 0 and compress(nf=0, label=None) == 0 and torch.equal(work, label0) and changed.item() == 0
     for kw in (dict(nv=-1), dict(nf=-1), dict(nc=-1), dict(nv=big), dict(nf=big), dict(nc=big), dict(verts=None), dict(faces=None), dict(label=None),
                dict(cid=None), dict(count=None), dict(lo=None), dict(hi=None), dict(hi=out_lo)):
         assert stats(**kw) == 1, kw

@@ -104,7 +104,7 @@ def fixed_point(grid, eps, label, order=None):
         assert int(changed.item()) in (0, 1)
         if int(changed.item()) == 0:
             return rounds
-        _lib.call('ppsx_weld_compress', label, grid.n)
+        _lib.call('ppsx_labels_compress', label, grid.n)
     raise AssertionError('no fixed point')
 
 
@@ -163,7 +163,6 @@ def test_hook_and_compress_on_crowds_walls_and_single_vertices():
     assert got.tolist() == [0] and rounds == 1
     changed = torch.zeros(1, dtype=I32, device=DEV)
     _lib.call('ppsx_weld_hook', None, 0, None, None, 1.0, 1.0, None, 64, None, None, 0.0, None, changed)
-    _lib.call('ppsx_weld_compress', None, 0, on=torch.device(DEV))
     assert changed.item() == 0
 
 
@@ -195,11 +194,6 @@ def test_labels_and_order_entries_out_of_range_are_skipped_not_read_through():
     want = S.clusters_of_pairs(257, hi[live], lo[live])
     want[out] = start[out]                                             # (compress stores its own index into a root with a label above it)
     assert label.cpu().numpy().tobytes() == want.tobytes() and untouched(lbuf, -7)
-    # compress alone: chains, an untouched negative label, a label above its slot
-    cbuf, chain = guarded(8, I32, -7)
-    chain.copy_(dev(np.array([0, 0, 1, 2, -1, 9, 5, 4], dtype=np.int32)))
-    _lib.call('ppsx_weld_compress', chain, 8)
-    assert chain.cpu().numpy().tolist() == [0, 0, 0, 0, -1, 5, 5, 4] and untouched(cbuf, -7)
 
 
 @pytest.mark.parametrize('nf', [255, 256, 257])
@@ -248,9 +242,6 @@ def test_bad_arguments_are_an_error_return_and_write_nothing():
               offsets=grid.offsets, eps=0.0, label=label, changed=changed):
         return run('ppsx_weld_hook', pts, n, lo, hi, h, inv_h, table, capacity, order, offsets, eps, label, changed)
 
-    def compress(label=label, n=n):
-        return run('ppsx_weld_compress', label, n)
-
     def faces_(faces=f, nf=nf, nv=n, newrow=newrow, out=out, code=code):
         return run('ppsx_weld_faces', faces, nf, nv, newrow, out, code)
 
@@ -261,16 +252,11 @@ def test_bad_arguments_are_an_error_return_and_write_nothing():
         assert torch.equal(label, label0) and changed.item() == 0, kw
     assert hook_(label=None) == 1 and hook_(n=0) == 0 and changed.item() == 0
     assert hook_(n=0, pts=None, lo=None, hi=None, table=None, order=None, offsets=None, label=None, changed=None) == 0
-    for kw in (dict(n=-1), dict(n=big), dict(label=None)):
-        assert compress(**kw) == 1, kw
-    assert compress(n=0) == 0 and compress(n=0, label=None) == 0 and torch.equal(label, label0)
     for kw in (dict(nf=-1), dict(nv=-1), dict(nf=big), dict(nv=big), dict(faces=None), dict(newrow=None), dict(code=None), dict(faces=out)):
         assert faces_(**kw) == 1, kw
         assert bool((out == -7).all()) and bool((code == 9).all()), kw
     assert faces_(out=None) == 1 and faces_(nf=0) == 0 and faces_(nf=0, faces=None, newrow=None, out=None, code=None) == 0
     assert bool((out == -7).all()) and bool((code == 9).all())
-    with pytest.raises(_lib.PpsError, match='ppsx_weld_compress failed with status 1'):
-        _lib.call('ppsx_weld_compress', label, -1)
     # the good calls after the refused ones
     assert fixed_point(grid, 0.0, label) >= 2 and label.cpu().numpy().tobytes() == spec('torus soup', 0.0)[3]['leader'].tobytes()
     assert faces_() == 0 and bool((code == 2).all()) and out.cpu().numpy().tobytes() == faces.tobytes()          # every row is row 0: all collapse

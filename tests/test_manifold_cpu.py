@@ -171,12 +171,15 @@ def test_the_entries_are_declared_and_every_call_site_lies_where_it_should():
             assert path == 'manifold.py', '{}:{}:{}'.format(path, line, name)
             assert nargs == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}:{}'.format(path, line, name)
     assert {name: len(where) for name, where in sites.items()} == {'ppsx_manifold_hook': 1, 'ppsx_manifold_faces': 1}
-    # manifold.py names no other entry: the keys come through topology.py, the compress launch through pieces.compress_labels, which
-    # holds the one call of the generic entry
+    # manifold.py names no other entry: the keys come through topology.py, the loop and the compress launch through labels.py, which
+    # holds the one call of the one compress entry
     source = open(os.path.join(call_sites.REPO, 'ppsurf_amd', 'manifold.py')).read()
     assert set(re.findall(r'\bppsx_\w+', source)) == set(sites) and not re.search(r'call\(\s*[\'"]pps_', source)
-    assert 'pieces.compress_labels(label, 3 * nf)' in source
-    assert [path for path, _, _ in call_sites.ext_call_sites('ppsx_pieces_compress')['ppsx_pieces_compress']] == ['pieces.py']
+    assert [path for path, _, _ in call_sites.ext_call_sites('ppsx_labels_compress')['ppsx_labels_compress']] == ['labels.py']
+    # no stage holds a loop of its own: the flag is zeroed in labels.fixed_point and nowhere else in the package
+    package = os.path.join(call_sites.REPO, 'ppsurf_amd')
+    assert [os.path.basename(p) for p in sorted(glob.glob(os.path.join(package, '**', '*.py'), recursive=True))
+            if 'changed.zero_()' in open(p).read()] == ['labels.py']
     assert 'pps_manifold.hip' in build.SOURCES and 'pps_labels.h' in build.HEADERS
     lib = _lib.lib()
     assert lib.pps_abi_version() == 2 and set(sites) <= set(_lib._ext_entries)
@@ -184,17 +187,18 @@ def test_the_entries_are_declared_and_every_call_site_lies_where_it_should():
 
 def test_the_label_walk_lives_in_one_header():
     csrc = os.path.join(call_sites.REPO, 'ppsurf_amd', 'csrc')
-    defines = re.compile(r'\bint\s+(load_label|walk_end)\s*\(')
+    defines = re.compile(r'\b(?:int|void)\s+(load_label|walk_end|join_ends)\s*\(')
     users = []
     for path in sorted(glob.glob(os.path.join(csrc, '*.h')) + glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.cpp'))):
         text = open(path).read()
         name = os.path.basename(path)
         if name == 'pps_labels.h':
-            assert sorted(defines.findall(text)) == ['load_label', 'walk_end']
+            assert sorted(defines.findall(text)) == ['join_ends', 'load_label', 'walk_end']
             assert '__hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)' in text
         else:
             assert not defines.findall(text), name
             if '#include "pps_labels.h"' in text:
                 users.append(name)
-                assert 'walk_end(label' in text and 'load_label(label' in text, name
-    assert users == ['pps_manifold.hip', 'pps_pieces.hip', 'pps_weld.hip']
+                # every user walks through the header: directly, or through the shared join (weld, manifold)
+                assert ('walk_end(label' in text or 'join_ends(label' in text) and 'load_label(label' in text, name
+    assert users == ['pps_labels.hip', 'pps_manifold.hip', 'pps_pieces.hip', 'pps_weld.hip']

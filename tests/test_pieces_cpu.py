@@ -173,12 +173,11 @@ def test_the_pieces_entries_are_declared_and_every_call_site_lies_where_it_shoul
     I, I64, P, D = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double
     assert _lib.EXT_SIGNATURES['ppsx_pieces_edge_keys'] == (I, [P, I64, I64, P, P])
     assert _lib.EXT_SIGNATURES['ppsx_pieces_hook'] == (I, [P, P, I64, P, I64, P, P])
-    assert _lib.EXT_SIGNATURES['ppsx_pieces_compress'] == (I, [P, I64, P])
+    assert len([n for n in _lib.EXT_SIGNATURES if n.startswith('ppsx_pieces_')]) == 4                   # no compress of its own: labels.py's
     assert _lib.EXT_SIGNATURES['ppsx_pieces_stats'] == (I, [P, I64, P, I64, P, P, I64, P, P, P, P])
     assert _lib.EXT_SIGNATURES['ppsx_pieces_select'] == (I, [P, P, P, P, I64, I, I64, I, D, I, I64, D, P, P])
     assert _lib.EXT_PARAMS['ppsx_pieces_edge_keys'] == ['faces', 'nf', 'nv', 'keys', 'stream']
     assert _lib.EXT_PARAMS['ppsx_pieces_hook'] == ['fa', 'fb', 'np', 'label', 'nf', 'changed', 'stream']
-    assert _lib.EXT_PARAMS['ppsx_pieces_compress'] == ['label', 'nf', 'stream']
     assert _lib.EXT_PARAMS['ppsx_pieces_stats'] == ['verts', 'nv', 'faces', 'nf', 'label', 'cid', 'nc', 'count', 'lo', 'hi', 'stream']
     assert _lib.EXT_PARAMS['ppsx_pieces_select'] == ['count', 'lo', 'hi', 'rank', 'nc', 'has_min_faces', 'min_faces', 'has_min_diag_frac',
                                                      'min_diag_frac', 'has_keep_largest', 'keep_largest', 'box_diag2', 'keep', 'stream']
@@ -188,8 +187,8 @@ def test_the_pieces_entries_are_declared_and_every_call_site_lies_where_it_shoul
         for path, line, nargs in where:
             assert path == ('topology.py' if name == 'ppsx_pieces_edge_keys' else 'pieces.py'), '{}:{}:{}'.format(path, line, name)
             assert nargs == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}:{}'.format(path, line, name)
-    assert {name: len(where) for name, where in sites.items()} == {'ppsx_pieces_edge_keys': 1, 'ppsx_pieces_hook': 1, 'ppsx_pieces_compress': 1,
-                                                                   'ppsx_pieces_stats': 1, 'ppsx_pieces_select': 1}
+    assert {name: len(where) for name, where in sites.items()} == {'ppsx_pieces_edge_keys': 1, 'ppsx_pieces_hook': 1, 'ppsx_pieces_stats': 1,
+                                                                   'ppsx_pieces_select': 1}
     assert 'pps_pieces.hip' in build.SOURCES
     lib = _lib.lib()
     assert lib.pps_abi_version() == 2 and set(sites) <= set(_lib._ext_entries)

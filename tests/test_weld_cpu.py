@@ -193,19 +193,19 @@ def test_the_weld_entries_are_declared_and_every_call_site_lies_where_it_should(
     from ppsurf_amd import _lib, build
     I, I64, P, F, Dbl = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
     assert _lib.EXT_SIGNATURES['ppsx_weld_hook'] == (I, [P, I64, P, P, F, F, P, I64, P, P, Dbl, P, P, P])
-    assert _lib.EXT_SIGNATURES['ppsx_weld_compress'] == (I, [P, I64, P])
+    assert len([n for n in _lib.EXT_SIGNATURES if n.startswith('ppsx_weld_')]) == 2                      # no compress of its own: labels.py's
     assert _lib.EXT_SIGNATURES['ppsx_weld_faces'] == (I, [P, I64, I64, P, P, P, P])
     assert _lib.EXT_PARAMS['ppsx_weld_hook'] == ['pts', 'n', 'lo', 'hi', 'h', 'inv_h', 'table', 'capacity', 'order', 'offsets', 'eps', 'label', 'changed',
                                                  'stream']
-    assert _lib.EXT_PARAMS['ppsx_weld_compress'] == ['label', 'n', 'stream']
     assert _lib.EXT_PARAMS['ppsx_weld_faces'] == ['faces', 'nf', 'nv', 'newrow', 'out', 'code', 'stream']
     sites = call_sites.ext_call_sites('ppsx_weld')
     for name, where in sites.items():
         for path, line, nargs in where:
             assert path == 'weld.py', '{}:{}:{}'.format(path, line, name)
             assert nargs == len(_lib.EXT_PARAMS[name]) - 1, '{}:{}:{}'.format(path, line, name)
-    assert {name: len(where) for name, where in sites.items()} == {n: 1 for n in _lib.EXT_PARAMS if n.startswith('ppsx_weld_')} and len(sites) == 3
-    # weld.py calls no other stage's entries: the cell lists come through trim.SupportGrid, which holds the one call of the slot entry
+    assert {name: len(where) for name, where in sites.items()} == {n: 1 for n in _lib.EXT_PARAMS if n.startswith('ppsx_weld_')} and len(sites) == 2
+    # weld.py calls no other stage's entries: the cell lists come through trim.SupportGrid, which holds the one call of the slot entry, the
+    # loop and the compress launch through labels.py
     source = open(os.path.join(call_sites.REPO, 'ppsurf_amd', 'weld.py')).read()
     assert set(re.findall(r'\bppsx_\w+', source)) == set(sites) and not re.search(r'call\(\s*[\'"]pps_', source)
     assert [path for path, _, _ in call_sites.ext_call_sites('ppsx_trim_cell_slots')['ppsx_trim_cell_slots']] == ['trim.py']

@@ -429,6 +429,40 @@ int ppsx_manifold_hook(const int64_t* faces, int64_t nf, int64_t nv, const int32
 int ppsx_manifold_faces(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* label, const int64_t* newrow, int64_t nv_out, int64_t* out,
                         void* stream);
 
+/* ---- Delaunay edge flips: the diagonal of a quad turns where that repairs a sliver (csrc/pps_flip.hip) ---------------------------------------
+ * new capability: replaces nothing -- the reference has no such stage.  Driven by ppsurf_amd/flip.py (the edges, their owners and slots by
+ * ppsurf_amd/topology.py); the rule and the argument that the winners of a round are independent are written out at the top of
+ * csrc/pps_flip.hip and in DESIGN.md section 27.  Pairs: fa, fb int32 [np] the two valid faces on an edge that exactly two valid faces hold, in
+ * ascending edge key and in either order, ea, eb int32 [np] the slot of that edge in each (slot k is corner k -> corner k + 1 mod 3).  A
+ * priority is a u64, the smallest first, NONE = 2^64 - 1.
+ *   ppsx_flip_candidates  one thread per pair, on verts f32 [nv,3] and the working faces int64 [nf,3]: with f < g the two faces and k, l
+ *                         their slots, a = F[f][k], b = F[f][k + 1], c = F[f][k + 2], d = F[g][l + 2]; the pair is a candidate when
+ *                         F[g][l] == b and F[g][l + 1] == a, c != d, the key (min(c, d) << 32) | max(c, d) is none of keys int64 [ne]
+ *                         (ascending; a binary search), the fold guard and the crease guard with cos2 pass and the sum s of the two
+ *                         opposite cotangents is below -min_gain (fp64, every operation rounded on its own; the .hip file has the formulas).
+ *                         Writes prio u64 [np] = ((0x7F800000 - bits(f32(-s))) << 32) | fmix32(pair index) and quad int32 [np,4] =
+ *                         (a, b, c, d), NONE and zeros for a pair that is no candidate, and does atomicMin(&vmin[v], prio) on vmin u64 [nv]
+ *                         (the caller presets it to all ones) at the four quad vertices of a candidate.  A pair with a face outside [0, nf),
+ *                         two equal faces, a slot outside [0, 3) or a face that is not valid for nv is no candidate and is not read through.
+ *                         np, nv, nf or ne < 0, np, nv or nf > 2^31 - 1, ne > 3 (2^31 - 1), or -- with np > 0 -- a NULL fa, fb, ea, eb, prio or quad, a NULL
+ *                         verts or vmin with nv > 0, a NULL faces with nf > 0 or a NULL keys with ne > 0: PPS_ERR_ARG, nothing is launched
+ *                         or written.  np == 0: 0, nothing is launched.
+ *   ppsx_flip_winners     flag u8 [np]: 1 when prio[i] != NONE, the four entries of quad[i] lie in [0, nv) and vmin equals prio[i] at all
+ *                         four, else 0.  Every flag is written.
+ *                         np or nv < 0 or > 2^31 - 1, or -- with np > 0 -- a NULL prio, quad or flag or a NULL vmin with nv > 0:
+ *                         PPS_ERR_ARG, nothing is launched or written.  np == 0: 0, nothing is launched.
+ *   ppsx_flip_apply       a pair with flag[i] != 0 rewrites two rows of faces int64 [nf,3] in place, with f < g its two faces and
+ *                         (a, b, c, d) = quad[i]: F[f] = (a, d, c), F[g] = (b, c, d).  A pair with a face outside [0, nf), two equal faces or
+ *                         a quad entry outside [0, nv) writes nothing.  The flagged pairs must share no face (the winners of a round do not).
+ *                         np, nv or nf < 0 or > 2^31 - 1, or -- with np > 0 and nf > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is launched
+ *                         or written.  np == 0 or nf == 0: 0, nothing is launched. */
+int ppsx_flip_candidates(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const int32_t* fa, const int32_t* fb, const int32_t* ea,
+                         const int32_t* eb, int64_t np, const int64_t* keys, int64_t ne, double cos2, double min_gain, uint64_t* prio, int32_t* quad,
+                         uint64_t* vmin, void* stream);
+int ppsx_flip_winners(const uint64_t* prio, const int32_t* quad, int64_t np, const uint64_t* vmin, int64_t nv, uint8_t* flag, void* stream);
+int ppsx_flip_apply(const int32_t* fa, const int32_t* fb, const int32_t* quad, const uint8_t* flag, int64_t np, int64_t nv, int64_t* faces, int64_t nf,
+                    void* stream);
+
 /* ---- tile claims of the split-precision decoder (csrc/pps_decode.hip, csrc/pps_common.h) ---------------------------------------------------------
  * changes no entry: inside pps_decode_fwd_mixed_f32 the persistent split-precision kernels take their next unit of work from counters in the
  * head of the workspace `ws` instead of walking a fixed share of the units.  int32 words of that head: [0] range flag, [1] fall-back count (as

@@ -2,7 +2,8 @@
 
 smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
 face pairs (section 21), orient.py the same pairs with their edge slots (section 23) and manifold.py those pairs and slots once more,
-with the owner count of every edge (section 25); the hooking and compressing loop that runs on those pairs is labels.py (section 26), the
+with the owner count of every edge (section 25), flip.py the same runs with their keys (section 27); the hooking and compressing loop
+that runs on those pairs is labels.py (section 26), the
 frame of the commands mesh_cli.py; the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
 """
@@ -103,15 +104,21 @@ def edge_runs(faces, nv):
     position of each, whose owner is position // 3 and whose slot is position % 3.  owners == 1 is a border edge, 2 a manifold one, 3 and
     more a non-manifold one (section 25 counts them).  Where there are invalid faces their SENTINEL keys form one more run at the end,
     with owners 0, so that no compaction (and no synchronisation) is spent on it here."""
+    return edge_runs_keys(faces, nv)[:4]
+
+
+def edge_runs_keys(faces, nv):
+    """edge_runs with a fifth entry, keys int64 [ne]: the key of every run, ascending and distinct, the SENTINEL of the run of the invalid
+    faces last where there is one.  flip.py looks up in them whether an edge exists."""
     nf = int(faces.shape[0])
     keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
     if nf == 0:
-        return keys, keys, keys, keys.bool()
+        return keys, keys, keys, keys.bool(), keys
     _lib.call('ppsx_pieces_edge_keys', faces, nf, nv, keys)
     valid = keys[0::3] != SENTINEL
     keys, order = torch.sort(keys)
     uniq, counts = torch.unique_consecutive(keys, return_counts=True)
-    return order, torch.cumsum(counts, 0) - counts, torch.where(uniq != SENTINEL, counts, torch.zeros_like(counts)), valid
+    return order, torch.cumsum(counts, 0) - counts, torch.where(uniq != SENTINEL, counts, torch.zeros_like(counts)), valid, uniq
 
 
 def pairs_of_runs(order, first, owners, valid):

@@ -147,6 +147,27 @@ def test_signed_distance_reproduces_recorded_labels():
     assert worst <= 2e-5
 
 
+def test_signed_distance_signs_next_to_the_surface():
+    """The labels of queries at the face centroids of icosphere(2, 0.3), offset along the normal by +-1e-2, +-1e-3 and +-1e-4, for both
+    windings of the faces: the sign is the fp64 winding number's wherever that is further from +-0.5 than its fp32 error bound
+    (eval_spec.winding_spec_bounded) -- by the reference alone at least 99 % of these queries -- and the magnitude is the offset to 1e-6."""
+    v, f = eval_spec.icosphere(2, 0.3)
+    v = v.astype(np.float32)
+    _, nrm, corners = eval_spec.face_stats_spec(v, f)
+    centroid = corners.reshape(-1, 3, 3).mean(axis=1)
+    offs = np.array([1e-2, -1e-2, 1e-3, -1e-3, 1e-4, -1e-4])
+    q = (centroid[None] + offs[:, None, None] * nrm[None]).reshape(-1, 3).astype(np.float32)
+    off = np.repeat(offs, f.shape[0])
+    w, bound = eval_spec.winding_spec_bounded(v, f, q)
+    clear = np.abs(np.abs(w) - 0.5) > bound
+    assert clear.mean() >= 0.99
+    assert np.array_equal(np.abs(w) > 0.5, off < 0)                           # the normals point outwards: a negative offset is inside
+    for faces in (f, f[:, ::-1].copy()):
+        sd = md.signed_distance(_dev(v), _dev(faces.astype(np.int32)), _dev(q)).cpu().numpy()
+        assert np.array_equal((sd > 0)[clear], (off < 0)[clear])              # positive inside, whichever way the faces wind
+        assert np.abs(np.abs(sd.astype(np.float64)) - np.abs(off)).max() <= 1e-6
+
+
 def _tree(root):
     out = {}
     for dp, _, fns in os.walk(root):

@@ -463,6 +463,52 @@ int ppsx_flip_winners(const uint64_t* prio, const int32_t* quad, int64_t np, con
 int ppsx_flip_apply(const int32_t* fa, const int32_t* fb, const int32_t* quad, const uint8_t* flag, int64_t np, int64_t nv, int64_t* faces, int64_t nf,
                     void* stream);
 
+/* ---- subdivide: edges longer than a bound are split at their midpoint, longest first (csrc/pps_subdivide.hip) -------------------------------
+ * new capability: replaces nothing -- the reference has no such stage.  Driven by ppsurf_amd/subdivide.py (the edge runs, their keys and owners
+ * by ppsurf_amd/topology.py); the rule and the argument that the winners of a round are independent are written out at the top of
+ * csrc/pps_subdivide.hip and in DESIGN.md section 28.  Runs: keys int64 [ne] the distinct edge keys (min << 32) | max in ascending order, the
+ * sentinel 2^63 - 1 of the invalid faces last where there is one, owners int64 [ne] the faces on each (0 for the sentinel); run_of
+ * int64 [3 nf] the run of key position 3 f + k (slot k of face f is corner k -> corner k + 1 mod 3).  A priority is a u64, the smallest
+ * first, NONE = 2^64 - 1.
+ *   ppsx_subdivide_edges    one thread per run, on verts f32 [nv,3]: with a < b the two halves of keys[e], d = P_b - P_a in fp64,
+ *                           len2[e] = (dx dx + dy dy) + dz dz (f64 [ne]) and M = f32((P_a + P_b) 0.5) per component; the run is a candidate when
+ *                           len2 > max2 and M differs from verts[a] and from verts[b] in some component.  prio[e] (u64 [ne]) =
+ *                           ((0x7FF00000 - (bits(len2) >> 32)) << 32) | fmix32(e) for a candidate and NONE for every other run.  A key that is
+ *                           negative, has a >= b or b >= nv (the sentinel is one) gives len2 0 and NONE and is not read through.  max2 = +inf
+ *                           writes the lengths alone.
+ *                           ne or nv < 0, ne > 2^32 - 1, nv > 2^31 - 1, a NaN max2, or -- with ne > 0 -- a NULL keys, len2 or prio or a NULL
+ *                           verts with nv > 0: PPS_ERR_ARG, nothing is launched or written.  ne == 0: 0, nothing is launched.
+ *   ppsx_subdivide_votes    one thread per face: choice[f] (int32 [nf]) = the slot k whose run has the smallest priority, the first of equal
+ *                           ones, -1 when all three are NONE; a run_of entry outside [0, ne) counts as NONE and is not read through.  A face
+ *                           with a choice adds 1 to votes[run] (int32 [ne], the caller zeroes it before): an integer atomicAdd.
+ *                           nf or ne < 0, nf > 2^31 - 1, ne > 2^32 - 1, or -- with nf > 0 -- a NULL run_of or choice or a NULL prio or votes
+ *                           with ne > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_subdivide_winners  win[e] (u8 [ne]) = 1 when prio[e] != NONE and votes[e] == owners[e], else 0.  Every flag is written.
+ *                           ne < 0 or > 2^32 - 1, or -- with ne > 0 -- a NULL pointer: PPS_ERR_ARG, nothing is launched or written.
+ *                           ne == 0: 0, nothing is launched.
+ *   ppsx_subdivide_hits     hit[f] (u8 [nf]) = 1 when choice[f] lies in 0..2, the run of that slot lies in [0, ne) and win is set there,
+ *                           else 0.  Every flag is written.
+ *                           nf or ne < 0, nf > 2^31 - 1, ne > 2^32 - 1, or -- with nf > 0 -- a NULL run_of, choice or hit or a NULL win
+ *                           with ne > 0: PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_subdivide_emit     the rows of a round, with vslot int64 [ne] and fslot int64 [nf] the exclusive prefix sums of win and hit and
+ *                           nw, nh their totals.  One thread per run: a winner with a readable key and vslot[e] = i in [0, nw) writes
+ *                           new_verts[i] (f32 [nw,3]) = M and ends[i] (int64 [nw,2]) = (a, b); the caller appends new_verts to verts.  One
+ *                           thread per face: out int64 [nf + nh,3]; a hit face (as ppsx_subdivide_hits finds it again) with i = vslot[run] in
+ *                           [0, nw) and j = fslot[f] in [0, nh) writes row f as faces[f] with entry k + 1 mod 3 replaced by nv + i and row
+ *                           nf + j as faces[f] with entry k replaced by nv + i; every other row f is copied.  Rows nf .. nf + nh - 1 are
+ *                           written by their hits alone.  The entries of a face are never used as an address.
+ *                           a negative count, nv, nf, nv + nw or nf + nh > 2^31 - 1, ne > 2^32 - 1, nw > ne, nh > nf, out == faces, or --
+ *                           with ne > 0 -- a NULL keys, win or vslot, a NULL verts with nv > 0, a NULL new_verts or ends with nw > 0, or
+ *                           -- with nf > 0 -- a NULL faces, run_of, choice, hit, fslot or out: PPS_ERR_ARG, nothing is launched or written.
+ *                           ne == 0 and nf == 0: 0, nothing is launched. */
+int ppsx_subdivide_edges(const int64_t* keys, int64_t ne, const float* verts, int64_t nv, double max2, double* len2, uint64_t* prio, void* stream);
+int ppsx_subdivide_votes(const int64_t* run_of, int64_t nf, const uint64_t* prio, int64_t ne, int32_t* choice, int32_t* votes, void* stream);
+int ppsx_subdivide_winners(const uint64_t* prio, const int32_t* votes, const int64_t* owners, int64_t ne, uint8_t* win, void* stream);
+int ppsx_subdivide_hits(const int64_t* run_of, const int32_t* choice, int64_t nf, const uint8_t* win, int64_t ne, uint8_t* hit, void* stream);
+int ppsx_subdivide_emit(const float* verts, int64_t nv, const int64_t* keys, const uint8_t* win, const int64_t* vslot, int64_t ne, int64_t nw,
+                        const int64_t* faces, int64_t nf, const int64_t* run_of, const int32_t* choice, const uint8_t* hit, const int64_t* fslot,
+                        int64_t nh, float* new_verts, int64_t* ends, int64_t* out, void* stream);
+
 /* ---- tile claims of the split-precision decoder (csrc/pps_decode.hip, csrc/pps_common.h) ---------------------------------------------------------
  * changes no entry: inside pps_decode_fwd_mixed_f32 the persistent split-precision kernels take their next unit of work from counters in the
  * head of the workspace `ws` instead of walking a fixed share of the units.  int32 words of that head: [0] range flag, [1] fall-back count (as

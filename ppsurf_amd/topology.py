@@ -2,7 +2,7 @@
 
 smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
 face pairs (section 21), orient.py the same pairs with their edge slots (section 23) and manifold.py those pairs and slots once more,
-with the owner count of every edge (section 25), flip.py the same runs with their keys (section 27); the hooking and compressing loop
+with the owner count of every edge (section 25), flip.py the same runs with their keys (section 27) and subdivide.py those runs and keys again (section 28); the hooking and compressing loop
 that runs on those pairs is labels.py (section 26), the
 frame of the commands mesh_cli.py; the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
@@ -109,7 +109,8 @@ def edge_runs(faces, nv):
 
 def edge_runs_keys(faces, nv):
     """edge_runs with a fifth entry, keys int64 [ne]: the key of every run, ascending and distinct, the SENTINEL of the run of the invalid
-    faces last where there is one.  flip.py looks up in them whether an edge exists."""
+    faces last where there is one.  flip.py looks up in them whether an edge exists; subdivide.py reads the two
+    ends of every edge from them (section 28)."""
     nf = int(faces.shape[0])
     keys = torch.empty(3 * nf, dtype=torch.int64, device=faces.device)
     if nf == 0:

@@ -509,6 +509,47 @@ int ppsx_subdivide_emit(const float* verts, int64_t nv, const int64_t* keys, con
                         const int64_t* faces, int64_t nf, const int64_t* run_of, const int32_t* choice, const uint8_t* hit, const int64_t* fslot,
                         int64_t nh, float* new_verts, int64_t* ends, int64_t* out, void* stream);
 
+/* ---- intersect: which pairs of faces of a mesh cross (csrc/pps_intersect.hip) ------------------------------------------------------------------
+ * new capability: replaces nothing -- the reference has no such check.  Driven by ppsurf_amd/intersect.py (the cell lists by trim.SupportGrid over
+ * the box lower corners of the small faces); the rule -- live faces, boxed pairs, the admitted edge-against-triangle tests in fp64 -- and the
+ * argument that the cell range misses no partner are written out at the top of csrc/pps_intersect.hip and in DESIGN.md section 29; restated in
+ * numpy by tests/intersect_spec.py, which the entries match bit for bit.  No result depends on h, on the capacity, on which live face is in
+ * `small` and which in `large`, or on the order in which the partners are met.
+ *   ppsx_intersect_boxes  one thread per face of verts f32 [nv,3] / faces int64 [nf,3]: live[f] (u8 [nf]) = 1 when the face is valid for nv
+ *                         (indices in [0, nv), pairwise distinct) and its nine coordinates are finite; lo, hi (f32 [nf,3]) the box of its three
+ *                         corners; ext[f] (f32 [nf]) the largest of the three fp64 differences hi - lo, rounded up to f32 (+inf above the
+ *                         largest float).  A face that is not live is not read through and gets zeros in all four.
+ *                         nf or nv < 0 or > 2^31 - 1, or -- with nf > 0 -- a NULL faces, lo, hi, ext or live or a NULL verts with nv > 0:
+ *                         PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_intersect_count  one wave per face f, four faces per workgroup, with lo, hi, live from ppsx_intersect_boxes.  Partners: small int64 [ns]
+ *                         lists faces with ext <= h, whose box lower corners (in that order) are the ns points of the cell lists glo, ghi, h,
+ *                         inv_h, table, capacity, order, offsets (those of ppsx_trim_cell_slots and ppsx_trim_face_support, over n = ns
+ *                         points); large int64 [nl] lists further faces, of any extent; no face is listed twice.  Every listed g != f that
+ *                         is live and in [0, nf) is met exactly once when its box overlaps f's.  flag[f] (u8 [nf]) = 1 when some partner
+ *                         crosses f; count[f] (int32 [nf]) = the crossing partners g > f; boxed[f] (int32 [nf]) = the boxed partners g > f.
+ *                         A face that is not live gets zeros.  An entry of order, offsets, small, large or faces that is out of range is
+ *                         skipped, never used as an address.
+ *                         a negative count, nf or nv > 2^31 - 1, ns + nl > nf, h < 0 or NaN, or -- with nf > 0 -- a NULL faces, lo, hi,
+ *                         live, flag, count or boxed, a NULL verts with nv > 0, a NULL large with nl > 0, or -- with ns > 0 -- a NULL
+ *                         small, table, order or offsets, a capacity that is no power of two > ns, or a grid that pps_cells.h refuses
+ *                         (h == 0 among them): PPS_ERR_ARG, nothing is launched or written.  nf == 0: 0, nothing is launched.
+ *   ppsx_intersect_emit   the same walk with count from ppsx_intersect_count and pair_offsets int64 [nf] its exclusive prefix sum: the crossing
+ *                         pair (f, g), g > f, goes to row pair_offsets[f] + p of pairs int64 [np,2], p its position among the pairs of f in
+ *                         the order of the walk (a ballot prefix); the caller sorts the rows.  A pair is written only while p < count[f], and
+ *                         a face with count[f] <= 0, pair_offsets[f] < 0 or pair_offsets[f] + count[f] > np writes nothing.
+ *                         the rules of ppsx_intersect_count, and np < 0, a NULL count or pair_offsets, a NULL pairs with np > 0: PPS_ERR_ARG,
+ *                         nothing is launched or written.  nf == 0 or np == 0: 0, nothing is launched. */
+int ppsx_intersect_boxes(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, float* lo, float* hi, float* ext, uint8_t* live,
+                         void* stream);
+int ppsx_intersect_count(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* lo, const float* hi, const uint8_t* live,
+                         const int64_t* small, int64_t ns, const float* glo, const float* ghi, float h, float inv_h, const uint64_t* table,
+                         int64_t capacity, const int64_t* order, const int64_t* offsets, const int64_t* large, int64_t nl, uint8_t* flag,
+                         int32_t* count, int32_t* boxed, void* stream);
+int ppsx_intersect_emit(const float* verts, int64_t nv, const int64_t* faces, int64_t nf, const float* lo, const float* hi, const uint8_t* live,
+                        const int64_t* small, int64_t ns, const float* glo, const float* ghi, float h, float inv_h, const uint64_t* table,
+                        int64_t capacity, const int64_t* order, const int64_t* offsets, const int64_t* large, int64_t nl, const int32_t* count,
+                        const int64_t* pair_offsets, int64_t np, int64_t* pairs, void* stream);
+
 /* ---- tile claims of the split-precision decoder (csrc/pps_decode.hip, csrc/pps_common.h) ---------------------------------------------------------
  * changes no entry: inside pps_decode_fwd_mixed_f32 the persistent split-precision kernels take their next unit of work from counters in the
  * head of the workspace `ws` instead of walking a fixed share of the units.  int32 words of that head: [0] range flag, [1] fall-back count (as

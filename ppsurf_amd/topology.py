@@ -2,7 +2,7 @@
 
 smooth.py takes its adjacency from here, normals.py its incidence, fill.py its adjacency and its rims (section 19), pieces.py its
 face pairs (section 21), orient.py the same pairs with their edge slots (section 23) and manifold.py those pairs and slots once more,
-with the owner count of every edge (section 25), flip.py the same runs with their keys (section 27) and subdivide.py those runs and keys again (section 28); the hooking and compressing loop
+with the owner count of every edge (section 25), flip.py the same runs with their keys (section 27) and subdivide.py those runs and keys again (section 28); intersect.py takes only the checks (section 29); the hooking and compressing loop
 that runs on those pairs is labels.py (section 26), the
 frame of the commands mesh_cli.py; the valid-face rule on the device is csrc/pps_faces.h, the numpy restatement tests/topology_spec.py.  One key
 kernel per face, one torch.sort, the sentinel keys of the invalid faces dropped from the end, ops.row_offsets for the rows.
@@ -27,14 +27,14 @@ def need_device(what, *tensors):
         raise CpuTensorError(str(e)) from None
 
 
-def checked_mesh(what, verts, faces, limit=False):
-    """(verts f32 contiguous, faces contiguous) of a device mesh, or a ValueError: non-finite vertices, with `limit` more than 2^31 - 1
-    vertices or faces."""
+def checked_mesh(what, verts, faces, limit=False, finite=True):
+    """(verts f32 contiguous, faces contiguous) of a device mesh, or a ValueError: non-finite vertices (unless `finite` is off: intersect.py
+    takes them, a face with such a corner is not live there), with `limit` more than 2^31 - 1 vertices or faces."""
     assert verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3 and faces.dtype == torch.int64
     v, f = verts.contiguous().float(), faces.contiguous()
     if limit and (v.shape[0] > MAX_COUNT or f.shape[0] > MAX_COUNT):
         raise ValueError('{}: at most 2^31 - 1 vertices and faces, got {} and {}'.format(what, v.shape[0], f.shape[0]))
-    if not bool(torch.isfinite(v).all()):
+    if finite and not bool(torch.isfinite(v).all()):
         raise ValueError('{}: the mesh has non-finite vertices'.format(what))
     return v, f
 

@@ -557,7 +557,8 @@ int ppsx_intersect_emit(const float* verts, int64_t nv, const int64_t* faces, in
  * [12] STN head, [13] fc3 + feature rows, [14] tail.  The caller zeroes the head once, as before; every kernel leaves words 2..14 at zero.  The
  * single entries (pps_interp_pool_f16x3, pps_pointnet_f16x3, pps_decode_tail_f16x3) keep the fixed share.  A query's results do not depend on
  * the unit or the workgroup that evaluates it.  Environment, read per call: PPS_TILE_CLAIMS=0 keeps the fixed share everywhere; a number selects
- * kernels by bit (1 interpolation, 2 STN rows, 4 STN head, 8 fc3 + feature rows, 16 tail).
+ * kernels by bit (1 interpolation, 2 STN rows, 4 STN head, 8 fc3 + feature rows, 16 tail).  PPS_INTERP_AHEAD=0 (here and in pps_interp_pool_f16x3)
+ * lets every trip of the fixed-share interpolation kernel fetch its own neighbour ids and G rows instead of one trip ahead: same bits.
  *   ppsx_decode_units  HOST function, launches nothing; units, count are HOST pointers.  Lists the units of kernel 0 interp_pool_f16x3,
  *                      1 pointnet_stn_rows (split precision, one launch), 2 pointnet_stn_head_h, 3 pointnet_fc3_feat_rows, 4 decode_tail_h for
  *                      q queries with patches of p points on a chip that holds wgs workgroups of that kernel, in the order the counters hand

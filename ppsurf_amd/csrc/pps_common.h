@@ -463,6 +463,12 @@ __device__ __forceinline__ void chunk_copy_piece_at(const char* chunk, f32x4* ds
     const unsigned lds_addr = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(dst + i * NTHREADS + wave_base));
     asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(lds_addr), "v"(voff), "s"(chunk) : "memory", "m0");
 }
+// One 1 KiB piece of a row GATHER by the same instruction: every lane names its own 16 source bytes (`src`, a 64-bit address per lane), the data
+// lands at lds_addr + lane * 16 (lds_addr wave-uniform).  Returns in order with the weight stream's pieces: the next stream_wait() covers it, and the
+// wave that issued it may read its slot back behind that wait without a barrier.  (s_nop: one wait state between the write of M0 and its use)
+__device__ __forceinline__ void gather_piece_async(const char* src, unsigned lds_addr) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(lds_addr), "v"(src) : "memory", "m0");
+}
 // all outstanding pieces of this wave have landed in LDS (call before the barrier that hands the chunk to the other waves)
 __device__ __forceinline__ void stream_wait() {
     asm volatile("s_waitcnt vmcnt(0)" : : : "memory");

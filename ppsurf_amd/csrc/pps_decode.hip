@@ -313,19 +313,44 @@ __global__ __launch_bounds__(NT, 2) void interp_pool_kernel(const float* __restr
 #define IH_NCH (32 / IH_OB + 4 / IH_OB)       // chunks per pass: fc2 and fc3 16 output blocks each, fc_query 4
 static_assert(IH_OB == 2, "the weight pointer of the kernel's layer step wraps behind the step that fetches the last chunk: right for two output blocks per chunk only");
 #define IH_LDS_BYTES (2 * IH_CH4 * 16 + (IP_W_XYZ + IP_NBIAS + IH_NW * 64 * 3 + IH_NW * 256) * 4)
+// AHEAD: blocks 0..7 (channels 0..127) of the 128 G rows of the NEXT trip are staged in LDS: one 1 KiB slot per (wave, block), lane l's 16 bytes at
+// l * 16 of the slot.  The staging area lies between the weight ring and the tables, so every LDS-DMA destination of the kernel stays below 128 KiB
+#define IH_STAGE_BLOCKS 8
+#define IH_STAGE_F4 (IH_NW * IH_STAGE_BLOCKS * 64)
+#define IH_LDS_BYTES_AHEAD (IH_LDS_BYTES + IH_STAGE_F4 * 16)
+static_assert(IH_LDS_BYTES_AHEAD <= 160 * 1024, "one workgroup per CU: ring, staged G rows and tables within the CU's 160 KiB of LDS");
+
+// What lane (n, g) of wave `wave` loads first for tile t (t < ntiles) of interp_pool_f16x3_kernel: the id of neighbour row 16 (wave & 3) + n of the
+// wave's query and coordinate g of that query, with the clamps of the trip head (query to Q - 1, rows >= k to row 0)
+struct InterpIds { int64_t id; float qx; };
+__device__ __forceinline__ InterpIds interp_ids(int t, int wave, int n, int g, int64_t Q, int k, const int64_t* __restrict__ idx,
+                                                const float* __restrict__ query) {
+    const int64_t qn = (int64_t)t * (IH_NW / 4) + (wave >> 2);
+    const int64_t qnc = qn < Q ? qn : Q - 1;
+    const int r = (wave & 3) * 16 + n;
+    return InterpIds{idx[qnc * k + (r < k ? r : 0)], query[qnc * 3 + (g < 3 ? g : 2)]};        // g = 3: loaded without a branch, dropped by the caller
+}
 
 // CLAIM: tiles are claimed (pps_common.h) from the words head[PPS_CLAIM_INTERP ..] of the decoder workspace instead of walked as a fixed share.
 // Every XCD keeps its contiguous query range (the G gather lives on that L2) with a counter of its own; a workgroup whose range is used up takes
 // from the next XCD's.  !CLAIM (head unused): the fixed share of xcd_tile_range.
-template <bool CLAIM>
+// AHEAD (fixed share only: the next tile is known a trip ahead): a trip opens on data that is on chip already.  Today's head is two dependent
+// round trips to L2 / Infinity Cache with all eight waves of the CU at the same point (neighbour id, then the G row and the pts row it addresses).
+// With AHEAD the id, query and pts coordinates of the next trip are loaded into registers during this trip, blocks 0..7 of its G rows go into the
+// LDS staging area by LDS-DMA, one piece between every two steps of fc3, and blocks 8..15 are ordinary loads from the known id at the top of the
+// trip, with xyz / ReLU / split of blocks 0..7 running out of LDS underneath them.  Same values into the same operations in the same order as
+// !AHEAD: bit-identical (tests/test_gpu_interp_ahead.py).  Every prefetch address comes from a tile of this workgroup's own share (it + 1 < count)
+// and a query clamped to Q - 1; the last trip prefetches nothing.
+template <bool CLAIM, bool AHEAD = false>
 PPS_PLAIN_F32
 __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float* __restrict__ G, const float* __restrict__ pts,
                                                                      const float* __restrict__ query, const int64_t* __restrict__ idx,
                                                                      int64_t Q, int k, const float* __restrict__ wxyz,
                                                                      const f32x4* __restrict__ w16, const float* __restrict__ bias,
                                                                      float* __restrict__ pooled, int* __restrict__ range, int* __restrict__ head) {
+    static_assert(!(CLAIM && AHEAD), "a claimed tile is not known a trip ahead");
     float amax = 0.f;
-    float* xyz_l = (float*)((f32x4*)pps_smem + 2 * IH_CH4);
+    float* xyz_l = (float*)((f32x4*)pps_smem + 2 * IH_CH4 + (AHEAD ? IH_STAGE_F4 : 0));
     float* bias_l = xyz_l + IP_W_XYZ;
     float* msm = bias_l + IP_NBIAS;
     float* mss = msm + IH_NW * 64;
@@ -373,6 +398,23 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
     // Static priority instead of a flip around the MFMA phase of every pass: the second-dispatched half of the workgroup (waves 4-7, the second query)
     // loses the issue arbitration to its older SIMD partner on every phase; raised once, it takes the partner's timing (profiles/NOTES_unpacked_valu.md)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+    // AHEAD: this wave's staging slots, and what the trip about to start needs in registers: its neighbour id and query-minus-neighbour coordinate
+    const f32x4* stage = (const f32x4*)pps_smem + 2 * IH_CH4 + wave * (IH_STAGE_BLOCKS * 64);
+    const unsigned stage_lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)stage);
+    int64_t inext = 0;
+    float cnext = 0.f;
+    if constexpr (AHEAD) {
+        if (count > 0) {                 // the first trip's data: the same loads, waited for here, once per launch
+            const InterpIds f = interp_ids(first, wave, n, g, Q, k, idx, query);
+            inext = f.id;
+            const float qx = f.qx;
+            const char* gsrc = (const char*)G + inext * 1024 + g * 16;
+#pragma unroll
+            for (int bb = 0; bb < IH_STAGE_BLOCKS; ++bb) gather_piece_async(gsrc + bb * 64, stage_lds + bb * 1024);
+            cnext = (g < 3) ? (qx - pts[inext * 3 + g]) : 0.f;
+            stream_wait();
+        }
+    }
     for (int it = 0; CLAIM ? tile >= 0 : it < count; ++it) {
         if constexpr (CLAIM) {
             if (threadIdx.x == 0) pend = atomicAdd(head + PPS_CLAIM_INTERP + slot[1], 1);      // for the trip after this one
@@ -384,10 +426,38 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
         const int64_t qc = qv ? qi : Q - 1;
         const int row = wq * 16 + n;
         const bool valid = row < k;
-        const int64_t i = idx[qc * k + (valid ? row : 0)];
-
         HiLo x[8], y[8];
-        {
+        bool more = false;               // AHEAD: this workgroup has a trip after this one
+        float qnext = 0.f, pnext = 0.f;
+        const char* gnext = nullptr;
+        if constexpr (AHEAD) {
+            const int64_t i = inext;
+            const float coord = cnext;
+            f32x4 a[8], a8[8];           // blocks 0..7 (staged) and 8..15 (loaded)
+            const f32x4* grow = (const f32x4*)(G + i * 256) + g;
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) a8[bb] = grow[4 * (8 + bb)];
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) a[bb] = stage[bb * 64 + lane];
+            // the same xyz_blocks<16> / relu_blocks<16> / split in two halves: the staged blocks do not wait for the loaded ones
+            xyz_blocks<8>(coord, a, xyz_l, lane);
+            relu_blocks<8>(a);
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) x[kb] = split_f16_r(amax, a[2 * kb], a[2 * kb + 1]);
+            xyz_blocks<8>(coord, a8, xyz_l + 8 * 64, lane);
+            relu_blocks<8>(a8);
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) x[4 + kb] = split_f16_r(amax, a8[2 * kb], a8[2 * kb + 1]);
+            // the next trip's id and query coordinate: behind the last use of the loaded blocks (loads return in order: issued earlier, the wait
+            // for those blocks would wait for these too); in flight under the first step of fc2, whose stream_wait() covers them
+            more = it + 1 < count;
+            if (more) {
+                const InterpIds f = interp_ids(tile + stride, wave, n, g, Q, k, idx, query);
+                inext = f.id;
+                qnext = f.qx;
+            }
+        } else {
+            const int64_t i = idx[qc * k + (valid ? row : 0)];
             f32x4 a[16];
             const f32x4* grow = (const f32x4*)(G + i * 256) + g;
 #pragma unroll
@@ -412,9 +482,30 @@ __global__ __launch_bounds__(IH_NT, 2) void interp_pool_f16x3_kernel(const float
 #pragma unroll
         for (int c = 0; c < 16 / IH_OB; ++c)                           // fc2: output blocks IH_OB c .. = k-blocks IH_OB/2 c .. of fc3
             IH_STEP(false, x, bias4 + 4 * IH_OB * c, 1, ([&](int p, const f32x4& o0, const f32x4& o1) { y[IH_OB / 2 * c + p] = split_f16_r(amax, o0, o1); }));
+        if constexpr (AHEAD) {
+            if (more) {                                                // the id is back: the pts row, and the first byte of this lane's part of the G row
+                gnext = (const char*)G + inext * 1024 + g * 16;
+                pnext = pts[inext * 3 + (g < 3 ? g : 2)];              // every lane loads (no branch, no wait behind it); g = 3 is dropped below
+            }
+        }
 #pragma unroll
-        for (int c = 0; c < 16 / IH_OB; ++c)                           // fc3
+        for (int c = 0; c < 16 / IH_OB; ++c) {                         // fc3
+            if constexpr (AHEAD) {
+                // block c of the next trip's G rows, ahead of the step: the ring's pieces follow after k-steps 0, 2, 4, 6, the step's stream_wait()
+                // covers this one too.  One running address, opaque: not eight hoisted ones
+                static_assert(16 / IH_OB == IH_STAGE_BLOCKS && IH_STAGE_BLOCKS == 8, "one staged block per step of fc3, half a row staged");
+                if (more) {
+                    gather_piece_async(gnext, stage_lds + c * 1024);
+                    gnext += 64;
+                    asm volatile("" : "+v"(gnext));
+                }
+            }
             IH_STEP(false, y, bias4 + 64 + 4 * IH_OB * c, 1, ([&](int p, const f32x4& o0, const f32x4& o1) { x[IH_OB / 2 * c + p] = split_f16_r(amax, o0, o1); }));
+        }
+        if constexpr (AHEAD) {
+            cnext = (g < 3) ? (qnext - pnext) : 0.f;
+            asm volatile("" : "+v"(cnext));      // here, behind waits the steps have had anyway: not sunk to the end of the trip behind the pooled store
+        }
         f32x4 b[4];
 #pragma unroll
         for (int c = 0; c < 4 / IH_OB; ++c)                            // fc_query: 64 heads
@@ -1774,6 +1865,16 @@ static int decode_tail_f32_impl(const float* pooled, const float* xbar, int64_t 
                                       gate);
 }
 
+// The schedule of the fixed-share interpolation kernel (interp_pool_f16x3_kernel, AHEAD): PPS_INTERP_AHEAD, read per call (tests and A/B runs switch
+// it): 0 = every trip fetches its own ids and G rows at its head (the reference schedule), unset or anything else = one trip ahead.  Same bits.
+#ifndef PPS_INTERP_AHEAD_DEFAULT
+#define PPS_INTERP_AHEAD_DEFAULT 1
+#endif
+static bool interp_ahead() {
+    const char* e = getenv("PPS_INTERP_AHEAD");
+    return (e && *e) ? atoi(e) != 0 : PPS_INTERP_AHEAD_DEFAULT != 0;
+}
+
 // head: the claim words of the decoder workspace, or null for the fixed share (so for the two split-precision launchers below)
 static int interp_pool_f16x3_impl(const float* G, const float* pts, const float* query, const int64_t* idx, int64_t q, int k, const float* wxyz,
                                   const void* w16, const float* bias, float* pooled, int32_t* range_flag, int* head, void* stream) {
@@ -1781,6 +1882,9 @@ static int interp_pool_f16x3_impl(const float* G, const float* pts, const float*
     if (q == 0) return PPS_OK;
     if (!G || !pts || !query || !idx || !wxyz || !w16 || !bias || !pooled) return PPS_ERR_ARG;
     const int grid = grid_for((q + IH_NW / 4 - 1) / (IH_NW / 4), chip_wgs(IH_WG_PER_CU));      // one 8-wave workgroup per CU (IH_NT = 512)
+    if (head == nullptr && interp_ahead())
+        return launch<interp_pool_f16x3_kernel<false, true>>(grid, IH_NT, IH_LDS_BYTES_AHEAD, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16,
+                                                             bias, pooled, (int*)range_flag, (int*)nullptr);
     if (head != nullptr)
         return launch<interp_pool_f16x3_kernel<true>>(grid, IH_NT, IH_LDS_BYTES, stream, G, pts, query, idx, q, k, wxyz, (const f32x4*)w16, bias, pooled,
                                                       (int*)range_flag, head);

@@ -11,8 +11,9 @@ ORDER = ['interp_pool_kernel', 'interp_pool_f16x3_kernel', 'pointnet_feat_rows_k
 
 def main(prefix):
     k = json.load(open(prefix + '_pmc.json'))['kernels']
-    # a kernel whose name the profiler did not demangle (half8 arguments) is listed under its mangled name
-    for plain in ('pointnet_stn_fc_h_kernel', 'pointnet_stn_head_h_kernel', 'pointnet_fc3_feat_rows_kernel'):
+    # a kernel whose name the profiler did not demangle (half8 arguments) is listed under its mangled name; the split-precision interpolation
+    # kernel under the instantiation that ran (`<false, true>`: fixed share, one trip ahead)
+    for plain in ('pointnet_stn_fc_h_kernel', 'pointnet_stn_head_h_kernel', 'pointnet_fc3_feat_rows_kernel', 'interp_pool_f16x3_kernel'):
         k = dict(k, **{plain: v for n, v in k.items() if plain in n})
     import os
     tag = os.path.basename(prefix)

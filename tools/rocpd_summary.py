@@ -44,8 +44,11 @@ def main(src, dst):
             out[short(name)].setdefault('n', {})[counter] = n
     open(dst + '_rocprof_summary.txt', 'w').write('\n'.join(lines) + '\n')
     # the dominant kernel of the run: in an f16x3 run the fp32 kernel of the same name also appears (the gated fall-back launch, a few microseconds)
-    # (the split-precision kernel is a template over its tile assignment: `interp_pool_f16x3_kernel<false>` = fixed share, `<true>` = claims)
-    names = ('interp_pool_kernel', 'interp_pool_f16x3_kernel', 'interp_pool_f16x3_kernel<false>', 'interp_pool_f16x3_kernel<true>')
+    # (the split-precision kernel is a template over its tile assignment and its schedule: `interp_pool_f16x3_kernel<false, true>` = fixed share one
+    # trip ahead (the product), `<false, false>` = fixed share, every trip fetching its own data, `<true, false>` = claims; `<false>` / `<true>`:
+    # libraries from before the second argument)
+    names = ('interp_pool_kernel', 'interp_pool_f16x3_kernel', 'interp_pool_f16x3_kernel<false>', 'interp_pool_f16x3_kernel<true>',
+             'interp_pool_f16x3_kernel<false, true>', 'interp_pool_f16x3_kernel<false, false>', 'interp_pool_f16x3_kernel<true, false>')
     k = max((out.get(n, {}) for n in names), key=lambda v: v.get('avg_us', 0.0))
     # the GPU box has no .git: the caller passes the commit the snapshot was taken at (PPS_GIT_HEAD=$(git rev-parse --short=12 HEAD))
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))

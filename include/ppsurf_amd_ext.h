@@ -308,6 +308,37 @@ int ppsx_decimate_move(const int64_t* win, int64_t nw, const int32_t* src, const
                        int32_t* rename, void* stream);
 int ppsx_decimate_rename(const int64_t* faces, int64_t nf, int64_t nv, const int32_t* rename, int64_t* out, uint8_t* keep, void* stream);
 
+/* ---- isotropic remeshing: short-edge collapse and tangential relaxation (csrc/pps_remesh.hip) ----------------------------------------------
+ * new capability: replaces nothing -- the reference has no remeshing, and decimate, flip, subdivide and smooth stay as they are.  Driven by
+ * ppsurf_amd/remesh.py; the rules are written out at the top of csrc/pps_remesh.hip and in DESIGN.md section 30.  The rows, the regular
+ * vertices and the priorities are those of the decimation above (section 22), and the rest of a collapse round is its entries.  All
+ * arithmetic is fp64, every operation rounded on its own; one thread per entry or vertex; no atomics, no LDS, no square root.  A row whose
+ * offsets are not 0 <= o0 <= o1 <= the count is taken as empty and an index out of range is skipped; neither is read through.
+ *   ppsx_remesh_short_edges  prio u64 [ne,3]: for the entry e = (a, b) = (src[e], nbr[e]) with a < b, both ends regular, exactly two common
+ *                            entries c, d in the rows of a and b and not (a face of a holds c and d and a face of b holds c and d):
+ *                            len2 = (dx dx + dy dy) + dz dz of P_b - P_a must be < min2; with mid = (P_a + P_b) * 0.5 every face of a, and of
+ *                            b without a, that holds one end only must keep a positive n . n' with that end at mid; and every entry w of
+ *                            the rows of a and b other than a, b must have |P_w - mid|^2 <= max2 (+inf: no bound).  A candidate gets
+ *                            (the bits of len2, h(key), key), every other entry NONE three times.  Every row of prio is written.
+ *                            nv, nf or ne < 0 or > 2^31 - 1, ni < 0, min2 or max2 negative or a NaN, or -- with ne > 0 -- a NULL nbr, src
+ *                            or prio, with nv > 0 a NULL pos, offsets, inc_offsets or regular, a NULL faces with nf > 0 or a NULL inc
+ *                            with ni > 0: PPS_ERR_ARG, nothing is launched or written.  ne == 0: 0, nothing is launched.
+ *   ppsx_remesh_relax_pass   y f64 [nv,3], state u8 [nv]: one Jacobi pass over x f64 [nv,3].  A vertex that is not regular is copied
+ *                            (state 0).  A regular v: c = the mean of its row (summed ascending from +0.0), d = c - P_v, N = the sum of
+ *                            the cross products (P_i1 - P_i0) x (P_i2 - P_i0) of its incidence row (ascending), t = d - N * ((N . d) /
+ *                            (N . N)), P' = P_v + lam * t.  Copied with state 2 when N . N is 0 or not finite or a component of t is not
+ *                            finite; copied with state 3 when a face of its row, its corners at v replaced by P' and the others as in x,
+ *                            does not keep a positive n . n'; else y_v = P' and state 1.  Every row of y and state is written.
+ *                            nv or nf < 0 or > 2^31 - 1, ne or ni < 0, lam not in (0, 1], y == x, or -- with nv > 0 -- a NULL x, offsets,
+ *                            inc_offsets, regular, y or state, a NULL faces with nf > 0, a NULL nbr with ne > 0 or a NULL inc with
+ *                            ni > 0: PPS_ERR_ARG, nothing is launched or written.  nv == 0: 0, nothing is launched. */
+int ppsx_remesh_short_edges(const double* pos, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* offsets, const int32_t* nbr,
+                            const int32_t* src, int64_t ne, const int64_t* inc_offsets, const int32_t* inc, int64_t ni, const uint8_t* regular,
+                            double min2, double max2, uint64_t* prio, void* stream);
+int ppsx_remesh_relax_pass(const double* x, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* offsets, const int32_t* nbr, int64_t ne,
+                           const int64_t* inc_offsets, const int32_t* inc, int64_t ni, const uint8_t* regular, double lam, double* y,
+                           uint8_t* state, void* stream);
+
 /* ---- orientation: coherent, outward winding per component (csrc/pps_orient.hip) -----------------------------------------------------------
  * new capability: replaces nothing -- the reference has no such stage and every other stage takes the winding as it comes.  Driven by
  * ppsurf_amd/orient.py (the pairs and their edge slots by ppsurf_amd/topology.py); the rule and what the parity adds to the labelling argument of

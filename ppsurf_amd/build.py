@@ -18,8 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libppsurf_amd.so')
 SOURCES = ['pps_decode.hip', 'pps_knn.hip', 'pps_grow.hip', 'pps_mc.hip', 'pps_mesh.hip', 'pps_fkaconv.hip', 'pps_sample.hip', 'pps_train.hip', 'pps_csr.hip', 'pps_fka_train.hip', 'pps_bn_train.hip',
-           'pps_attn_train.hip', 'pps_rows_train.hip', 'pps_gemm_train.hip', 'pps_optim.hip', 'pps_eval.hip', 'pps_vis.hip', 'pps_scan.hip', 'pps_cloud.hip', 'pps_simplify.hip', 'pps_transfer.hip', 'pps_trim.hip', 'pps_smooth.hip', 'pps_normals.hip', 'pps_fill.hip', 'pps_denoise.hip', 'pps_pieces.hip', 'pps_decimate.hip', 'pps_orient.hip', 'pps_weld.hip', 'pps_manifold.hip', 'pps_labels.hip', 'pps_flip.hip', 'pps_subdivide.hip', 'pps_intersect.hip', 'pps_pack.cpp']
-HEADERS = ['pps_common.h', 'pps_fka_common.h', 'pps_rows_train_impl.h', 'pps_head_chain_impl.h', 'pps_sweep.h', 'pps_rng.h', 'pps_cells.h', 'pps_tri.h', 'pps_faces.h', 'pps_labels.h', os.path.join('..', '..', 'include', 'ppsurf_amd.h'),
+           'pps_attn_train.hip', 'pps_rows_train.hip', 'pps_gemm_train.hip', 'pps_optim.hip', 'pps_eval.hip', 'pps_vis.hip', 'pps_scan.hip', 'pps_cloud.hip', 'pps_simplify.hip', 'pps_transfer.hip', 'pps_trim.hip', 'pps_smooth.hip', 'pps_normals.hip', 'pps_fill.hip', 'pps_denoise.hip', 'pps_pieces.hip', 'pps_decimate.hip', 'pps_orient.hip', 'pps_weld.hip', 'pps_manifold.hip', 'pps_labels.hip', 'pps_flip.hip', 'pps_subdivide.hip', 'pps_intersect.hip', 'pps_remesh.hip', 'pps_pack.cpp']
+HEADERS = ['pps_common.h', 'pps_fka_common.h', 'pps_rows_train_impl.h', 'pps_head_chain_impl.h', 'pps_sweep.h', 'pps_rng.h', 'pps_cells.h', 'pps_tri.h', 'pps_faces.h', 'pps_labels.h', 'pps_collapse.h', os.path.join('..', '..', 'include', 'ppsurf_amd.h'),
            os.path.join('..', '..', 'include', 'ppsurf_amd_ext.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC']
 

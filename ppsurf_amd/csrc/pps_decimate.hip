@@ -38,50 +38,14 @@
 // Every index is range-checked before it becomes an address; a row whose offsets are not 0 <= o0 <= o1 <= count is taken as empty.
 #include <math.h>
 
+#include "pps_collapse.h"
 #include "pps_common.h"
 #include "pps_faces.h"
 #include "../../include/ppsurf_amd_ext.h"
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr u64 NONE = ~0ull;
-
-struct Prio {
-    u64 cost, hash, key;
-};
-
-__device__ __forceinline__ bool less(const Prio& p, const Prio& q) {
-    if (p.cost != q.cost) return p.cost < q.cost;
-    if (p.hash != q.hash) return p.hash < q.hash;
-    return p.key < q.key;
-}
-
-__device__ __forceinline__ bool same(const Prio& p, const Prio& q) { return p.cost == q.cost && p.hash == q.hash && p.key == q.key; }
-
-__device__ __forceinline__ Prio load_prio(const uint64_t* __restrict__ t, int64_t i) { return Prio{t[3 * i], t[3 * i + 1], t[3 * i + 2]}; }
-
-__device__ __forceinline__ void store_prio(uint64_t* __restrict__ t, int64_t i, const Prio& p) {
-    t[3 * i] = p.cost;
-    t[3 * i + 1] = p.hash;
-    t[3 * i + 2] = p.key;
-}
-
-__device__ __forceinline__ u64 mix(u64 key) {
-    u64 z = key + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ void open_row(const int64_t* __restrict__ offsets, int64_t v, int64_t count, int64_t& p, int64_t& end) {
-    const int64_t o0 = offsets[v], o1 = offsets[v + 1];
-    const bool ok = o0 >= 0 && o0 <= o1 && o1 <= count;
-    p = ok ? o0 : 0;
-    end = ok ? o1 : 0;
-}
-
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < (double)INFINITY; }          // false for a NaN
+using namespace pps_collapse;          // Prio and its order, mix, open_row, the link-rule merge, plane_of
 
 __global__ __launch_bounds__(256) void regular_kernel(const int64_t* __restrict__ offsets, const int32_t* __restrict__ mult, int64_t ne,
                                                       const int64_t* __restrict__ inc_offsets, int64_t ni, int64_t nv, uint8_t* __restrict__ regular) {
@@ -93,26 +57,6 @@ __global__ __launch_bounds__(256) void regular_kernel(const int64_t* __restrict_
     bool ok = fend - fp >= 1 && fend - fp == end - p;
     for (; ok && p < end; ++p) ok = mult[p] == 2;
     regular[v] = ok ? 1 : 0;
-}
-
-// The corners of a face relative to mid, its normal and its plane offset.
-struct Plane {
-    double q[3][3], n[3], m;
-};
-
-__device__ __forceinline__ void plane_of(const double* __restrict__ pos, int64_t i0, int64_t i1, int64_t i2, const double mid[3], Plane& f) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        f.q[0][k] = pos[3 * i0 + k] - mid[k];
-        f.q[1][k] = pos[3 * i1 + k] - mid[k];
-        f.q[2][k] = pos[3 * i2 + k] - mid[k];
-    }
-    const double ux = f.q[1][0] - f.q[0][0], uy = f.q[1][1] - f.q[0][1], uz = f.q[1][2] - f.q[0][2];
-    const double wx = f.q[2][0] - f.q[0][0], wy = f.q[2][1] - f.q[0][1], wz = f.q[2][2] - f.q[0][2];
-    f.n[0] = uy * wz - uz * wy;
-    f.n[1] = uz * wx - ux * wz;
-    f.n[2] = ux * wy - uy * wx;
-    f.m = (f.n[0] * f.q[0][0] + f.n[1] * f.q[0][1]) + f.n[2] * f.q[0][2];
 }
 
 // One thread per adjacency entry: rules (1) to (6).
@@ -130,21 +74,10 @@ __global__ __launch_bounds__(256) void edges_kernel(const double* __restrict__ p
     bool live = a >= 0 && a < b && b < nv && regular[a] != 0 && regular[b] != 0;
     int64_t c = -1, d = -1;
     if (live) {                                                      // the link rule: the common neighbours by a merge
-        int64_t pa, ea, pb, eb;
-        open_row(offsets, a, ne, pa, ea);
-        open_row(offsets, b, ne, pb, eb);
-        int common = 0;
-        while (pa < ea && pb < eb) {
-            const int32_t va = nbr[pa], vb = nbr[pb];
-            if (va == vb) {
-                if (common == 0) c = va;
-                if (common == 1) d = va;
-                ++common;
-            }
-            pa += va <= vb;
-            pb += vb <= va;
-        }
-        live = common == 2;
+        const Common both = common_neighbours(offsets, nbr, ne, a, b);
+        c = both.c;
+        d = both.d;
+        live = both.count == 2;
     }
     if (live) {
         double mid[3], d2 = 0.0;
@@ -210,7 +143,7 @@ __global__ __launch_bounds__(256) void edges_kernel(const double* __restrict__ p
             }
         }
         live = !(tet_a && tet_b) && is_finite(cost) && !folds;
-        if (live) mine = Prio{(u64)__double_as_longlong(cost), mix(((u64)a << 32) | (u64)b), ((u64)a << 32) | (u64)b};
+        if (live) mine = prio_of(cost, a, b);
     }
     store_prio(prio, e, mine);
 #pragma unroll

@@ -45,18 +45,26 @@ def _rows(F, nv):
     return {'offsets': offsets, 'nbr': nbr, 'mult': mult, 'src': src, 'inc_offsets': inc_offsets, 'inc': inc, 'regular': regular}
 
 
+def _winners(rows, prio, nv):
+    """flag u8 [ne] of the priorities prio of a round: the vertex minimum, the ring minimum and the winners (remesh.py takes its rounds
+    through here too)."""
+    ne, dev = int(rows['nbr'].shape[0]), prio.device
+    flag = torch.empty(ne, dtype=torch.uint8, device=dev)
+    m1, best = torch.empty(nv, 3, dtype=torch.int64, device=dev), torch.empty(nv, 3, dtype=torch.int64, device=dev)
+    _lib.call('ppsx_decimate_vertex_min', rows['offsets'], rows['nbr'], ne, nv, prio, m1)
+    _lib.call('ppsx_decimate_ring_min', rows['offsets'], rows['nbr'], ne, nv, m1, best)
+    _lib.call('ppsx_decimate_winners', rows['src'], rows['nbr'], ne, nv, prio, best, flag)
+    return flag
+
+
 def _candidates(P, F, rows):
     """(prio int64 [ne,3] holding u64 bits, x f64 [ne,3], fell u8 [ne], flag u8 [ne]) of a round: the four kernels."""
     nv, nf, ne, dev = int(P.shape[0]), int(F.shape[0]), int(rows['nbr'].shape[0]), F.device
     prio, x = torch.empty(ne, 3, dtype=torch.int64, device=dev), torch.empty(ne, 3, dtype=torch.float64, device=dev)
-    fell, flag = torch.empty(ne, dtype=torch.uint8, device=dev), torch.empty(ne, dtype=torch.uint8, device=dev)
-    m1, best = torch.empty(nv, 3, dtype=torch.int64, device=dev), torch.empty(nv, 3, dtype=torch.int64, device=dev)
+    fell = torch.empty(ne, dtype=torch.uint8, device=dev)
     _lib.call('ppsx_decimate_edges', P, nv, F, nf, rows['offsets'], rows['nbr'], rows['src'], ne, rows['inc_offsets'], rows['inc'],
               int(rows['inc'].shape[0]), rows['regular'], prio, x, fell)
-    _lib.call('ppsx_decimate_vertex_min', rows['offsets'], rows['nbr'], ne, nv, prio, m1)
-    _lib.call('ppsx_decimate_ring_min', rows['offsets'], rows['nbr'], ne, nv, m1, best)
-    _lib.call('ppsx_decimate_winners', rows['src'], rows['nbr'], ne, nv, prio, best, flag)
-    return prio, x, fell, flag
+    return prio, x, fell, _winners(rows, prio, nv)
 
 
 def _first(prio, win, need):

@@ -1,4 +1,4 @@
-"""The frame of the commands that work on a mesh in its own box: smooth, denoise, fill, pieces, decimate, orient, weld, manifold, flip, subdivide, intersect and normals
+"""The frame of the commands that work on a mesh in its own box: smooth, denoise, fill, pieces, decimate, orient, weld, manifold, flip, subdivide, intersect, remesh and normals
 (DESIGN.md section 18).  `load` reads and checks the file and centres it, `Mesh.to_device` uploads it, and three writers put the result
 back: as read, gathered through rows, or moved positions on the centre.  The stages work on row numbers and on the centred float32 copy,
 so whatever they do not move is written from the file's own float64 values and colours.  trim and transfer centre on the scan's box and

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -27,10 +27,8 @@ SIGN = -2 ** 63                            # x ^ SIGN orders the bits of a u64 k
 
 def _checked_params(max_faces, max_rounds):
     """(max_faces, max_rounds) as ints or a ValueError: max_faces an integer in 4..2^31 - 1, max_rounds in 1..2^31 - 1, no bools."""
-    for name, value, least in (('max_faces', max_faces, MIN_FACES), ('max_rounds', max_rounds, 1)):
-        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not least <= int(value) <= MAX_COUNT:
-            raise ValueError('{} must be an integer in {}..2^31 - 1, got {!r}'.format(name, least, value))
-    return int(max_faces), int(max_rounds)
+    return (params.integer('max_faces', max_faces, MIN_FACES, MAX_COUNT, '{}..2^31 - 1'.format(MIN_FACES)),
+            params.integer('max_rounds', max_rounds, 1, MAX_COUNT, '1..2^31 - 1'))
 
 
 def _rows(F, nv):
@@ -86,12 +84,20 @@ def _apply(P, F, rows, x, win):
     return out[keep.bool()]
 
 
+def _compacted(P, F, nv):
+    """(kept vertex rows int64 ascending, their positions f32, re-indexed faces) of the working mesh after the rounds: the vertices no face
+    uses are dropped with the order of the rest kept (remesh.py ends its collapse here too)."""
+    used, remap = topology.used_rows(F, nv)
+    kept = torch.nonzero(used).reshape(-1)
+    return kept, P[kept].float(), remap[F]
+
+
 def _decimate_rows(v, f, max_faces, max_rounds, timer=None):
     """(kept vertex rows int64 ascending, their positions f32, re-indexed faces, info) of a checked device mesh and checked parameters.  The
     rows are None when the mesh comes back as given.  timer(name) is called before every part of a round (tools/time_decimate.py)."""
     nv, nf = int(v.shape[0]), int(f.shape[0])
     tick = timer or (lambda name: None)
-    F = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0]) & ((f >= 0) & (f < nv)).all(dim=1)].contiguous()
+    F = f[topology.valid_faces(f, nv)].contiguous()
     info = {'faces_in': nf, 'faces_valid': int(F.shape[0]), 'faces_out': nf, 'vertices_in': nv, 'vertices_out': nv, 'rounds': 0, 'collapses': 0,
             'fallbacks': 0, 'locked_vertices': 0, 'reached': int(F.shape[0]) <= max_faces, 'max_faces': max_faces, 'max_rounds': max_rounds}
     if F.shape[0] == 0:
@@ -123,12 +129,9 @@ def _decimate_rows(v, f, max_faces, max_rounds, timer=None):
         tick('rows')
         rows = _rows(F, nv)
     tick('output')
-    used = torch.zeros(nv, dtype=torch.bool, device=f.device)
-    used[F.reshape(-1)] = True
-    kept = torch.nonzero(used).reshape(-1)
-    out_f = (torch.cumsum(used, 0) - 1)[F]
+    kept, out_v, out_f = _compacted(P, F, nv)
     info.update(faces_out=int(F.shape[0]), vertices_out=int(kept.shape[0]), fallbacks=int(fallbacks.item()), reached=int(F.shape[0]) <= max_faces)
-    return kept, P[kept].float(), out_f, info
+    return kept, out_v, out_f, info
 
 
 def decimate_mesh(verts: torch.Tensor, faces: torch.Tensor, max_faces, max_rounds=1000):
@@ -174,12 +177,8 @@ def main(argv=None):
         mesh.write_as_read(args.out_file)
     else:
         # a vertex that never moved is written as read; a moved one from its float32 position
-        kept, out_v = kept.cpu().numpy(), out_v.cpu().numpy()
-        moved = (out_v.view(np.int32) != mesh.local32[kept].view(np.int32)).any(axis=1)
-        pos = np.asarray(mesh.verts, dtype=np.float64)[kept]
-        pos[moved] = out_v[moved].astype(np.float64) + mesh.centre[None]
-        meshio.write_ply_mesh(args.out_file, pos, out_f.cpu().numpy(), double=mesh.double,
-                              colors_u8=None if mesh.colors is None else np.asarray(mesh.colors)[kept])
+        kept = kept.cpu().numpy()
+        mesh.write_origin(args.out_file, kept, out_v, out_f, None if mesh.colors is None else np.asarray(mesh.colors)[kept])
     print(json.dumps(info))
     return info
 

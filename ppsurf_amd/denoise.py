@@ -17,16 +17,14 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_ITERS = 1000
 
 
 def _checked_iters(name, value):
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) <= MAX_ITERS:
-        raise ValueError('{} must be an integer in 0..{}, got {!r}'.format(name, MAX_ITERS, value))
-    return int(value)
+    return params.integer(name, value, 0, MAX_ITERS)
 
 
 def _checked_threshold(threshold):

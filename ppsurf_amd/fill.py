@@ -15,7 +15,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here like from the siblings)
 
 MAX_EDGES = 4096
@@ -23,9 +23,7 @@ MAX_EDGES = 4096
 
 def _checked_max_edges(max_edges, name='max_edges'):
     """max_edges as an int, or a ValueError: an integer in 3..4096, no bool."""
-    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not 3 <= int(max_edges) <= MAX_EDGES:
-        raise ValueError('{} must be an integer in 3..{}, got {!r}'.format(name, MAX_EDGES, max_edges))
-    return int(max_edges)
+    return params.integer(name, max_edges, 3, MAX_EDGES)
 
 
 def fill_holes(verts: torch.Tensor, faces: torch.Tensor, max_edges: int):

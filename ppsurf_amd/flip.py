@@ -19,29 +19,36 @@ import json
 import math
 import sys
 
-import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
 NONE = -1                                  # 2^64 - 1, the priority of a pair that is no candidate, as the int64 that holds its bits
 
 
+def _finite(name, value):
+    return params.number(name, value, lambda x: True, 'a finite number')
+
+
+def _checked_angle(max_angle):
+    """max_angle as a float, or a ValueError: a finite number in (0, 90], no bool (remesh.py checks its flip_angle here)."""
+    angle = _finite('max_angle', max_angle)
+    if not 0.0 < angle <= 90.0:
+        raise ValueError('max_angle must lie in (0, 90], got {!r}'.format(max_angle))
+    return angle
+
+
 def _checked_params(max_angle, min_gain, max_rounds):
     """(max_angle, min_gain as floats, max_rounds as an int) or a ValueError: max_angle finite in (0, 90], min_gain finite and >= 0,
     max_rounds an integer in 1..2^31 - 1, no bools."""
-    for name, value in (('max_angle', max_angle), ('min_gain', min_gain)):
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(value):
-            raise ValueError('{} must be a finite number, got {!r}'.format(name, value))
-    if not 0.0 < float(max_angle) <= 90.0:
-        raise ValueError('max_angle must lie in (0, 90], got {!r}'.format(max_angle))
-    if float(min_gain) < 0.0:
+    _finite('max_angle', max_angle)                                      # both types before either range, the order the errors have always had
+    gain = _finite('min_gain', min_gain)
+    max_angle = _checked_angle(max_angle)
+    if gain < 0.0:
         raise ValueError('min_gain must be >= 0, got {!r}'.format(min_gain))
-    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 1 <= int(max_rounds) <= MAX_COUNT:
-        raise ValueError('max_rounds must be an integer in 1..2^31 - 1, got {!r}'.format(max_rounds))
-    return float(max_angle), float(min_gain), int(max_rounds)
+    return max_angle, gain, params.integer('max_rounds', max_rounds, 1, MAX_COUNT, '1..2^31 - 1')
 
 
 def _evaluate(v, F, cos2, min_gain, tick):

@@ -23,7 +23,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 from .trim import SupportGrid, _f32_not_below
 
@@ -35,9 +35,7 @@ F32_MAX = float(np.finfo(np.float32).max)
 
 def _checked_params(max_pairs):
     """max_pairs as an int, or a ValueError: an integer in 0..2^31 - 1, no bool."""
-    if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 0 <= int(max_pairs) <= MAX_COUNT:
-        raise ValueError('max_pairs must be an integer in 0..2^31 - 1, got {!r}'.format(max_pairs))
-    return int(max_pairs)
+    return params.integer('max_pairs', max_pairs, 0, MAX_COUNT, '0..2^31 - 1')
 
 
 def face_boxes(v, f):

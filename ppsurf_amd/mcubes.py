@@ -744,7 +744,6 @@ def clean_mesh_torch(verts, faces, min_component_faces=6, digits=8, welded=False
         ow = owner[order]
         a, b = _two_owner_pairs(skey[1:] == skey[:-1], ow, torch)
         faces = faces[~_small_component_faces(a, b, nf, int(min_component_faces))]
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=dev)           # compaction of the referenced vertices, order kept
-    used[faces.reshape(-1)] = True
-    remap = torch.cumsum(used, 0) - 1
+    from . import topology
+    used, remap = topology.used_rows(faces, verts.shape[0])                   # compaction of the referenced vertices, order kept
     return verts[used], remap[faces]

@@ -1,6 +1,7 @@
 """The frame of the commands that work on a mesh in its own box: smooth, denoise, fill, pieces, decimate, orient, weld, manifold, flip, subdivide, intersect, remesh and normals
-(DESIGN.md section 18).  `load` reads and checks the file and centres it, `Mesh.to_device` uploads it, and three writers put the result
-back: as read, gathered through rows, or moved positions on the centre.  The stages work on row numbers and on the centred float32 copy,
+(DESIGN.md section 18).  `load` reads and checks the file and centres it, `Mesh.to_device` uploads it, and four writers put the result
+back: as read, gathered through rows, moved positions on the centre, or -- for decimate, subdivide and remesh, which drop, move and add
+vertices -- every vertex through the row it came from (`write_origin`).  The stages work on row numbers and on the centred float32 copy,
 so whatever they do not move is written from the file's own float64 values and colours.  trim and transfer centre on the scan's box and
 simplify has its own reader: they are not served here.
 """
@@ -52,6 +53,17 @@ class Mesh:
         """The positions out_v f32 [nv,3] of the centred frame put back on the centre in float64; faces and colours as read."""
         meshio.write_ply_mesh(out_file, _host(out_v).astype(np.float64) + self.centre[None], self.faces, double=self.double,
                               colors_u8=self.colors)
+
+    def write_origin(self, out_file, origin, out_v, out_f, colors):
+        """The mesh out_v f32 / out_f of a stage that drops, moves and adds vertices: origin int64 [nv out] is the row as read of every
+        output vertex, -1 for one the stage made.  A vertex whose float32 bytes equal those of its origin row is written as read, every
+        other one from its float32 position put back on the centre; colors (uint8 [nv out, c] or None) are the caller's."""
+        origin, out_v = _host(origin), _host(out_v)
+        same = origin >= 0
+        same[same] = (out_v[same].view(np.int32) == self.local32[origin[same]].view(np.int32)).all(axis=1)
+        pos = out_v.astype(np.float64) + self.centre[None]
+        pos[same] = np.asarray(self.verts, dtype=np.float64)[origin[same]]
+        meshio.write_ply_mesh(out_file, pos, _host(out_f), double=self.double, colors_u8=colors)
 
 
 def load(path, prog, reader=None):

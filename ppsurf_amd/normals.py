@@ -15,7 +15,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, ops, topology
+from . import _lib, mesh_cli, meshio, ops, params, topology
 from .topology import CpuTensorError, vertex_incidence  # noqa: F401  (their home is topology.py; the names stay importable from here)
 
 MAX_K = 256
@@ -29,9 +29,7 @@ def _checked_weight(weight):
 
 
 def _checked_k(k):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
-        raise ValueError('k must be an integer in 1..{}, got {!r}'.format(MAX_K, k))
-    return int(k)
+    return params.integer('k', k, 1, MAX_K)
 
 
 def _vertex_normals(v, f, weight):

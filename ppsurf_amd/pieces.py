@@ -19,7 +19,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, labels, mesh_cli, meshio, topology
+from . import _lib, labels, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -27,11 +27,7 @@ TOP = 8                                    # the command lists that many first-r
 
 
 def _checked_count(name, value):
-    if value is None:
-        return None
-    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= MAX_COUNT:
-        raise ValueError('{} must be an integer in 1..2^31 - 1, got {!r}'.format(name, value))
-    return int(value)
+    return None if value is None else params.integer(name, value, 1, MAX_COUNT, '1..2^31 - 1')
 
 
 def _checked_rules(min_faces, min_diag_frac, keep_largest):
@@ -142,10 +138,9 @@ def _pieces_rows(verts, faces, min_faces, min_diag_frac, keep_largest):
     keep = _selected(table, rank, min_faces, min_diag_frac, keep_largest)
     cid = table['cid'].long()
     kept = faces[(cid >= 0) & keep[cid.clamp(min=0)]]
-    used = torch.zeros(nv, dtype=torch.bool, device=verts.device)
-    used[kept.reshape(-1)] = True
+    used, remap = topology.used_rows(kept, nv)
     rows = torch.nonzero(used).reshape(-1)
-    out_f = (torch.cumsum(used, 0) - 1)[kept]
+    out_f = remap[kept]
     first = torch.sort(rank)[1][:TOP]
     D2 = table['box_diag2']
     top = [[int(l), int(n), float(np.float64(d) / np.float64(D2)) if D2 > 0 else None]

@@ -18,7 +18,7 @@ import typing
 import numpy as np
 import torch
 
-from . import ops, mcubes, sharding
+from . import ops, mcubes, sharding, topology
 
 
 def _dilate(mask: torch.Tensor, r: int) -> torch.Tensor:
@@ -181,9 +181,8 @@ def small_components_removed(verts: torch.Tensor, faces: torch.Tensor, min_compo
     dropped, order kept: the last stage of mcubes.clean_mesh_torch without its merging by position."""
     if faces.shape[0]:
         faces = faces[~ops.mesh_small_components(faces.contiguous(), verts.shape[0], int(min_component_faces))]
-    used = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
-    used[faces.reshape(-1)] = True
-    return verts[used], (torch.cumsum(used, 0) - 1)[faces]
+    used, remap = topology.used_rows(faces, verts.shape[0])
+    return verts[used], remap[faces]
 
 
 def export_mesh_and_refine_vertices_region_growing_v3(network, latent: dict, pts_raw_ms, resolution: int, padding=0, mc_value=0,

@@ -23,7 +23,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, decimate, flip, mesh_cli, meshio, subdivide, topology
+from . import _lib, decimate, flip, mesh_cli, meshio, params, subdivide, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -32,29 +32,18 @@ NONE = -1                                  # 2^64 - 1, the first word of the pri
 STAGES = ('remesh', 'collapse', 'relax')
 
 
-def _is_number(value):
-    return not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating)) and math.isfinite(value)
-
-
 def _checked_collapse(min_edge, max_edge, max_rounds):
     """(min_edge float, max_edge float or None, max_rounds int) or a ValueError: min_edge a finite number > 0, max_edge None or a finite
     number >= min_edge, max_rounds an integer in 1..2^31 - 1, no bools."""
-    if not _is_number(min_edge) or not min_edge > 0:
-        raise ValueError('min_edge must be a finite number > 0, got {!r}'.format(min_edge))
-    if max_edge is not None and (not _is_number(max_edge) or not max_edge >= min_edge):
-        raise ValueError('max_edge must be None or a finite number >= min_edge = {!r}, got {!r}'.format(min_edge, max_edge))
-    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 1 <= int(max_rounds) <= MAX_COUNT:
-        raise ValueError('max_rounds must be an integer in 1..2^31 - 1, got {!r}'.format(max_rounds))
-    return float(min_edge), (None if max_edge is None else float(max_edge)), int(max_rounds)
+    least = params.number('min_edge', min_edge, lambda x: x > 0, 'a finite number > 0')
+    if max_edge is not None:
+        max_edge = params.number('max_edge', max_edge, lambda x: x >= least, 'None or a finite number >= min_edge = {!r}'.format(min_edge))
+    return least, max_edge, params.integer('max_rounds', max_rounds, 1, MAX_COUNT, '1..2^31 - 1')
 
 
 def _checked_relax(iters, lam, name='lam'):
     """(iters int, lam float) or a ValueError: iters an integer in 0..1000, lam a finite number in (0, 1], no bools."""
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= int(iters) <= MAX_ITERS:
-        raise ValueError('iters must be an integer in 0..{}, got {!r}'.format(MAX_ITERS, iters))
-    if not _is_number(lam) or not 0.0 < float(lam) <= 1.0:
-        raise ValueError('{} must be a finite number in (0, 1], got {!r}'.format(name, lam))
-    return int(iters), float(lam)
+    return params.integer('iters', iters, 0, MAX_ITERS), params.number(name, lam, lambda x: 0.0 < x <= 1.0, 'a finite number in (0, 1]')
 
 
 def _checked_remesh(target_edge, factor, iters, relax_lam, flip_angle, max_faces):
@@ -62,13 +51,10 @@ def _checked_remesh(target_edge, factor, iters, relax_lam, flip_angle, max_faces
     integer in 0..1000; relax_lam finite in (0, 1]; flip_angle and max_faces by the rules of flip.py and subdivide.py; no bools."""
     if (target_edge is None) == (factor is None):
         raise ValueError('exactly one of target_edge and factor must be given, got {!r} and {!r}'.format(target_edge, factor))
-    for name, value in (('target_edge', target_edge), ('factor', factor)):
-        if value is not None and (not _is_number(value) or not value > 0):
-            raise ValueError('{} must be a finite number > 0, got {!r}'.format(name, value))
+    target_edge, factor = (None if value is None else params.number(name, value, lambda x: x > 0, 'a finite number > 0')
+                           for name, value in (('target_edge', target_edge), ('factor', factor)))
     iters, relax_lam = _checked_relax(iters, relax_lam, 'relax_lam')
-    flip_angle = flip._checked_params(flip_angle, 1e-6, 100)[0]
-    max_faces = subdivide._checked_params(1.0, None, 100, max_faces)[3]
-    return (None if target_edge is None else float(target_edge)), (None if factor is None else float(factor)), iters, relax_lam, flip_angle, max_faces
+    return target_edge, factor, iters, relax_lam, flip._checked_angle(flip_angle), subdivide._checked_max_faces(max_faces)
 
 
 def _short_edges(P, F, rows, min2, max2):
@@ -86,7 +72,7 @@ def _collapsed(v, f, min_edge, max_edge, max_rounds, timer=None):
     kernels (with the host read), apply -- and before the output (tools/time_remesh.py)."""
     nv, nf = int(v.shape[0]), int(f.shape[0])
     tick = timer or (lambda name: None)
-    F = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0]) & ((f >= 0) & (f < nv)).all(dim=1)].contiguous()
+    F = f[topology.valid_faces(f, nv)].contiguous()
     info = {'faces_in': nf, 'faces_valid': int(F.shape[0]), 'faces_out': nf, 'vertices_in': nv, 'vertices_out': nv, 'rounds': 0, 'collapses': 0,
             'candidates': 0, 'locked_vertices': 0, 'converged': True, 'min_edge': min_edge, 'max_edge': max_edge, 'max_rounds': max_rounds}
     if F.shape[0] == 0:
@@ -116,12 +102,9 @@ def _collapsed(v, f, min_edge, max_edge, max_rounds, timer=None):
     tick('output')
     if info['collapses'] == 0:
         return None, None, f, info
-    used = torch.zeros(nv, dtype=torch.bool, device=f.device)
-    used[F.reshape(-1)] = True
-    kept = torch.nonzero(used).reshape(-1)
-    out_f = (torch.cumsum(used, 0) - 1)[F]
+    kept, out_v, out_f = decimate._compacted(P, F, nv)
     info.update(faces_out=int(F.shape[0]), vertices_out=int(kept.shape[0]))
-    return kept, P[kept].float(), out_f, info
+    return kept, out_v, out_f, info
 
 
 def collapse_short_edges(verts: torch.Tensor, faces: torch.Tensor, min_edge, max_edge=None, max_rounds=1000):
@@ -194,18 +177,6 @@ def relax_tangential(verts: torch.Tensor, faces: torch.Tensor, iters=1, lam=0.5)
     return (verts if out is None else out), faces, info
 
 
-def _median_edge(v, f):
-    """The square root of the lower median of the squared lengths of the distinct edges of the valid faces (subdivide's median), 0.0 without
-    a valid face."""
-    _, _, _, valid, keys = topology.edge_runs_keys(f, int(v.shape[0]))
-    invalid = int(f.shape[0]) - int(valid.sum().item())
-    live = int(keys.shape[0]) - (1 if invalid else 0)
-    if invalid == int(f.shape[0]) or live <= 0:
-        return 0.0
-    len2 = torch.sort(subdivide._priorities(v, keys, math.inf)[0][:live])[0]
-    return math.sqrt(len2[(live - 1) // 2].item())
-
-
 def _remeshed(v, f, target_edge, factor, iters, relax_lam, flip_angle, max_faces, colors=None, timer=None):
     """(origin int64 [nv out] on the host, verts f32, faces, colors, info) of a checked device mesh and checked parameters: origin is the
     given row of every output vertex, -1 for one that a split made; colors (a host array or None) are carried along -- a split gives the
@@ -214,12 +185,12 @@ def _remeshed(v, f, target_edge, factor, iters, relax_lam, flip_angle, max_faces
     nv, nf = int(v.shape[0]), int(f.shape[0])
     tick = timer or (lambda name: None)
     tick('median')
-    target = target_edge if factor is None else factor * (_median_edge(v, f) if nf else 0.0)
+    target = target_edge if factor is None else factor * (subdivide.median_edge(v, f) if nf else 0.0)
     low, high = (4.0 * target) / 5.0, (4.0 * target) / 3.0
     info = {'target_edge': target, 'low': low, 'high': high, 'faces_in': nf, 'faces_out': nf, 'vertices_in': nv, 'vertices_out': nv, 'iters': iters,
             'relax_lam': relax_lam, 'flip_angle': flip_angle, 'max_faces': max_faces, 'iterations': [], 'limited': False}
     origin = np.arange(nv, dtype=np.int64)
-    valid = nf > 0 and bool(((f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0]) & ((f >= 0) & (f < nv)).all(dim=1)).any().item())
+    valid = nf > 0 and bool(topology.valid_faces(f, nv).any().item())
     if not valid or not target > 0.0:
         return origin, v, f, colors, info
     V, F = v, f
@@ -279,17 +250,6 @@ def remesh_isotropic(verts: torch.Tensor, faces: torch.Tensor, target_edge=None,
     return out_v, out_f, info
 
 
-def _write(mesh, out_file, origin, out_v, out_f, colors):
-    """The result on the file's frame: a vertex whose float32 bytes equal those of its origin row is written as read, every other one from
-    its float32 position put back on the centre."""
-    out_v = out_v.cpu().numpy()
-    same = origin >= 0
-    same[same] = (out_v[same].view(np.int32) == mesh.local32[origin[same]].view(np.int32)).all(axis=1)
-    pos = out_v.astype(np.float64) + mesh.centre[None]
-    pos[same] = np.asarray(mesh.verts, dtype=np.float64)[origin[same]]
-    meshio.write_ply_mesh(out_file, pos, out_f.cpu().numpy(), double=mesh.double, colors_u8=colors)
-
-
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog='python -m ppsurf_amd.remesh',
@@ -321,7 +281,7 @@ def main(argv=None):
         origin, out_f, colors = np.arange(int(v.shape[0]), dtype=np.int64), f, mesh.colors
         out_v = v if out_v is None else out_v
     elif args.stage == 'collapse':
-        target = target_edge if factor is None else factor * (_median_edge(v, f) if int(f.shape[0]) else 0.0)
+        target = target_edge if factor is None else factor * (subdivide.median_edge(v, f) if int(f.shape[0]) else 0.0)
         if not target > 0.0:
             raise SystemExit('{} has no edge to take a target from'.format(args.mesh))
         kept, out_v, out_f, info = _collapsed(v, f, (4.0 * target) / 5.0, None, 1000)
@@ -332,7 +292,7 @@ def main(argv=None):
             colors = None if mesh.colors is None else np.asarray(mesh.colors)[origin]
     else:
         origin, out_v, out_f, colors, info = _remeshed(v, f, target_edge, factor, iters, relax_lam, flip_angle, max_faces, colors=mesh.colors)
-    _write(mesh, args.out_file, origin, out_v, out_f, colors)
+    mesh.write_origin(args.out_file, origin, out_v, out_f, colors)
     print(json.dumps(info))
     return info
 

@@ -21,7 +21,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, meshio, ops
+from . import _lib, meshio, ops, topology
 from .cells import CellGrid
 
 PLACEMENTS = ('quadric', 'mean')
@@ -129,9 +129,7 @@ class ClusterGrid(CellGrid):
         moved = pos[new]
         n_new = _cross(moved[:, 1] - moved[:, 0], moved[:, 2] - moved[:, 0])
         dot = (n_old[:, 0] * n_new[:, 0] + n_old[:, 1] * n_new[:, 1]) + n_old[:, 2] * n_new[:, 2]
-        used = torch.zeros(ncell, dtype=torch.bool, device=dev)
-        used[new.reshape(-1)] = True
-        remap = torch.cumsum(used, 0) - 1
+        used, remap = topology.used_rows(new, ncell)
         out_v, out_f = pos[used], remap[new]
         report.update(faces_out=int(out_f.shape[0]), verts_out=int(out_v.shape[0]), fallback=int(fell.sum()), flipped=int((~(dot > 0)).sum()))
         if keep:

@@ -12,10 +12,9 @@ import json
 import math
 import sys
 
-import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError, mesh_adjacency  # noqa: F401  (their home is topology.py; the names stay importable from here)
 
 MAX_ITERS = 1000
@@ -23,14 +22,13 @@ MAX_ITERS = 1000
 
 def _checked_params(iters, lam, mu):
     """(iters int, lam float, mu float) or a ValueError: iters an integer in 0..1000, lam finite in (0, 1], mu finite and 0 or < -lam."""
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 0 <= int(iters) <= MAX_ITERS:
-        raise ValueError('iters must be an integer in 0..{}, got {!r}'.format(MAX_ITERS, iters))
-    lam, mu = float(lam), float(mu)
+    iters = params.integer('iters', iters, 0, MAX_ITERS)
+    lam, mu = float(lam), float(mu)                                     # lam and mu stay loose: whatever float() takes (DESIGN.md section 18)
     if not (math.isfinite(lam) and 0.0 < lam <= 1.0):
         raise ValueError('lam must be a finite number in (0, 1], got {}'.format(lam))
     if not (math.isfinite(mu) and (mu == 0.0 or mu < -lam)):
         raise ValueError('mu must be 0 (plain Laplacian smoothing) or a finite number < -lam = {}, got {}'.format(-lam, mu))
-    return int(iters), lam, mu
+    return iters, lam, mu
 
 
 def smooth_mesh(verts: torch.Tensor, faces: torch.Tensor, iters: int, lam: float = 0.5, mu: float = -0.53):

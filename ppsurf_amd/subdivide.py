@@ -22,7 +22,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, mesh_cli, meshio, topology
+from . import _lib, mesh_cli, meshio, params, topology
 from .topology import CpuTensorError  # noqa: F401  (its home is topology.py; the name stays importable from here)
 
 MAX_COUNT = topology.MAX_COUNT
@@ -35,18 +35,15 @@ def _checked_params(max_edge, factor, max_rounds, max_faces):
     finite number > 0; max_rounds an integer in 1..2^31 - 1; max_faces None (the largest count) or an integer in 0..(2^32 - 1) // 3; no bools."""
     if (max_edge is None) == (factor is None):
         raise ValueError('exactly one of max_edge and factor must be given, got {!r} and {!r}'.format(max_edge, factor))
-    for name, value in (('max_edge', max_edge), ('factor', factor)):
-        if value is None:
-            continue
-        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not math.isfinite(value) or not value > 0:
-            raise ValueError('{} must be a finite number > 0, got {!r}'.format(name, value))
-    if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 1 <= int(max_rounds) <= MAX_COUNT:
-        raise ValueError('max_rounds must be an integer in 1..2^31 - 1, got {!r}'.format(max_rounds))
-    if max_faces is None:
-        max_faces = MAX_FACES
-    if isinstance(max_faces, bool) or not isinstance(max_faces, (int, np.integer)) or not 0 <= int(max_faces) <= MAX_FACES:
-        raise ValueError('max_faces must be an integer in 0..{}, got {!r}'.format(MAX_FACES, max_faces))
-    return (None if max_edge is None else float(max_edge)), (None if factor is None else float(factor)), int(max_rounds), int(max_faces)
+    max_edge, factor = (None if value is None else params.number(name, value, lambda x: x > 0, 'a finite number > 0')
+                        for name, value in (('max_edge', max_edge), ('factor', factor)))
+    return max_edge, factor, params.integer('max_rounds', max_rounds, 1, MAX_COUNT, '1..2^31 - 1'), _checked_max_faces(max_faces)
+
+
+def _checked_max_faces(max_faces):
+    """max_faces as an int, or a ValueError: None (the largest count) or an integer in 0..(2^32 - 1) // 3, no bool (remesh.py checks its
+    max_faces here)."""
+    return MAX_FACES if max_faces is None else params.integer('max_faces', max_faces, 0, MAX_FACES)
 
 
 def _runs(F, nv):
@@ -66,6 +63,21 @@ def _priorities(v, keys, max2):
     len2, prio = torch.empty(ne, dtype=torch.float64, device=v.device), torch.empty(ne, dtype=torch.int64, device=v.device)
     _lib.call('ppsx_subdivide_edges', keys, ne, v, int(v.shape[0]), max2, len2, prio)
     return len2, prio
+
+
+def median_edge(v, f, edges=None):
+    """The square root of the lower median of the squared lengths of the distinct edges of the valid faces of a checked device mesh, 0.0
+    without a valid face (remesh.py takes its target from here).  edges: (the number of valid faces, the keys of topology.edge_runs_keys)
+    from a caller that has them already, so that no mesh is sorted twice."""
+    if edges is None:
+        _, _, _, valid, keys = topology.edge_runs_keys(f, int(v.shape[0]))
+        edges = int(valid.sum().item()), keys
+    faces_valid, keys = edges
+    live = int(keys.shape[0]) - (1 if faces_valid < int(f.shape[0]) else 0)            # without the run of the invalid faces
+    if faces_valid == 0 or live <= 0:
+        return 0.0
+    len2 = torch.sort(_priorities(v, keys, math.inf)[0][:live])[0]
+    return math.sqrt(len2[(live - 1) // 2].item())
 
 
 def _evaluate(v, F, max2, tick):
@@ -107,9 +119,7 @@ def _subdivided(v, f, max_edge, factor, max_rounds, max_faces, timer=None):
     V, F = v, f if info['faces_valid'] == nf0 else torch.where(valid[:, None], f, torch.full_like(f, -1))
     if max_edge is None:
         tick('kernels')
-        live = int(keys.shape[0]) - (1 if info['faces_valid'] < nf0 else 0)              # without the run of the invalid faces
-        len2 = torch.sort(_priorities(v, keys, math.inf)[0][:live])[0]
-        info['max_edge'] = factor * math.sqrt(len2[(live - 1) // 2].item())
+        info['max_edge'] = factor * median_edge(v, f, (info['faces_valid'], keys))
     max2 = info['max_edge'] * info['max_edge']
     ends, first = [], True
     while True:
@@ -211,11 +221,11 @@ def main(argv=None):
     if out_v is None:
         mesh.write_as_read(args.out_file)
     else:
-        # the given vertices keep the file's own values; only the new ones come back from the centred float32 frame
-        verts = np.concatenate([mesh.verts, out_v[nv:].cpu().numpy().astype(np.float64) + mesh.centre[None]])
+        # the given vertices keep their rows and bytes, so they are written as read; only the new ones come back from the centred float32 frame
         if colors is not None:
             colors = midpoint_colors(colors, ends.cpu().numpy(), info['added'])
-        meshio.write_ply_mesh(args.out_file, verts, out_f.cpu().numpy(), double=mesh.double, colors_u8=colors)
+        origin = np.concatenate([np.arange(nv, dtype=np.int64), np.full(info['splits'], -1, dtype=np.int64)])
+        mesh.write_origin(args.out_file, origin, out_v, out_f, colors)
     print(json.dumps(info))
     return info
 

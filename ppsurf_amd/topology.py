@@ -39,6 +39,21 @@ def checked_mesh(what, verts, faces, limit=False, finite=True):
     return v, f
 
 
+def valid_faces(faces, nv):
+    """bool [nf]: the faces int64 [nf,3] whose indices lie in [0, nv) and are pairwise distinct -- the rule of csrc/pps_faces.h and of
+    tests/topology_spec.py as a torch expression, for the stages that filter the faces themselves.  Only comparisons: CPU tensors work too."""
+    f = faces
+    return (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0]) & ((f >= 0) & (f < nv)).all(dim=1)
+
+
+def used_rows(faces, n):
+    """(used bool [n], remap int64 [n]) of faces that index n rows: which rows a face uses, and remap = cumsum(used) - 1, the row of every
+    used one after the unused are dropped with the order kept.  `verts[used]` and `remap[faces]` are the compacted mesh."""
+    used = torch.zeros(n, dtype=torch.bool, device=faces.device)
+    used[faces.reshape(-1)] = True
+    return used, torch.cumsum(used, 0) - 1
+
+
 def live_keys(keys):
     """The keys int64 of a key entry in ascending order without the SENTINEL ones."""
     keys = torch.sort(keys)[0]

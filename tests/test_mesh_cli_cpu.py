@@ -1,4 +1,4 @@
-"""The command frame of the mesh stages without a GPU (ppsurf_amd/mesh_cli.py): the record of the loader and the three writers, each file
+"""The command frame of the mesh stages without a GPU (ppsurf_amd/mesh_cli.py): the record of the loader and the four writers, each file
 byte for byte what the stage's own meshio.write_ply_mesh call wrote before the frame existed."""
 import numpy as np
 import pytest
@@ -61,6 +61,54 @@ def test_the_writers_write_the_bytes_of_the_direct_calls(tmp_path, monkeypatch, 
     if double:                                                            # the add is a float64 add: a float32 one would lose the move
         moved = out_v.astype(np.float64) + centre[None]
         assert not np.array_equal(moved, (out_v + centre.astype(np.float32)[None]).astype(np.float64))
+
+
+@pytest.mark.parametrize('double', [False, True])
+@pytest.mark.parametrize('colored', [False, True])
+def test_write_origin_writes_the_bytes_of_the_three_mains(tmp_path, monkeypatch, double, colored):
+    """decimate, subdivide and remesh each wrote their result themselves before `write_origin`: restated here as the direct calls."""
+    from ppsurf_amd import meshio
+    verts, faces, colors = _mesh(double)
+    colors = colors if colored else None
+    mesh = _load(monkeypatch, verts, faces, colors, double)
+    centre, local32 = mesh.centre, mesh.local32
+    rng = np.random.default_rng(7)
+
+    def same(origin, out_v, out_f, out_c, pos):
+        a, b = str(tmp_path / 'frame.ply'), str(tmp_path / 'direct.ply')
+        before = origin.copy()
+        mesh.write_origin(a, origin, out_v, out_f, out_c)
+        meshio.write_ply_mesh(b, pos, out_f, double=double, colors_u8=out_c)
+        got, want = open(a, 'rb').read(), open(b, 'rb').read()
+        assert got == want and len(got) > 100 and np.array_equal(origin, before)
+
+    def ulp(x):
+        return np.nextafter(x, np.float32(np.inf))
+
+    # decimate: a subset in ascending order; row 1 of it moved by one ulp in one coordinate, the others not at all
+    kept, out_f = np.array([0, 1, 3, 4]), np.array([[0, 1, 2], [2, 1, 3]])
+    out_v = local32[kept].copy()
+    out_v[1, 2] = ulp(out_v[1, 2])
+    moved = (out_v.view(np.int32) != local32[kept].view(np.int32)).any(axis=1)
+    assert moved.tolist() == [False, True, False, False]
+    pos = np.asarray(verts, dtype=np.float64)[kept]
+    pos[moved] = out_v[moved].astype(np.float64) + centre[None]
+    same(kept, out_v, out_f, None if colors is None else np.asarray(colors)[kept], pos)
+    assert np.array_equal(pos[0], verts[0]) and not np.array_equal(pos[1], verts[1])
+    # subdivide: every row kept with its bytes, two appended
+    new = rng.standard_normal((2, 3)).astype(np.float32)
+    out_v, out_f = np.concatenate([local32, new]), np.array([[0, 1, 5], [5, 1, 2], [2, 1, 6], [6, 1, 3], [3, 1, 4]])
+    out_c = None if colors is None else np.concatenate([colors, rng.integers(0, 256, (2, 3)).astype(np.uint8)])
+    same(np.concatenate([np.arange(5, dtype=np.int64), np.full(2, -1, dtype=np.int64)]), out_v, out_f, out_c,
+         np.concatenate([verts, new.astype(np.float64) + centre[None]]))
+    # remesh: a permuted subset with new rows between; row 0 of the file moved, rows 3, 4 and 1 not
+    origin, out_f = np.array([3, -1, 0, 4, -1, 1], dtype=np.int64), np.array([[0, 1, 2], [2, 1, 3], [3, 4, 5]])
+    out_v = np.stack([local32[3], new[0], local32[0], local32[4], new[1], local32[1]])
+    out_v[2, 0] = ulp(out_v[2, 0])
+    pos = np.stack([verts[o] if o >= 0 and out_v[i].tobytes() == local32[o].tobytes() else out_v[i].astype(np.float64) + centre
+                    for i, o in enumerate(origin)])
+    assert [bool(np.array_equal(pos[i], verts[o])) for i, o in enumerate(origin)] == [True, False, False, True, False, True]
+    same(origin, out_v, out_f, None if colors is None else rng.integers(0, 256, (6, 3)).astype(np.uint8), pos)
 
 
 def test_the_loader_checks_the_gpu_first_and_refuses_non_finite_vertices(monkeypatch):

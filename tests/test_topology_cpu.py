@@ -1,5 +1,5 @@
 """CPU tier of the shared layer of the mesh stages: one CpuTensorError and one home for the row tables
-(ppsurf_amd/topology.py), the mesh-file front end of the five command lines (meshio.read_mesh_file, ply_stores_doubles)."""
+(ppsurf_amd/topology.py), its valid-face rule and its compaction on CPU tensors, the mesh-file front end of the five command lines (meshio.read_mesh_file, ply_stores_doubles)."""
 import numpy as np
 import pytest
 
@@ -24,6 +24,43 @@ def test_cpu_tensors_raise_the_one_error_with_the_guards_message():
         assert str(e.value) == '{}: tensor on cpu; inputs must be device tensors, there is no CPU path'.format(what)
     with pytest.raises(topology.CpuTensorError, match='got ndarray; inputs must be device tensors, there is no CPU path'):
         smooth.smooth_mesh(np.zeros((3, 3), dtype=np.float32), f, 1)
+
+
+def test_valid_faces_is_the_rule_of_the_specification():
+    import torch
+    import topology_spec
+    from ppsurf_amd import topology
+    nv = 5
+    faces = np.array([[0, 1, 2], [4, 3, 0],                                  # good, the largest index included
+                      [1, 1, 2], [3, 2, 2], [4, 0, 4], [2, 2, 2],            # a repeated index in each of the three positions, and all three
+                      [-1, 1, 2], [0, -1, 2], [0, 1, -1],                    # -1 in each position
+                      [nv, 1, 2], [0, nv, 2], [0, 1, nv], [0, 1, 2 ** 31]], dtype=np.int64)
+    want = topology_spec.valid_faces(faces, nv)
+    assert want.tolist() == [True, True] + [False] * 11
+    got = topology.valid_faces(torch.from_numpy(faces), nv)
+    assert got.dtype == torch.bool and got.shape == (13,) and np.array_equal(got.numpy(), want)
+    for order in (np.arange(13)[::-1].copy(), np.random.default_rng(3).permutation(13)):
+        assert np.array_equal(topology.valid_faces(torch.from_numpy(faces[order]), nv).numpy(), want[order])
+    assert not topology.valid_faces(torch.from_numpy(faces), 0).any()          # no vertices: no face is valid
+    empty = topology.valid_faces(torch.zeros(0, 3, dtype=torch.int64), nv)
+    assert empty.dtype == torch.bool and empty.shape == (0,)
+
+
+def test_used_rows_is_the_compaction_that_np_unique_gives():
+    import torch
+    from ppsurf_amd import topology
+    n = 9
+    for faces in (np.array([[2, 3, 5], [5, 3, 6], [6, 2, 2]], dtype=np.int64),       # rows 0, 1 (front), 4 (middle), 7, 8 (end) are skipped
+                  np.array([[8, 0, 4]], dtype=np.int64), np.arange(9, dtype=np.int64).reshape(3, 3)[::-1].copy(),
+                  np.zeros((0, 3), dtype=np.int64)):
+        used, remap = topology.used_rows(torch.from_numpy(faces), n)
+        rows, inverse = np.unique(faces, return_inverse=True)
+        assert used.dtype == torch.bool and remap.dtype == torch.int64 and used.shape == remap.shape == (n,)
+        assert np.array_equal(np.nonzero(used.numpy())[0], rows)
+        assert np.array_equal(remap[torch.from_numpy(faces)].numpy(), inverse.reshape(faces.shape))
+        assert np.array_equal(remap.numpy(), np.cumsum(used.numpy()) - 1)          # an unused row holds the last used one before it, -1 at the front
+    used, remap = topology.used_rows(torch.zeros(0, 3, dtype=torch.int64), 0)
+    assert used.dtype == torch.bool and remap.dtype == torch.int64 and used.shape == remap.shape == (0,)
 
 
 def test_read_mesh_file(tmp_path):

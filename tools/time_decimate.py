@@ -20,16 +20,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 sys.path.insert(0, os.path.join(REPO, 'tools'))
-from ppsurf_amd import decimate, geometry, mcubes, simplify, topology  # noqa: E402
-from time_smooth import wall_ms  # noqa: E402
-
-
-def sphere(R, dev):
-    g = torch.linspace(-0.5, 0.5, R, dtype=torch.float64, device=dev)
-    gx, gy, gz = torch.meshgrid(g, g, g, indexing='ij')
-    verts, faces = mcubes.marching_cubes_torch((0.35 - torch.sqrt(gx * gx + gy * gy + gz * gz)).contiguous(), 0.0)
-    verts, faces = mcubes.clean_mesh_torch(verts.to(torch.float32).to(torch.float64), faces, min_component_faces=6, welded=True, grid_coords=True)
-    return (verts * (1.0 / (R - 1)) - 0.5).float().contiguous(), faces.contiguous()
+from ppsurf_amd import decimate, geometry, simplify, topology  # noqa: E402
+from timing import parts_of, sphere, wall_ms  # noqa: E402
 
 
 def quality(verts, faces, query, cell):
@@ -67,17 +59,8 @@ def main():
         med, low = wall_ms(lambda: decimate.decimate_mesh(verts, faces, budget), args.reps)
         rounds = max(info['rounds'], 1)
         print('                 end to end median {:.2f} ms  min {:.2f} ms; {} rounds, {:.3f} ms per round'.format(med, low, info['rounds'], med / rounds))
-        parts, last = {}, [None, 0.0]
-
-        def timer(name):
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            if last[0] is not None:
-                parts[last[0]] = parts.get(last[0], 0.0) + (now - last[1]) * 1e3
-            last[0], last[1] = name, now
         v, f = topology.checked_mesh('time_decimate', verts, faces, limit=True)
-        decimate._decimate_rows(v, f, budget, 1000, timer=timer)
-        timer(None)
+        parts = parts_of(lambda timer: decimate._decimate_rows(v, f, budget, 1000, timer=timer))
         total = sum(parts.values())
         print('                 one run with a synchronise between the parts, {:.2f} ms: '.format(total) +
               ', '.join('{} {:.2f} ms ({:.0f} %)'.format(k, parts[k], 100.0 * parts[k] / total) for k in ('rows', 'kernels', 'select', 'apply', 'output')))

@@ -20,8 +20,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 sys.path.insert(0, os.path.join(REPO, 'tools'))
 from ppsurf_amd import decimate, denoise, fill, intersect, simplify, smooth, trim  # noqa: E402
-from time_decimate import sphere  # noqa: E402
-from time_smooth import wall_ms  # noqa: E402
+from timing import parts_of, sphere, wall_ms  # noqa: E402
 
 PARTS = ('boxes', 'lists', 'count', 'emit', 'output')
 SHIFT = (0.25, 0.04, 0.02)
@@ -31,16 +30,7 @@ def parts_ms(verts, faces, reps):
     """{part: median ms} over `reps` runs (after one warm-up) of one walk with a synchronise between the parts."""
     rows = []
     for rep in range(reps + 1):
-        parts, last = {}, [None, 0.0]
-
-        def timer(part):
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            if last[0] is not None:
-                parts[last[0]] = parts.get(last[0], 0.0) + (now - last[1]) * 1e3
-            last[0], last[1] = part, now
-        intersect._walk(verts, faces, intersect.MAX_PAIRS, True, timer=timer)
-        timer(None)
+        parts = parts_of(lambda timer: intersect._walk(verts, faces, intersect.MAX_PAIRS, True, timer=timer))
         if rep > 0:
             rows.append(parts)
     return {p: float(np.median([r.get(p, 0.0) for r in rows])) for p in PARTS}

@@ -21,7 +21,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 from ppsurf_amd import _lib, manifold, mcubes, pieces, topology  # noqa: E402
 import manifold_spec as S  # noqa: E402
-from time_smooth import device_ms, wall_ms  # noqa: E402
+from timing import device_ms, wall_ms  # noqa: E402
 
 BATCH = 20
 

@@ -18,34 +18,10 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 from ppsurf_amd import _lib, mcubes, normals, ops, topology  # noqa: E402
 import normals_spec as N  # noqa: E402
+from timing import device_ms, wall_ms  # noqa: E402
 
 
 BATCH = 100
-
-
-def device_ms(fn, reps):
-    times = []
-    for rep in range(reps + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if rep > 0:                                   # the first round warms up (code objects, allocator)
-            times.append(e0.elapsed_time(e1))
-    return float(np.median(times)), float(np.min(times))
-
-
-def wall_ms(fn, reps):
-    times = []
-    for rep in range(reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if rep > 0:
-            times.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(times)), float(np.min(times))
 
 
 def main():

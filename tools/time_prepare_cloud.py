@@ -18,6 +18,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 from ppsurf_amd import cloud, ops  # noqa: E402
 import cloud_spec as S  # noqa: E402
+from timing import device_ms, wall_ms  # noqa: E402
 
 
 def torus_scan(n, seed=1):
@@ -25,31 +26,6 @@ def torus_scan(n, seed=1):
     u, v = rng.rand(n) * 2 * np.pi, rng.rand(n) * 2 * np.pi
     p = np.stack([(1.0 + 0.3 * np.cos(v)) * np.cos(u), (1.0 + 0.3 * np.cos(v)) * np.sin(u), 0.3 * np.sin(v)], axis=1)
     return (p + 0.002 * rng.randn(n, 3)) * 20.0 + np.array([512345.0, 5403210.0, 310.0])
-
-
-def device_ms(fn, reps):
-    times = []
-    for rep in range(reps + 1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if rep > 0:                                   # the first round warms up (code objects, allocator)
-            times.append(e0.elapsed_time(e1))
-    return float(np.median(times)), float(np.min(times))
-
-
-def wall_ms(fn, reps):
-    times = []
-    for rep in range(reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if rep > 0:
-            times.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(times)), float(np.min(times))
 
 
 def main():

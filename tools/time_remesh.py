@@ -19,9 +19,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 sys.path.insert(0, os.path.join(REPO, 'tools'))
-from ppsurf_amd import decimate, intersect, remesh, smooth, topology  # noqa: E402
-from time_decimate import sphere  # noqa: E402
-from time_smooth import wall_ms  # noqa: E402
+from ppsurf_amd import decimate, intersect, remesh, smooth, subdivide, topology  # noqa: E402
+from timing import parts_of, sphere, wall_ms  # noqa: E402
 
 BINS = (0, 10, 20, 30, 40, 50, 60, 90, 120, 180.0001)
 
@@ -39,21 +38,6 @@ def quality(verts, faces):
             'smallest_angle': float(a.min()), 'corners_below_30': float((a < 30.0).mean()), 'edge_cv': float(e.std() / e.mean()),
             'edge_min_med_max': [float(e.min() / med), med, float(e.max() / med)],
             'crossing_pairs': intersect.self_intersections(verts, faces)[1]['pairs']}
-
-
-def parts_of(run):
-    """{part: ms} of one run of run(timer) with a synchronise between the parts."""
-    parts, last = {}, [None, 0.0]
-
-    def timer(name):
-        torch.cuda.synchronize()
-        now = time.perf_counter()
-        if last[0] is not None:
-            parts[last[0]] = parts.get(last[0], 0.0) + (now - last[1]) * 1e3
-        last[0], last[1] = name, now
-    run(timer)
-    timer(None)
-    return parts
 
 
 def shown(parts):
@@ -104,7 +88,7 @@ def main():
     import remesh_spec as R
     small_v, small_f = sphere(args.cpu_res, dev)
     hv, hf = small_v.cpu().numpy(), small_f.cpu().numpy()
-    low, high = 0.8 * remesh._median_edge(small_v, small_f), 4.0 / 3.0 * remesh._median_edge(small_v, small_f)
+    low, high = 0.8 * subdivide.median_edge(small_v, small_f), 4.0 / 3.0 * subdivide.median_edge(small_v, small_f)
     for name, device, spec in (('remesh_isotropic', lambda: remesh.remesh_isotropic(small_v, small_f, factor=args.factor, iters=args.iters),
                                 lambda: R.remesh_spec(hv, hf, factor=args.factor, iters=args.iters)),
                                ('collapse_short_edges', lambda: remesh.collapse_short_edges(small_v, small_f, low, high),

@@ -18,8 +18,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 sys.path.insert(0, os.path.join(REPO, 'tools'))
 from ppsurf_amd import decimate, subdivide, topology  # noqa: E402
-from time_decimate import sphere  # noqa: E402
-from time_smooth import wall_ms  # noqa: E402
+from timing import parts_of, sphere, wall_ms  # noqa: E402
 
 FACTORS = (0.5, 1.0)
 
@@ -48,17 +47,8 @@ def run_case(name, verts, faces, factor, reps):
     evaluations = info['rounds'] + 1
     print('              end to end median {:.2f} ms  min {:.2f} ms; {} rounds and one last evaluation, {:.3f} ms per evaluation'.format(
         med, low, info['rounds'], med / evaluations))
-    parts, last = {}, [None, 0.0]
-
-    def timer(part):
-        torch.cuda.synchronize()
-        now = time.perf_counter()
-        if last[0] is not None:
-            parts[last[0]] = parts.get(last[0], 0.0) + (now - last[1]) * 1e3
-        last[0], last[1] = part, now
     v, f = topology.checked_mesh('time_subdivide', verts, faces, limit=True)
-    subdivide._subdivided(v, f, None, factor, 100, subdivide.MAX_FACES, timer=timer)
-    timer(None)
+    parts = parts_of(lambda timer: subdivide._subdivided(v, f, None, factor, 100, subdivide.MAX_FACES, timer=timer))
     total = sum(parts.values())
     print('              one run with a synchronise between the parts, {:.2f} ms (the sort of the given faces under sort, the median under kernels): '.format(total) +
           ', '.join('{} {:.2f} ms ({:.0f} %)'.format(k, parts.get(k, 0.0), 100.0 * parts.get(k, 0.0) / total) for k in ('sort', 'kernels', 'emit', 'output')))

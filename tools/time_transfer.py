@@ -18,18 +18,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 from ppsurf_amd import ops, transfer  # noqa: E402
 import transfer_spec as T  # noqa: E402
-
-
-def wall_ms(fn, reps):
-    times = []
-    for rep in range(reps + 1):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        if rep > 0:                                   # the first round warms up (code objects, allocator)
-            times.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(times)), float(np.min(times))
+from timing import wall_ms  # noqa: E402
 
 
 def main():

@@ -20,7 +20,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 from ppsurf_amd import _lib, mcubes, trim, weld  # noqa: E402
 import weld_spec as S  # noqa: E402
-from time_smooth import device_ms, wall_ms  # noqa: E402
+from timing import device_ms, wall_ms  # noqa: E402
 
 BATCH = 20
 
